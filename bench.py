@@ -11,10 +11,20 @@ SURVEY.md 8d, inputs resident in HBM.  With N > 1 ranks every rank renders a dif
 replicated scene and the step ends with the RCCL exchange of parameter gradients + densification statistics
 (reduced-3dgs_amd/multiview.py), i.e. weak scaling in views.
 
-Rank 0 prints ONE JSON line: metric/value = whole-job training iterations (views) per second; plus
-`roofline` for the dominant kernel (algorithmic bytes of SURVEY.md 8d / its HIP-event duration measured
-inside the timed region by the library's stage timers), `cpu_baseline` (N=1 only) and `host` (what the host
-side of the run looked like: CPU quota of the container, throttling during the timed region, per-step host time).
+Rank 0 prints ONE JSON line: metric/value = whole-job training iterations (views) per second, ms_per_step = one
+timed step, `config` and `host` (what the host side of the run looked like: CPU quota of the container, throttling
+during the timed region, per-step host time).  A plain run does only that: set up, warm up, time the K steps.
+
+--full adds everything else behind the timed region: the instrumented per-stage pass (`stages`), `roofline` for the
+dominant kernel (algorithmic bytes of SURVEY.md 8d / its HIP-event duration measured inside the timed region by the
+library's stage timers), `iter_roofline`, render-only throughput, the lambda_sh_sparsity and reference-mode legs,
+`cpu_baseline` (N=1 only) and, for N > 1, the exchange alone, the replica check, the compact transports and the
+overlapped form.
+
+--dump-outputs DIR writes what the last timed step computed -- the image, radii and the gradients autograd hands
+back -- as DIR/<name>.npy in float32 (a fixed, seeded sample of the Gaussians' rows when the whole would exceed
+DUMP_BUDGET_BYTES, with the sample's indices in gaussian_index.npy, float64), so that two builds can be compared output
+for output.  The inputs depend on the arguments only.  out/ is ignored by git and a good place for DIR.
 """
 import argparse
 import json
@@ -50,6 +60,31 @@ KERNEL_STATS = os.path.join("profiles", f"{PROFILE_ROUND}_kernel_stats_bench_500
 
 
 CLOCK_WARMUP_STEPS = 50   # untimed, ahead of the --warmup steps (see main())
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 12345         # which Gaussians' rows are written when they do not all fit
+
+
+def dump_outputs(out_dir, color, radii, means2D_grad, grads):
+    """Writes one step's outputs as float32 .npy files: the image whole, the per-Gaussian arrays (radii, the gradient
+    of the screen-space means and of every parameter) for all Gaussians or, past DUMP_BUDGET_BYTES, for the same fixed,
+    seeded, sorted sample of them (its indices in gaussian_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    image = color.detach().float().cpu().numpy()
+    rows = {"radii": radii.float(), "grad_means2D": means2D_grad}
+    rows.update({f"grad_{k}": v for k, v in grads.items()})
+    rows = {k: v for k, v in rows.items() if v is not None}   # a leaf no visible Gaussian reached has no gradient
+    P = radii.shape[0]
+    row_bytes = sum(4 * (v[0].numel() if v.dim() > 1 else 1) for v in rows.values())
+    n = min(P, (DUMP_BUDGET_BYTES - image.nbytes) // (row_bytes + 8))
+    idx = None
+    if n < P:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(P, size=n, replace=False))
+        np.save(os.path.join(out_dir, "gaussian_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "color.npy"), image)
+    sel = None if idx is None else torch.from_numpy(idx).to(radii.device)
+    for name, t in rows.items():
+        t = t.detach().float()
+        np.save(os.path.join(out_dir, f"{name}.npy"), (t if sel is None else t.index_select(0, sel)).cpu().numpy())
 
 
 def stage_bytes(P, R, N, Tn, Kbar):
@@ -306,8 +341,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cameras", type=int, default=8)
     ap.add_argument("--main-only", action="store_true",
-                    help="only the timed region and its instrumented pass: no render-only, lambda_sh_sparsity or reference-mode "
+                    help="with --full: only the timed region and its instrumented pass: no render-only, lambda_sh_sparsity or reference-mode "
                          "leg -- for rocprofv3 passes, whose per-kernel means would otherwise mix those legs' launches in")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything the headline does not need (per-stage pass, roofline, render-only, "
+                         "sparsity and reference-mode legs, CPU baseline, N > 1 exchange forms); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (image, radii, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
     cg_warm0 = cgroup_cpu()   # throttling seen from here to the timed region decides whether to align with a period
     ncpu = effective_cpus()
@@ -361,6 +401,7 @@ def main():
         _C.set_gradient_arena(exch.arena)   # parameter gradients are written straight into the exchange buffer
 
     born_in_buffer = [None]
+    last = {}            # --dump-outputs: the last timed step's color, radii and screen-space mean gradient
     pending = [None]     # exchange of the previous step still in flight
     # N > 1: the timed region (-> `value`) runs the SERIALISED exchange: step k's sums are complete before step k+1
     # starts, i.e. "all-reduce before the optimizer / prune step" as BASELINE.json words it.  The overlapped form (step
@@ -371,7 +412,7 @@ def main():
     def cam_index(step):
         return (step * world + rank) % len(cams)
 
-    def train_step(step, lam=0.0):
+    def train_step(step, lam=0.0, keep=False):
         for t in leaves.values():
             t.grad = None
         means2D = torch.zeros_like(leaves["means3D"], requires_grad=True) + 0  # gaussian_renderer/__init__.py:27
@@ -380,6 +421,8 @@ def main():
                                                leaves["opacity"], leaves["scales"], leaves["rotations"], empty,
                                                settings[cam_index(step)], lam)
         color.backward(dl)
+        if keep:   # --dump-outputs: the last timed step's outputs
+            last.update(color=color.detach(), radii=radii, means2D_grad=means2D.grad)
         if exch is not None:
             grads = {k: v.grad for k, v in leaves.items()}
             if step == 0:   # reported once: did autograd keep the arena views as .grad (zero-copy pack)?
@@ -455,11 +498,12 @@ def main():
     cg0 = cgroup_cpu()
     host_ms = []
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    keep_at = args.steps - 1 if args.dump_outputs else -1
     t0 = time.perf_counter()
     ev0.record()
     for i in range(args.steps):
         th = time.perf_counter()
-        train_step(args.warmup + i)
+        train_step(args.warmup + i, keep=i == keep_at)
         host_ms.append(1e3 * (time.perf_counter() - th))
     drain()
     ev1.record()
@@ -477,18 +521,23 @@ def main():
     overflow1 = _C.reserve_overflow_events()
     prof_timed = _C.profile_read()
     _C.profile_enable(False)
-    # second, untimed pass with every stage timer on: the per-stage breakdown
-    _C.profile_enable(True)
-    for i in range(min(args.steps, 20)):
-        train_step(args.warmup + i)
-    drain()
-    torch.cuda.synchronize()
-    prof = _C.profile_read()
-    _C.profile_enable(False)
+    if args.dump_outputs and rank == 0:   # the last timed step's outputs, before any further step replaces them
+        dump_outputs(args.dump_outputs, last["color"], last["radii"], last["means2D_grad"],
+                     {k: v.grad for k, v in leaves.items()})
+    prof = {}
+    if args.full:
+        # second, untimed pass with every stage timer on: the per-stage breakdown
+        _C.profile_enable(True)
+        for i in range(min(args.steps, 20)):
+            train_step(args.warmup + i)
+        drain()
+        torch.cuda.synchronize()
+        prof = _C.profile_read()
+        _C.profile_enable(False)
     # N > 1: the exchange alone (events around a synchronous exchange), whether every replica ended up with the same
     # bits, and the same K steps in the overlapped (one-step-late) form
     exchange_ms = overlapped_ms_per_step = replicas_identical = exchange_forms = None
-    if exch is not None:
+    if exch is not None and args.full:
         n_x = min(args.steps, 10)
         xa, xb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         barrier()
@@ -595,23 +644,25 @@ def main():
         elapsed = float(t.item())
 
     # render-only throughput (render.py's FPS path: forward under no_grad), after the timed region
-    with torch.no_grad():
-        torch.cuda.synchronize()
-        tr0 = time.perf_counter()
-        for i in range(0 if args.main_only else args.steps):
-            s_ = settings[cam_index(i)]
-            _C.rasterize_gaussians(s_.bg, leaves["means3D"], empty, leaves["opacity"], leaves["scales"],
-                                   leaves["rotations"], 1.0, empty, s_.viewmatrix, s_.projmatrix, s_.tanfovx,
-                                   s_.tanfovy, H, W, leaves["sh"], degrees, s_.campos, False, False)
-        torch.cuda.synchronize()
-        render_s = time.perf_counter() - tr0
+    render_s = None
+    if args.full and not args.main_only:
+        with torch.no_grad():
+            torch.cuda.synchronize()
+            tr0 = time.perf_counter()
+            for i in range(args.steps):
+                s_ = settings[cam_index(i)]
+                _C.rasterize_gaussians(s_.bg, leaves["means3D"], empty, leaves["opacity"], leaves["scales"],
+                                       leaves["rotations"], 1.0, empty, s_.viewmatrix, s_.projmatrix, s_.tanfovx,
+                                       s_.tanfovy, H, W, leaves["sh"], degrees, s_.campos, False, False)
+            torch.cuda.synchronize()
+            render_s = time.perf_counter() - tr0
 
     # The method's own configuration (full_eval.py:33,44: every paper run trains with --lambda_sh_sparsity=0.1): the same K
     # steps with the SH L1 term on -- the per-Gaussian backward then reads the SH rows (signs of the coefficients) instead
     # of the direction derivatives the forward left.  A second number; `value` stays lambda = 0,
     # the default of arguments/__init__.py:94.
     sparsity = None
-    if world == 1 and not args.main_only:
+    if args.full and world == 1 and not args.main_only:
         lam = 0.1
         for i in range(5):
             train_step(i, lam)
@@ -642,7 +693,7 @@ def main():
     # stays the default mode.  (the driver's record then holds the rate of the mode a CUDA build can be
     # compared with at 1e-4.)
     reference_mode = None
-    if world == 1 and not args.main_only:
+    if args.full and world == 1 and not args.main_only:
         was_tight, was_f64 = _C.set_tight_rects(False), _C.set_f64_chain(False)
         try:
             with torch.no_grad():   # the longer lists' pair counts, per camera (and the reservation learns them)
@@ -686,92 +737,7 @@ def main():
     R_mean = float(np.mean([Rs[k] for k in used]))
     V_mean = float(np.mean([Vs[k] for k in used]))
     pairs_mean = float(np.mean([Ps[k] for k in used]))
-    sb = stage_bytes(P, R_mean, N, Tn, Kbar)
-    id_bits, tile_bits = max(1, int(np.ceil(np.log2(max(P, 2))))), max(1, int(np.ceil(np.log2(max(Tn, 2)))))
-    word_bytes, key_bytes = (4, 4) if id_bits + tile_bits <= 32 else ((6, 2) if Tn <= 65536 else (8, 8))
-    own = own_stage_bytes(P, V_mean, pairs_mean, N, Tn, Kbar, word_bytes, key_bytes,
-                          passes=2 if tile_bits <= 14 else -(-tile_bits // 8))
-    kernel_ms_events = None   # the backward blend kernel alone, HIP events of the instrumented pass
-    if prof.get("blend_bwd_kernel", (0, 0))[1]:
-        kernel_ms_events = prof["blend_bwd_kernel"][0] / prof["blend_bwd_kernel"][1]
-    stages = {}
-    for name, (ms, cnt) in prof.items():
-        if cnt and name != "blend_bwd_kernel":
-            avg_ms = ms / cnt
-            b = sb.get(name, 0)   # "sh_color" only exists as a stage of its own on the generic-sort path
-            # alg_GBps: SURVEY 8d's reference-algorithm bytes of the stage / its time.  NOT a bandwidth: bytes the library
-            # never moves (the reference's 64-bit key sort, its per-Gaussian fills) count, so it can exceed the HBM peak;
-            # counter_GBps: the bytes the committed rocprofv3 counters of this workload saw move / this run's time
-            tr = pmc_traffic(name, args.workload)
-            ob = own.get(name)
-            stages[name] = {"avg_ms": round(avg_ms, 4), "launches": cnt, "alg_bytes": int(b),
-                            "alg_GBps": round(b / (avg_ms * 1e-3) / 1e9, 1),
-                            # own_alg_*: the bytes THIS build's algorithm has to move (own_stage_bytes: pairs binned, no 64-bit
-                            # sort, no fills) -- a rate that cannot exceed the HBM peak; alg_* is the reference's algorithm
-                            "own_alg_bytes": int(ob) if ob is not None else None,
-                            "own_alg_GBps": round(ob / (avg_ms * 1e-3) / 1e9, 1) if ob is not None else None,
-                            "counter_bytes": tr,
-                            "counter_GBps": round(tr / (avg_ms * 1e-3) / 1e9, 1) if tr is not None else None,
-                            "counter_over_own_alg": round(tr / ob, 2) if (tr is not None and ob) else None}
-    dom = max(stages, key=lambda k: stages[k]["avg_ms"]) if stages else None
-    roofline = None
-    if dom:
-        A = stages[dom]["alg_GBps"]
-        traffic = pmc_traffic(dom, args.workload)
-        # kernel_frac: SURVEY 8d's bytes of the dominant KERNEL alone (R * 76 + N * 20 for the backward blend) over the
-        # kernel's own duration between HIP events of this run's timed region -- what a reader recomputes from the
-        # rocprofv3 kernel trace; frac: the whole stage's bytes over the stage's events (unit order + kernel + pair reduction)
-        kernel_alg = R_mean * 76 + N * 20 if dom == "blend_bwd" else None
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": A, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(A / HBM_PEAK_GBS, 4),
-                    "kernel_name": STAGE_KERNELS[dom][0][0] if dom in STAGE_KERNELS else None,
-                    "kernel_ms": round(kernel_ms_events, 4) if (kernel_ms_events and dom == "blend_bwd") else None,
-                    "kernel_alg_bytes": int(kernel_alg) if kernel_alg else None,
-                    "kernel_achieved": (round(kernel_alg / (kernel_ms_events * 1e-3) / 1e9, 1)
-                                        if (kernel_alg and kernel_ms_events and dom == "blend_bwd") else None),
-                    "kernel_frac": (round(kernel_alg / (kernel_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                    if (kernel_alg and kernel_ms_events and dom == "blend_bwd") else None),
-                    "traffic": traffic,
-                    "traffic_source": (PMC_SUMMARIES[args.workload] + " (committed rocprofv3 --pmc passes of this command; "
-                                       "not collected in this run)") if traffic is not None else None,
-                    "traffic_collected_on_this_build": pmc_matches_build(pmc_path(args.workload)) if traffic is not None else None,
-                    "duration_source": "HIP events around the stage on its stream, inside the timed region",
-                    "kernel_ms_source": "HIP events around the kernel alone, instrumented pass of this run (behind the timed region)",
-                    "valu": pmc_valu(dom, args.workload, stages[dom]["avg_ms"],
-                                     kernel_ms_events=kernel_ms_events if dom == "blend_bwd" else None)}
     iters_per_s = args.steps * world / elapsed
-    B_iter = P * (718 + 36 * Kbar) + R_mean * 280 + N * 40
-    gpu_ms = sum(v["avg_ms"] for v in stages.values())
-    per_stage_traffic = [pmc_traffic(k, args.workload) for k in STAGE_KERNELS]
-    counter_bytes = int(sum(per_stage_traffic)) if all(t is not None for t in per_stage_traffic) else None
-    # speed of light of this build's own algorithm: the VALU-bound stages at the calibrated issue floor of their main
-    # kernel, every other stage at the bytes it has to move (own_stage_bytes) over the achievable HBM rate
-    sol_parts, sol_ok = {}, bool(stages)
-    for name in stages:
-        if name in VALU_BOUND_STAGES:
-            v_ = pmc_valu(name, args.workload, stages[name]["avg_ms"])
-            if v_ is None:
-                sol_ok = False
-            else:
-                sol_parts[name] = v_["floor_ms"]
-        elif stages[name]["own_alg_bytes"] is not None:
-            sol_parts[name] = stages[name]["own_alg_bytes"] / (HBM_ACHIEVABLE_GBS * 1e9) * 1e3
-    sol_ms = sum(sol_parts.values()) if sol_ok else None
-    hs = sorted(host_ms)
-    host = {"cpus_visible": os.cpu_count(), "cpus_effective": ncpu,
-            "loadavg": [round(x, 1) for x in os.getloadavg()],
-            "host_ms_per_step_min_med_max": [round(hs[0], 3), round(hs[len(hs) // 2], 3), round(hs[-1], 3)],
-            "enqueue_ms_total": round(1e3 * (t_enq - t0), 3),
-            "gpu_event_ms_per_step": round(gpu_event_ms / args.steps, 4),   # first to last kernel of the timed region
-            "gpu_stage_ms_sum": round(gpu_ms, 4),
-            "step_over_gpu_stage_sum": round(1e3 * elapsed / args.steps / gpu_ms, 3) if gpu_ms else None}
-    if cg0 and cg1:
-        host["cgroup"] = {"quota_cpus": cg1["quota_cpus"],
-                          "throttled_periods_in_timed_region": cg1["nr_throttled"] - cg0["nr_throttled"],
-                          "throttled_ms_in_timed_region": round((cg1["throttled_usec"] - cg0["throttled_usec"]) / 1e3, 2),
-                          "cpu_ms_in_timed_region": round((cg1["usage_usec"] - cg0["usage_usec"]) / 1e3, 2),
-                          "throttled_periods_before_timed_region": cg_w["nr_throttled"] - cg_warm0["nr_throttled"] if cg_w and cg_warm0 else None,
-                          "timed_region_started_at_period_rollover": cfs_aligned}
     result = {
         "metric": "train iters/s (fwd+bwd) + Mpix/s render, 500k Gaussians @1600x1062",
         "value": round(iters_per_s, 2), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
@@ -799,45 +765,134 @@ def main():
                    "passes_in_timed_region": {k: stats1[k] - stats0[k] for k in
                                               ("reserved_passes", "exact_passes", "redone_passes")}},
         "value_serialised": round(iters_per_s, 2) if world > 1 else None,
-        "value_overlapped": round(args.steps * world / (overlapped_ms_per_step * 1e-3 * args.steps), 2)
-        if overlapped_ms_per_step else None,
-        "exchange_ms": round(exchange_ms, 4) if exchange_ms is not None else None,
-        # bytes ONE rank sends per step (both phases, all peers); exchange_forms: the same for the opt-in compact transports,
-        # measured the same way, each with the bytes / time model's prediction (multiview.exchange_model)
-        "exchange_bytes_per_rank": exch.bytes_per_rank() if exch is not None else None,
-        "exchange_forms": exchange_forms,
-        "step_ms_exchange_overlapped": round(overlapped_ms_per_step, 4) if overlapped_ms_per_step is not None else None,
-        "overlap_frac": (round(max(0.0, min(1.0, (1e3 * elapsed / args.steps - overlapped_ms_per_step) / exchange_ms)), 3)
-                         if exchange_ms and overlapped_ms_per_step else None),
-        "render_mpix_per_s": round(args.steps * N / render_s / 1e6, 1) if not args.main_only else None,
-        "render_fps": round(args.steps / render_s, 1) if not args.main_only else None,
-        "roofline": roofline,
-        # frac_of_8TBps: SURVEY 8d's reference-algorithm bytes (work this library avoids counts in its favour) -- NOT HBM
-        # utilisation; frac_counter_traffic: the bytes the committed rocprofv3 counters saw move, per step, over the same time
-        "iter_roofline": {"B_iter_bytes": int(B_iter), "achieved_GBps": round(B_iter * iters_per_s / world / 1e9, 1),
-                          "frac_of_8TBps": round(B_iter * iters_per_s / world / 8e12, 4),
-                          "counter_traffic_bytes": counter_bytes,
-                          "frac_counter_traffic": (round(counter_bytes * iters_per_s / world / 8e12, 4)
-                                                   if counter_bytes else None),
-                          "counter_traffic_source": PMC_SUMMARIES.get(args.workload) if counter_bytes else None,
-                          # sum over the stages of: the VALU issue floor (blend kernels) / own-algorithm bytes at 6.3 TB/s
-                          "speed_of_light_ms": round(sol_ms, 4) if sol_ms else None,
-                          "speed_of_light_parts_ms": {k: round(v, 4) for k, v in sol_parts.items()} if sol_ms else None,
-                          "frac_of_speed_of_light": round(sol_ms / (1e3 * elapsed / args.steps), 3) if sol_ms else None,
-                          "own_alg_bytes": int(sum(v["own_alg_bytes"] or 0 for v in stages.values())),
-                          "speed_of_light_assumes": f"{HBM_ACHIEVABLE_GBS / 1e3} TB/s for the HBM-bound stages; "
-                                                    f"VALU floors from {PMC_SUMMARIES.get(args.workload)}"},
-        "value_sh_sparsity": sparsity["value"] if sparsity else None,
-        "sh_sparsity": sparsity,
-        "value_reference_mode": reference_mode["value"] if reference_mode else None,
-        "reference_mode": reference_mode,
-        "ambiguous_profile_kernels": AMBIGUOUS_KERNELS or None,
-        "stages": stages,
-        "stages_note": f"{dom_stage}: HIP events inside the timed region; other stages: separate instrumented pass",
-        "host": host,
     }
+    gpu_ms = None
+    if args.full:
+        sb = stage_bytes(P, R_mean, N, Tn, Kbar)
+        id_bits, tile_bits = max(1, int(np.ceil(np.log2(max(P, 2))))), max(1, int(np.ceil(np.log2(max(Tn, 2)))))
+        word_bytes, key_bytes = (4, 4) if id_bits + tile_bits <= 32 else ((6, 2) if Tn <= 65536 else (8, 8))
+        own = own_stage_bytes(P, V_mean, pairs_mean, N, Tn, Kbar, word_bytes, key_bytes,
+                              passes=2 if tile_bits <= 14 else -(-tile_bits // 8))
+        kernel_ms_events = None   # the backward blend kernel alone, HIP events of the instrumented pass
+        if prof.get("blend_bwd_kernel", (0, 0))[1]:
+            kernel_ms_events = prof["blend_bwd_kernel"][0] / prof["blend_bwd_kernel"][1]
+        stages = {}
+        for name, (ms, cnt) in prof.items():
+            if cnt and name != "blend_bwd_kernel":
+                avg_ms = ms / cnt
+                b = sb.get(name, 0)   # "sh_color" only exists as a stage of its own on the generic-sort path
+                # alg_GBps: SURVEY 8d's reference-algorithm bytes of the stage / its time.  NOT a bandwidth: bytes the library
+                # never moves (the reference's 64-bit key sort, its per-Gaussian fills) count, so it can exceed the HBM peak;
+                # counter_GBps: the bytes the committed rocprofv3 counters of this workload saw move / this run's time
+                tr = pmc_traffic(name, args.workload)
+                ob = own.get(name)
+                stages[name] = {"avg_ms": round(avg_ms, 4), "launches": cnt, "alg_bytes": int(b),
+                                "alg_GBps": round(b / (avg_ms * 1e-3) / 1e9, 1),
+                                # own_alg_*: the bytes THIS build's algorithm has to move (own_stage_bytes: pairs binned, no 64-bit
+                                # sort, no fills) -- a rate that cannot exceed the HBM peak; alg_* is the reference's algorithm
+                                "own_alg_bytes": int(ob) if ob is not None else None,
+                                "own_alg_GBps": round(ob / (avg_ms * 1e-3) / 1e9, 1) if ob is not None else None,
+                                "counter_bytes": tr,
+                                "counter_GBps": round(tr / (avg_ms * 1e-3) / 1e9, 1) if tr is not None else None,
+                                "counter_over_own_alg": round(tr / ob, 2) if (tr is not None and ob) else None}
+        dom = max(stages, key=lambda k: stages[k]["avg_ms"]) if stages else None
+        roofline = None
+        if dom:
+            A = stages[dom]["alg_GBps"]
+            traffic = pmc_traffic(dom, args.workload)
+            # kernel_frac: SURVEY 8d's bytes of the dominant KERNEL alone (R * 76 + N * 20 for the backward blend) over the
+            # kernel's own duration between HIP events of this run's timed region -- what a reader recomputes from the
+            # rocprofv3 kernel trace; frac: the whole stage's bytes over the stage's events (unit order + kernel + pair reduction)
+            kernel_alg = R_mean * 76 + N * 20 if dom == "blend_bwd" else None
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": A, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(A / HBM_PEAK_GBS, 4),
+                        "kernel_name": STAGE_KERNELS[dom][0][0] if dom in STAGE_KERNELS else None,
+                        "kernel_ms": round(kernel_ms_events, 4) if (kernel_ms_events and dom == "blend_bwd") else None,
+                        "kernel_alg_bytes": int(kernel_alg) if kernel_alg else None,
+                        "kernel_achieved": (round(kernel_alg / (kernel_ms_events * 1e-3) / 1e9, 1)
+                                            if (kernel_alg and kernel_ms_events and dom == "blend_bwd") else None),
+                        "kernel_frac": (round(kernel_alg / (kernel_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                        if (kernel_alg and kernel_ms_events and dom == "blend_bwd") else None),
+                        "traffic": traffic,
+                        "traffic_source": (PMC_SUMMARIES[args.workload] + " (committed rocprofv3 --pmc passes of this command; "
+                                           "not collected in this run)") if traffic is not None else None,
+                        "traffic_collected_on_this_build": pmc_matches_build(pmc_path(args.workload)) if traffic is not None else None,
+                        "duration_source": "HIP events around the stage on its stream, inside the timed region",
+                        "kernel_ms_source": "HIP events around the kernel alone, instrumented pass of this run (behind the timed region)",
+                        "valu": pmc_valu(dom, args.workload, stages[dom]["avg_ms"],
+                                         kernel_ms_events=kernel_ms_events if dom == "blend_bwd" else None)}
+        B_iter = P * (718 + 36 * Kbar) + R_mean * 280 + N * 40
+        gpu_ms = sum(v["avg_ms"] for v in stages.values())
+        per_stage_traffic = [pmc_traffic(k, args.workload) for k in STAGE_KERNELS]
+        counter_bytes = int(sum(per_stage_traffic)) if all(t is not None for t in per_stage_traffic) else None
+        # speed of light of this build's own algorithm: the VALU-bound stages at the calibrated issue floor of their main
+        # kernel, every other stage at the bytes it has to move (own_stage_bytes) over the achievable HBM rate
+        sol_parts, sol_ok = {}, bool(stages)
+        for name in stages:
+            if name in VALU_BOUND_STAGES:
+                v_ = pmc_valu(name, args.workload, stages[name]["avg_ms"])
+                if v_ is None:
+                    sol_ok = False
+                else:
+                    sol_parts[name] = v_["floor_ms"]
+            elif stages[name]["own_alg_bytes"] is not None:
+                sol_parts[name] = stages[name]["own_alg_bytes"] / (HBM_ACHIEVABLE_GBS * 1e9) * 1e3
+        sol_ms = sum(sol_parts.values()) if sol_ok else None
+        result.update({
+            "value_overlapped": round(args.steps * world / (overlapped_ms_per_step * 1e-3 * args.steps), 2)
+            if overlapped_ms_per_step else None,
+            "exchange_ms": round(exchange_ms, 4) if exchange_ms is not None else None,
+            # bytes ONE rank sends per step (both phases, all peers); exchange_forms: the same for the opt-in compact transports,
+            # measured the same way, each with the bytes / time model's prediction (multiview.exchange_model)
+            "exchange_bytes_per_rank": exch.bytes_per_rank() if exch is not None else None,
+            "exchange_forms": exchange_forms,
+            "step_ms_exchange_overlapped": round(overlapped_ms_per_step, 4) if overlapped_ms_per_step is not None else None,
+            "overlap_frac": (round(max(0.0, min(1.0, (1e3 * elapsed / args.steps - overlapped_ms_per_step) / exchange_ms)), 3)
+                             if exchange_ms and overlapped_ms_per_step else None),
+            "render_mpix_per_s": round(args.steps * N / render_s / 1e6, 1) if not args.main_only else None,
+            "render_fps": round(args.steps / render_s, 1) if not args.main_only else None,
+            "roofline": roofline,
+            # frac_of_8TBps: SURVEY 8d's reference-algorithm bytes (work this library avoids counts in its favour) -- NOT HBM
+            # utilisation; frac_counter_traffic: the bytes the committed rocprofv3 counters saw move, per step, over the same time
+            "iter_roofline": {"B_iter_bytes": int(B_iter), "achieved_GBps": round(B_iter * iters_per_s / world / 1e9, 1),
+                              "frac_of_8TBps": round(B_iter * iters_per_s / world / 8e12, 4),
+                              "counter_traffic_bytes": counter_bytes,
+                              "frac_counter_traffic": (round(counter_bytes * iters_per_s / world / 8e12, 4)
+                                                       if counter_bytes else None),
+                              "counter_traffic_source": PMC_SUMMARIES.get(args.workload) if counter_bytes else None,
+                              # sum over the stages of: the VALU issue floor (blend kernels) / own-algorithm bytes at 6.3 TB/s
+                              "speed_of_light_ms": round(sol_ms, 4) if sol_ms else None,
+                              "speed_of_light_parts_ms": {k: round(v, 4) for k, v in sol_parts.items()} if sol_ms else None,
+                              "frac_of_speed_of_light": round(sol_ms / (1e3 * elapsed / args.steps), 3) if sol_ms else None,
+                              "own_alg_bytes": int(sum(v["own_alg_bytes"] or 0 for v in stages.values())),
+                              "speed_of_light_assumes": f"{HBM_ACHIEVABLE_GBS / 1e3} TB/s for the HBM-bound stages; "
+                                                        f"VALU floors from {PMC_SUMMARIES.get(args.workload)}"},
+            "value_sh_sparsity": sparsity["value"] if sparsity else None,
+            "sh_sparsity": sparsity,
+            "value_reference_mode": reference_mode["value"] if reference_mode else None,
+            "reference_mode": reference_mode,
+            "ambiguous_profile_kernels": AMBIGUOUS_KERNELS or None,
+            "stages": stages,
+            "stages_note": f"{dom_stage}: HIP events inside the timed region; other stages: separate instrumented pass",
+        })
+    hs = sorted(host_ms)
+    host = {"cpus_visible": os.cpu_count(), "cpus_effective": ncpu,
+            "loadavg": [round(x, 1) for x in os.getloadavg()],
+            "host_ms_per_step_min_med_max": [round(hs[0], 3), round(hs[len(hs) // 2], 3), round(hs[-1], 3)],
+            "enqueue_ms_total": round(1e3 * (t_enq - t0), 3),
+            "gpu_event_ms_per_step": round(gpu_event_ms / args.steps, 4),   # first to last kernel of the timed region
+            "gpu_stage_ms_sum": round(gpu_ms, 4) if gpu_ms is not None else None,
+            "step_over_gpu_stage_sum": round(1e3 * elapsed / args.steps / gpu_ms, 3) if gpu_ms else None}
+    if cg0 and cg1:
+        host["cgroup"] = {"quota_cpus": cg1["quota_cpus"],
+                          "throttled_periods_in_timed_region": cg1["nr_throttled"] - cg0["nr_throttled"],
+                          "throttled_ms_in_timed_region": round((cg1["throttled_usec"] - cg0["throttled_usec"]) / 1e3, 2),
+                          "cpu_ms_in_timed_region": round((cg1["usage_usec"] - cg0["usage_usec"]) / 1e3, 2),
+                          "throttled_periods_before_timed_region": cg_w["nr_throttled"] - cg_warm0["nr_throttled"] if cg_w and cg_warm0 else None,
+                          "timed_region_started_at_period_rollover": cfs_aligned}
+    result["host"] = host
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.workload, W, H, g, cams[0], ncpu)
 
     if rank == 0:

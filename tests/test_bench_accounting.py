@@ -94,3 +94,40 @@ def test_exchange_model_arithmetic():
     s = m(2_000_000, 8, 1.25, sparse=True, union_frac=0.5, sh_rest_bf16=True)
     assert s["rows"] == 1_000_000 and s["exchange_ms"] < m(2_000_000, 8, 1.25, sh_rest_bf16=True)["exchange_ms"]
     assert m(500_000, 1, 0.67)["speedup"] == 1.0
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array float32 (the sample's indices float64), all rows while they fit, else the same
+    seeded sample of Gaussians on every call, and never more bytes than DUMP_BUDGET_BYTES."""
+    import numpy as np
+    import torch
+    import bench
+    P, H, W = 5000, 24, 32
+    g = torch.Generator().manual_seed(0)
+    color = torch.rand(3, H, W, generator=g)
+    radii = torch.randint(0, 9, (P,), generator=g, dtype=torch.int32)
+    m2 = torch.randn(P, 3, generator=g)
+    grads = {"means3D": torch.randn(P, 3, generator=g), "opacity": torch.randn(P, 1, generator=g),
+             "sh": torch.randn(P, 16, 3, generator=g), "scales": None}
+    names = {"color", "radii", "grad_means2D", "grad_means3D", "grad_opacity", "grad_sh"}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    bench.dump_outputs(str(tmp_path / "all"), color, radii, m2, grads)
+    full = load(tmp_path / "all")
+    assert set(full) == names and all(a.dtype == np.float32 for a in full.values())
+    assert np.array_equal(full["color"], color.numpy()) and np.array_equal(full["radii"], radii.numpy().astype(np.float32))
+    assert full["grad_sh"].shape == (P, 16, 3)
+
+    row_bytes = 4 * (1 + 3 + 3 + 1 + 48)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", color.numel() * 4 + 1000 * (row_bytes + 8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), color, radii, m2, grads)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert set(a) == names | {"gaussian_index"} and a["gaussian_index"].dtype == np.float64
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+    idx = a["gaussian_index"].astype(np.int64)
+    assert len(idx) == 1000 and np.all(np.diff(idx) > 0) and np.array_equal(idx, b["gaussian_index"])
+    for k in names - {"color"}:
+        assert np.array_equal(a[k], full[k][idx]) and np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["color"], full["color"])

@@ -1,7 +1,7 @@
 """Debug aid: when and where every workgroup of the backward blend ran (build: python tools/build_variant.py tl blend.hip --
 -DR3_TIMELINE; run with R3DGS_LIB=tl) -- or, with the argument `fwd`, of the forward blend (variant tlf, -DR3_TIMELINE_FWD;
 one workgroup per 8x8 quadrant there).  Prints the distribution of workgroup durations, the resident workgroups over
-time and the per-SIMD load; saves the raw table to gpurun_out/bwd_timeline.npy."""
+time and the per-SIMD load; saves the raw table to $R3DGS_OUT/bwd_timeline.npy (default out/)."""
 import ctypes as C
 import os
 import sys
@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("R3DGS_OUT", "out")   # the folder the tools/*.sh scripts write into (relative to ROOT, or absolute)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "reduced-3dgs_amd")]
 FWD = len(sys.argv) > 1 and sys.argv[1] == "fwd"
 os.environ.setdefault("R3DGS_LIB", "tlf" if FWD else "tl")
@@ -37,8 +38,8 @@ rc = _C._lib.r3dgs_debug_timeline(tab.ctypes.data_as(C.c_void_p), C.c_int(n))
 assert rc == 0, rc
 tab = tab[tab[:, 1] > 0]   # workgroups beyond the pass's unit count (and tiles nothing contributed to) leave no record
 n = len(tab)
-os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-np.save(os.path.join(ROOT, "gpurun_out", "fwd_timeline.npy" if FWD else "bwd_timeline.npy"), tab)
+os.makedirs(os.path.join(ROOT, OUT), exist_ok=True)
+np.save(os.path.join(ROOT, OUT, "fwd_timeline.npy" if FWD else "bwd_timeline.npy"), tab)
 t0, t1, hw, lmax = (tab[:, k].astype(np.int64) for k in range(4))
 xcc = (hw >> 32) & 15          # HW_REG_XCC_ID
 hw = hw & 0xFFFFFFFF           # HW_REG_HW_ID: wave slot [3:0], simd [5:4], cu [11:8], sh [12], se [15:13]

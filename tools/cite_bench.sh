@@ -1,7 +1,10 @@
 set -u
 export PYTHONPATH=$PWD:$PWD/reduced-3dgs_amd TMPDIR=/tmp
-mkdir -p gpurun_out
-( timeout 240 python bench.py --steps 20 --warmup 5 ) > gpurun_out/bench.log 2>&1; echo "bench20 rc=$?"
-( timeout 240 python bench.py ) > gpurun_out/bench_default.log 2>&1; echo "bench50 rc=$?"
-bash tools/other_workloads.sh > gpurun_out/other.log 2>&1
-tail -1 gpurun_out/bench.log | cut -c1-300
+# logs, traces and summaries of this script: $R3DGS_OUT, relative to the repository root (the working directory) or
+# absolute, default out/; made absolute here so that steps run from another directory and the Python tools agree
+OUT=${R3DGS_OUT:-out}; case $OUT in /*) ;; *) OUT=$PWD/$OUT ;; esac; export R3DGS_OUT=$OUT
+mkdir -p $OUT
+( timeout 240 python bench.py --full --steps 20 --warmup 5 ) > $OUT/bench.log 2>&1; echo "bench20 rc=$?"
+( timeout 240 python bench.py --full ) > $OUT/bench_default.log 2>&1; echo "bench50 rc=$?"
+bash tools/other_workloads.sh > $OUT/other.log 2>&1
+tail -1 $OUT/bench.log | cut -c1-300

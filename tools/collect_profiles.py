@@ -1,11 +1,12 @@
-"""Copies the outputs of tools/refresh_profiles.sh (gpurun_out/) into profiles/r06_* and regenerates profiles/README.md."""
+"""Copies the outputs of tools/refresh_profiles.sh ($R3DGS_OUT, default out/) into profiles/r06_* and regenerates profiles/README.md."""
 import os
 import shutil
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+OUT = os.environ.get("R3DGS_OUT", "out")   # the folder the tools/*.sh scripts write into (relative to ROOT, or absolute)
+G, P = os.path.join(ROOT, OUT), os.path.join(ROOT, "profiles")
 R = "r06"
 
 

@@ -1,11 +1,11 @@
 """Per-kernel means of the rocprofv3 --pmc passes written by tools/gpu_round.sh (PMC="...;...") into
-gpurun_out/pmc*/..._counter_collection.csv  ->  one JSON {kernel: {counter: mean per launch}}.
+$R3DGS_OUT/pmc*/..._counter_collection.csv (default out/)  ->  one JSON {kernel: {counter: mean per launch}}.
 
-    python tools/pmc_summary.py [out.json [dir-prefix]]   (default: gpurun_out/pmc_summary.json from gpurun_out/pmc*;
-                                                          a prefix such as pmc2M_ takes gpurun_out/pmc2M_*)
+    python tools/pmc_summary.py [out.json [dir-prefix]]   (default: $R3DGS_OUT/pmc_summary.json from $R3DGS_OUT/pmc*;
+                                                          a prefix such as pmc2M_ takes $R3DGS_OUT/pmc2M_*)
 
 Only kernels of this library (r3::*) are kept; template arguments stay in the name, parameter lists are cut.
-Every pass is a separate run of `bench.py --steps 3 --warmup 1`, so the launch counts of the passes agree."""
+Every pass is a separate run of `bench.py --full --steps 3 --warmup 1`, so the launch counts of the passes agree."""
 import csv
 import glob
 import json
@@ -15,6 +15,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("R3DGS_OUT", "out")   # the folder the tools/*.sh scripts write into (relative to ROOT, or absolute)
 
 
 def short(name):
@@ -32,10 +33,10 @@ def short(name):
 
 
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "pmc_summary.json")
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, OUT, "pmc_summary.json")
     prefix = sys.argv[2] if len(sys.argv) > 2 else "pmc"
     acc = defaultdict(lambda: defaultdict(lambda: [0.0, 0]))
-    dirs = [d for d in glob.glob(os.path.join(ROOT, "gpurun_out", prefix + "*")) if os.path.isdir(d) and
+    dirs = [d for d in glob.glob(os.path.join(ROOT, OUT, prefix + "*")) if os.path.isdir(d) and
             (prefix != "pmc" or os.path.basename(d)[3:].isdigit())]   # plain "pmc": pmc0, pmc1 ... only
     for path in sorted(p_ for d in dirs for p_ in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)):
         per_dispatch = defaultdict(float)   # a counter is reported once per XCD/SE instance: sum them per dispatch

@@ -131,7 +131,7 @@ new = f'''# profiles/ — measurements on MI355X (round 6)
 
 Every `{R}_*` file comes from visits of `tools/refresh_profiles.sh` to a 1-GPU MI355X box (gfx950, ROCm 7.2, torch 2.10+rocm7.0;
 256 visible CPUs, **cgroup CPU quota 16**); `tools/collect_profiles.py` copies the results here and runs this generator
-(`tools/profiles_readme.py`), so the numbers below are the ones in the files.  The command profiled is `python bench.py`
+(`tools/profiles_readme.py`), so the numbers below are the ones in the files.  The command profiled is `python bench.py --full`
 (workload `metric_500k_1600x1062`: 500 000 Gaussians, 1600×1062, SH degree 3, SURVEY.md §8d recipe, 8 cameras; V̄ =
 {d50['config']['visible_mean'] / 1e3:.0f}k visible, `num_rendered` R̄ = {d50['config']['num_rendered_mean'] / 1e6:.2f} M — the reference's count, which the byte formulas are
 written in — of which {d50['config']['pairs_binned_mean'] / 1e6:.2f} M (tile, Gaussian) pairs are binned, N = 1.70 Mpix) unless a workload is named.  These are
@@ -141,11 +141,11 @@ previous round's library (`R3DGS_LIB=old`) run beside the new one where rounds a
 
 | file | what |
 |---|---|
-| `{R}_bench_n1_default.json`, `{R}_bench_n1_steps20.json` | the JSON line of `python bench.py` (50 steps, 10 warm-up) and of the driver's form (`--steps 20 --warmup 5`) |
+| `{R}_bench_n1_default.json`, `{R}_bench_n1_steps20.json` | the JSON line of `python bench.py --full` (50 steps, 10 warm-up) and of the driver's form (`--steps 20 --warmup 5`) |
 | `{R}_bench_n1_ab.jsonl` | the driver's form with `R3DGS_STRICT=0`, `R3DGS_TIGHT_RECT=0` (the reference's 3σ squares), `R3DGS_BWD_SEG=0` (whole tile lists: no list segments) and `R3DGS_F64_CHAIN=0` (the reference's fp32 covariance chain), in this order |
 | `{R}_bench_n1_cpu_burner64.jsonl` | the driver's form twice while `tools/cpu_burn.py 64` exhausts the container's CPU quota |
-| `{R}_kernel_stats_*.csv` | `rocprofv3 --kernel-trace --stats` of `bench.py --steps 10 --warmup 3` on the metric workload, the clustered 500 k scene, 2 M, 6 M @1920×1080 and the clustered 2 M scene |
-| `{R}_pmc_summary.json` | (`tools/pmc_summary.py`) per-kernel means of four separate `rocprofv3 --kernel-trace --pmc …` passes (VALU instructions by class; SQ activity / wait / LDS counters; `FETCH_SIZE`; `WRITE_SIZE`) of `bench.py --steps 3 --warmup 1`; `bench.py` cites it as `roofline.traffic`, `roofline.valu`, `stages.*.counter_bytes` |
+| `{R}_kernel_stats_*.csv` | `rocprofv3 --kernel-trace --stats` of `bench.py --full --steps 10 --warmup 3` on the metric workload, the clustered 500 k scene, 2 M, 6 M @1920×1080 and the clustered 2 M scene |
+| `{R}_pmc_summary.json` | (`tools/pmc_summary.py`) per-kernel means of four separate `rocprofv3 --kernel-trace --pmc …` passes (VALU instructions by class; SQ activity / wait / LDS counters; `FETCH_SIZE`; `WRITE_SIZE`) of `bench.py --full --steps 3 --warmup 1`; `bench.py` cites it as `roofline.traffic`, `roofline.valu`, `stages.*.counter_bytes` |
 | `{R}_pmc_summary_2M.json`, `_6M.json`, `_clustered_500k.json` | the `FETCH_SIZE` / `WRITE_SIZE` passes of the same command on those workloads (`bench.py --workload …` cites them) |
 | `{R}_ab_round5_vs_round6.txt` | five workloads through round 5's library and this round's, alternating, in one visit |
 | `{R}_other_workloads.jsonl` | `tools/other_workloads.sh`: bench.py lines of the configs[0..4] stand-ins and of the two clustered scenes |
