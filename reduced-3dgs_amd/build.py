@@ -36,10 +36,12 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     # max-ilp scheduling: blend_bwd 0.497 -> 0.484 ms, blend_fwd 0.179 -> 0.176 (max-memory-clause: no change; -O2: worse;
     # with SLP vectorisation: 0.76 / 0.20)
     "blend.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
+    "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "capi.hip": [],
 }
-HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
-           os.path.join("..", "..", "include", "r3dgs_reduction.h")]
+HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
+           os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h")]
 
 
 def _newest(paths):
@@ -93,9 +95,9 @@ def build_torch_binding(force=False, verbose=True):
     import sysconfig
 
     import torch
-    hdr = os.path.join(HERE, "..", "include", "r3dgs_rasterizer.h")
+    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
-            os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(hdr), os.path.getmtime(torch.__file__)):
+            [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT
     tdir = os.path.dirname(torch.__file__)
     cxx = os.environ.get("CXX", "g++")

@@ -9,7 +9,7 @@
 // cache, one reservation advisor -- whichever build R3DGS_LIB selected; an unbound module refuses every call.
 //
 // Scope: the two calls a training step makes -- the asynchronous forward (r3dgs_forward_reserved + the strict-mode check
-// of the pass header) and the backward.  Everything else (exact-size path, ragged inference forward, counter mode, the
+// of the pass header) and the backward -- plus the fused training loss of r3dgs_loss.h (r3dgs_loss.py).  Everything else (exact-size path, ragged inference forward, counter mode, the
 // reduction operators, debug accessors) stays in the ctypes module diff_gaussian_rasterization/_C.py, which calls this
 // one when it is built (R3DGS_BINDING=ctypes forces the pure-ctypes route).  Why it exists: at small scenes the step is
 // host-bound and the ctypes marshalling of ~35 arguments per call is a third of it.
@@ -29,6 +29,7 @@
 #include <string>
 #include <tuple>
 
+#include "r3dgs_loss.h"
 #include "r3dgs_rasterizer.h"
 
 namespace {
@@ -50,6 +51,12 @@ struct Api {
     R3_FN(r3dgs_pass_query)
     R3_FN(r3dgs_backward)
     R3_FN(r3dgs_mark_visible)
+    R3_FN(r3dgs_l1_ssim_workspace_bytes)
+    R3_FN(r3dgs_l1_ssim_forward)
+    R3_FN(r3dgs_l1_ssim_backward)
+    R3_FN(r3dgs_l1_workspace_bytes)
+    R3_FN(r3dgs_l1_forward)
+    R3_FN(r3dgs_l1_backward)
 #undef R3_FN
     bool bound = false;
 } api;
@@ -75,6 +82,19 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_FN(r3dgs_backward)
     R3_FN(r3dgs_mark_visible)
 #undef R3_FN
+    // the fused loss (r3dgs_loss.h) is optional: an older A/B build of the library has none, and its calls then refuse
+#define R3_OPT(name)                                                                        \
+    {                                                                                       \
+        auto it = addr.find(#name);                                                         \
+        api.name = it == addr.end() ? nullptr : reinterpret_cast<decltype(api.name)>(it->second); \
+    }
+    R3_OPT(r3dgs_l1_ssim_workspace_bytes)
+    R3_OPT(r3dgs_l1_ssim_forward)
+    R3_OPT(r3dgs_l1_ssim_backward)
+    R3_OPT(r3dgs_l1_workspace_bytes)
+    R3_OPT(r3dgs_l1_forward)
+    R3_OPT(r3dgs_l1_backward)
+#undef R3_OPT
     api.bound = true;
 }
 
@@ -251,6 +271,83 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
     return present;
 }
 
+// ---- fused L1 + D-SSIM loss (r3dgs_loss.h): the same calls as diff_gaussian_rasterization/_C.py's l1_ssim_* / l1_*;
+// r3dgs_loss.py has checked the inputs (device fp32, contiguous, same shape).  Absent optional tensors are empty.
+
+void need_loss()
+{
+    need_bound();
+    if (!api.r3dgs_l1_ssim_forward) throw std::runtime_error("the loaded libr3dgs_hip.so has no fused loss: rebuild it with build.py");
+}
+
+void* cur_stream(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> l1_ssim_forward(
+    const Tensor& img1, const Tensor& img2, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials,
+    bool want_map)
+{
+    need_loss();
+    const c10::Device dev = img1.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    Tensor l1 = at::empty({}, f32), ssim = at::empty({}, f32), loss = at::empty({}, f32), dssim = at::empty({}, f32);
+    Tensor per_image = at::empty({B}, f32);
+    Tensor ssim_map = want_map ? at::empty({B, C, H, W}, f32) : at::empty({0}, f32);
+    Tensor partials = want_partials ? at::empty({3, B, C, H, W}, f32) : at::empty({0}, f32);
+    const size_t ws_bytes = api.r3dgs_l1_ssim_workspace_bytes((int)B, (int)C, (int)H, (int)W);
+    if (ws_bytes == 0) throw std::runtime_error("l1_ssim_forward: invalid shape");
+    Tensor ws = at::empty({(int64_t)ws_bytes}, f32.dtype(at::kByte));
+    if (api.r3dgs_l1_ssim_forward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
+                                  (float)lambda_dssim, l1.data_ptr<float>(), ssim.data_ptr<float>(), per_image.data_ptr<float>(),
+                                  loss.data_ptr<float>(), dssim.data_ptr<float>(), want_map ? ssim_map.data_ptr<float>() : nullptr,
+                                  want_partials ? partials.data_ptr<float>() : nullptr, reinterpret_cast<char*>(ws.data_ptr()), cur_stream(dev)) < 0)
+        fail("l1_ssim_forward");
+    return {l1, ssim, loss, dssim, per_image, ssim_map, partials};
+}
+
+Tensor l1_ssim_backward(const Tensor& img1, const Tensor& img2, const Tensor& partials, const Tensor& grad_l1, double coef_l1,
+                        const Tensor& grad_ssim, int64_t ssim_grad_mode, double coef_ssim, int64_t B, int64_t C, int64_t H,
+                        int64_t W)
+{
+    need_loss();
+    const c10::Device dev = img1.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor dx = at::empty({B, C, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    if (api.r3dgs_l1_ssim_backward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
+                                   opt_ptr<float>(partials), opt_ptr<float>(grad_l1), (float)coef_l1, opt_ptr<float>(grad_ssim),
+                                   (int)ssim_grad_mode, (float)coef_ssim, dx.data_ptr<float>(), cur_stream(dev)) < 0)
+        fail("l1_ssim_backward");
+    return dx;
+}
+
+Tensor l1_forward(const Tensor& x, const Tensor& y)
+{
+    need_loss();
+    const c10::Device dev = x.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    Tensor out = at::empty({}, f32);
+    const size_t ws_bytes = api.r3dgs_l1_workspace_bytes(x.numel());
+    if (ws_bytes == 0) throw std::runtime_error("l1_forward: invalid element count");
+    Tensor ws = at::empty({(int64_t)ws_bytes}, f32.dtype(at::kByte));
+    if (api.r3dgs_l1_forward(x.numel(), x.data_ptr<float>(), y.data_ptr<float>(), out.data_ptr<float>(),
+                             reinterpret_cast<char*>(ws.data_ptr()), cur_stream(dev)) < 0)
+        fail("l1_forward");
+    return out;
+}
+
+Tensor l1_backward(const Tensor& x, const Tensor& y, const Tensor& grad)
+{
+    need_loss();
+    const c10::Device dev = x.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor dx = at::empty_like(x);
+    if (api.r3dgs_l1_backward(x.numel(), x.data_ptr<float>(), y.data_ptr<float>(), grad.data_ptr<float>(), dx.data_ptr<float>(),
+                              cur_stream(dev)) < 0)
+        fail("l1_backward");
+    return dx;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -260,6 +357,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("forward_reserved", &forward_reserved);
     m.def("backward", &backward);
     m.def("mark_visible", &mark_visible);
+    m.def("l1_ssim_forward", &l1_ssim_forward);
+    m.def("l1_ssim_backward", &l1_ssim_backward);
+    m.def("l1_forward", &l1_forward);
+    m.def("l1_backward", &l1_backward);
     m.def("library_version", []() {
         need_bound();
         return std::string(api.r3dgs_version());

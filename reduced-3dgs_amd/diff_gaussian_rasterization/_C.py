@@ -109,6 +109,21 @@ _lib.r3dgs_reduce_shards.argtypes = [_i, C.c_longlong, C.c_longlong, C.c_longlon
 if hasattr(_lib, "r3dgs_reduce_shards_mixed"):   # (absent from an older A/B build loaded through R3DGS_LIB)
     _lib.r3dgs_reduce_shards_mixed.restype = _i
     _lib.r3dgs_reduce_shards_mixed.argtypes = [_i, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _vp, _vp, _vp]
+if hasattr(_lib, "r3dgs_l1_ssim_forward"):   # fused L1 + D-SSIM loss (include/r3dgs_loss.h; absent from older A/B builds)
+    _lib.r3dgs_ssim_window.restype = None
+    _lib.r3dgs_ssim_window.argtypes = [_vp]
+    _lib.r3dgs_l1_ssim_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_l1_ssim_workspace_bytes.argtypes = [_i, _i, _i, _i]
+    _lib.r3dgs_l1_ssim_forward.restype = _i
+    _lib.r3dgs_l1_ssim_forward.argtypes = [_i, _i, _i, _i, _vp, _vp, _f] + [_vp] * 9
+    _lib.r3dgs_l1_ssim_backward.restype = _i
+    _lib.r3dgs_l1_ssim_backward.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _vp, _vp]
+    _lib.r3dgs_l1_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_l1_workspace_bytes.argtypes = [C.c_longlong]
+    _lib.r3dgs_l1_forward.restype = _i
+    _lib.r3dgs_l1_forward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
+    _lib.r3dgs_l1_backward.restype = _i
+    _lib.r3dgs_l1_backward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
 _lib.r3dgs_profile_enable.argtypes = [_i]
 _lib.r3dgs_profile_stage_name.restype = C.c_char_p
 _lib.r3dgs_profile_stage_name.argtypes = [_i]
@@ -122,6 +137,8 @@ LIBRARY_PATH = _LIB_PATH
 _EXT_FUNCS = ("r3dgs_last_error", "r3dgs_version", "r3dgs_geometry_bytes", "r3dgs_geometry_bytes_lean", "r3dgs_binning_bytes",
               "r3dgs_image_bytes", "r3dgs_forward_hint", "r3dgs_reserve_hint_view", "r3dgs_forward_reserved",
               "r3dgs_pass_query", "r3dgs_backward", "r3dgs_mark_visible")
+_EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3dgs_l1_ssim_backward", "r3dgs_l1_workspace_bytes",
+                   "r3dgs_l1_forward", "r3dgs_l1_backward")   # optional: an older A/B build has no loss
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -130,7 +147,8 @@ if _binding_request not in ("auto", "torch", "ctypes"):
 if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
-        _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value for n in _EXT_FUNCS})
+        _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value
+                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS if hasattr(_lib, f))})
         _ext = _ext_loaded
     except ImportError:
         if _binding_request == "torch":
@@ -983,3 +1001,88 @@ def reduce_shards_mixed(recv, world, shard_begin, sum_len, half_end, out):
     with _on_device(dev):
         _check(_lib.r3dgs_reduce_shards_mixed(int(world), shard, int(shard_begin), int(sum_len), int(half_end),
                                               recv.data_ptr(), out.data_ptr(), _stream()), "reduce_shards_mixed")
+
+
+# ---- fused L1 + D-SSIM training loss (include/r3dgs_loss.h, csrc/loss.hip); the autograd surface is r3dgs_loss.py.
+# Inputs are checked there (device fp32, contiguous, same shape); these calls only allocate and launch, on the current
+# stream, without a host synchronisation, so a forward + backward pair can be captured in a graph.
+
+def _need_loss():
+    if not hasattr(_lib, "r3dgs_l1_ssim_forward"):
+        raise RuntimeError(f"{_LIB_PATH} has no fused loss (r3dgs_l1_ssim_forward): rebuild it with build.py")
+
+
+def ssim_window():
+    """The 11 fp32 weights of the reference's 1-D SSIM window (utils/loss_utils.py:24-26), computed on the host."""
+    _need_loss()
+    w = (C.c_float * 11)()
+    _lib.r3dgs_ssim_window(w)
+    return np.array(w[:], np.float32)
+
+
+def l1_ssim_forward(img1, img2, B, Cc, H, W, lambda_dssim, want_partials, want_map):
+    """-> (l1, ssim, loss, dssim, ssim_image[B], ssim_map or empty, partials[3,B,C,H,W] or empty); 0-d tensors for the
+    scalars.  One tile kernel + one fixed-order reduction."""
+    _need_loss()
+    if _ext is not None:
+        return _ext.l1_ssim_forward(img1, img2, B, Cc, H, W, float(lambda_dssim), bool(want_partials), bool(want_map))
+    dev = img1.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    l1, ssim, loss, dssim = (torch.empty((), **f32) for _ in range(4))
+    per_image = torch.empty((B,), **f32)
+    ssim_map = torch.empty((B, Cc, H, W), **f32) if want_map else _NO_TENSOR
+    partials = torch.empty((3, B, Cc, H, W), **f32) if want_partials else _NO_TENSOR
+    with _on_device(dev):
+        ws_bytes = _lib.r3dgs_l1_ssim_workspace_bytes(B, Cc, H, W)
+        if ws_bytes == 0:
+            raise RuntimeError(f"l1_ssim_forward: invalid shape {B}x{Cc}x{H}x{W}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_l1_ssim_forward(B, Cc, H, W, _ptr(img1), _ptr(img2), float(lambda_dssim), _ptr(l1), _ptr(ssim),
+                                          _ptr(per_image), _ptr(loss), _ptr(dssim), _ptr(ssim_map), _ptr(partials),
+                                          _ptr(ws), _stream()), "l1_ssim_forward")
+    return l1, ssim, loss, dssim, per_image, ssim_map, partials
+
+
+def l1_ssim_backward(img1, img2, partials, grad_l1, coef_l1, grad_ssim, ssim_grad_mode, coef_ssim, B, Cc, H, W):
+    """-> d/d img1 [B,C,H,W] (r3dgs_l1_ssim_backward).  grad_l1 / grad_ssim: device tensors (empty: absent);
+    ssim_grad_mode 0: scalar upstream of the mean, 1: per image [B], 2: per pixel [B,C,H,W]."""
+    _need_loss()
+    if _ext is not None:
+        return _ext.l1_ssim_backward(img1, img2, partials, grad_l1, float(coef_l1), grad_ssim, int(ssim_grad_mode),
+                                     float(coef_ssim), B, Cc, H, W)
+    dev = img1.device
+    dx = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(_lib.r3dgs_l1_ssim_backward(B, Cc, H, W, _ptr(img1), _ptr(img2), _ptr(partials), _ptr(grad_l1),
+                                           float(coef_l1), _ptr(grad_ssim), int(ssim_grad_mode), float(coef_ssim), _ptr(dx),
+                                           _stream()), "l1_ssim_backward")
+    return dx
+
+
+def l1_forward(x, y):
+    """mean |x - y| over all elements (0-d tensor): one chunk kernel + the fixed-order reduction."""
+    _need_loss()
+    if _ext is not None:
+        return _ext.l1_forward(x, y)
+    dev = x.device
+    n = x.numel()
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        ws_bytes = _lib.r3dgs_l1_workspace_bytes(n)
+        if ws_bytes == 0:
+            raise RuntimeError(f"l1_forward: invalid element count {n}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_l1_forward(n, _ptr(x), _ptr(y), _ptr(out), _ptr(ws), _stream()), "l1_forward")
+    return out
+
+
+def l1_backward(x, y, grad):
+    """grad[0] * sign(x - y) / n, shaped like x."""
+    _need_loss()
+    if _ext is not None:
+        return _ext.l1_backward(x, y, grad)
+    dev = x.device
+    dx = torch.empty_like(x)
+    with _on_device(dev):
+        _check(_lib.r3dgs_l1_backward(x.numel(), _ptr(x), _ptr(y), _ptr(grad), _ptr(dx), _stream()), "l1_backward")
+    return dx
