@@ -38,10 +38,14 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "blend.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's
+    # kernels perform written out (adam_math.h)
+    "optim.hip": EXACT,
     "capi.hip": [],
 }
-HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
-           os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h")]
+HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
+           os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),
+           os.path.join("..", "..", "include", "r3dgs_optim.h")]
 
 
 def _newest(paths):
@@ -95,7 +99,7 @@ def build_torch_binding(force=False, verbose=True):
     import sysconfig
 
     import torch
-    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h")]
+    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
             [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT

@@ -9,7 +9,8 @@
 // cache, one reservation advisor -- whichever build R3DGS_LIB selected; an unbound module refuses every call.
 //
 // Scope: the two calls a training step makes -- the asynchronous forward (r3dgs_forward_reserved + the strict-mode check
-// of the pass header) and the backward -- plus the fused training loss of r3dgs_loss.h (r3dgs_loss.py).  Everything else (exact-size path, ragged inference forward, counter mode, the
+// of the pass header) and the backward -- plus the fused training loss of r3dgs_loss.h (r3dgs_loss.py) and the fused Adam
+// step of r3dgs_optim.h (r3dgs_optim.py).  Everything else (exact-size path, ragged inference forward, counter mode, the
 // reduction operators, debug accessors) stays in the ctypes module diff_gaussian_rasterization/_C.py, which calls this
 // one when it is built (R3DGS_BINDING=ctypes forces the pure-ctypes route).  Why it exists: at small scenes the step is
 // host-bound and the ctypes marshalling of ~35 arguments per call is a third of it.
@@ -28,8 +29,10 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "r3dgs_loss.h"
+#include "r3dgs_optim.h"
 #include "r3dgs_rasterizer.h"
 
 namespace {
@@ -57,6 +60,8 @@ struct Api {
     R3_FN(r3dgs_l1_workspace_bytes)
     R3_FN(r3dgs_l1_forward)
     R3_FN(r3dgs_l1_backward)
+    R3_FN(r3dgs_adam_step)
+    R3_FN(r3dgs_adam_step_capturable)
 #undef R3_FN
     bool bound = false;
 } api;
@@ -94,6 +99,8 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_OPT(r3dgs_l1_workspace_bytes)
     R3_OPT(r3dgs_l1_forward)
     R3_OPT(r3dgs_l1_backward)
+    R3_OPT(r3dgs_adam_step)
+    R3_OPT(r3dgs_adam_step_capturable)
 #undef R3_OPT
     api.bound = true;
 }
@@ -348,6 +355,63 @@ Tensor l1_backward(const Tensor& x, const Tensor& y, const Tensor& grad)
     return dx;
 }
 
+// ---- fused Adam step (r3dgs_optim.h): the same calls as diff_gaussian_rasterization/_C.py's adam_step*; r3dgs_optim.py has
+// checked the tensors (one device, fp32, contiguous, matching sizes).  Scalars arrive as doubles and are rounded to fp32 once.
+
+void need_optim()
+{
+    need_bound();
+    if (!api.r3dgs_adam_step) throw std::runtime_error("the loaded libr3dgs_hip.so has no fused Adam: rebuild it with build.py");
+}
+
+void check_rows(size_t n, const std::vector<Tensor>& g, const std::vector<Tensor>& m, const std::vector<Tensor>& v,
+                size_t n_scalars, size_t per_row)
+{
+    if (g.size() != n || m.size() != n || v.size() != n || n_scalars != per_row * n)
+        throw std::runtime_error("adam_step: list lengths differ");
+}
+
+void adam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+               const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars)
+{
+    need_optim();
+    const size_t n = params.size();
+    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 6);
+    if (n == 0) return;
+    const c10::Device dev = params[0].device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    std::vector<r3dgs_adam_segment> segs(n);
+    for (size_t i = 0; i < n; i++) {
+        const double* s = &scalars[6 * i];
+        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
+                   exp_avg_sqs[i].data_ptr<float>(), (long long)params[i].numel(), (float)s[0], (float)s[1], (float)s[2],
+                   (float)s[3], (float)s[4], (float)s[5]};
+    }
+    if (api.r3dgs_adam_step((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step");
+}
+
+// scalars: lr_value, beta1, beta2, eps per row; lrs[i] an empty tensor or a 0-d device float32 lr
+void adam_step_capturable(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+                          const std::vector<Tensor>& exp_avg_sqs, const std::vector<Tensor>& steps, const std::vector<Tensor>& lrs,
+                          const std::vector<double>& scalars)
+{
+    need_optim();
+    const size_t n = params.size();
+    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 4);
+    if (steps.size() != n || lrs.size() != n) throw std::runtime_error("adam_step_capturable: list lengths differ");
+    if (n == 0) return;
+    const c10::Device dev = params[0].device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    std::vector<r3dgs_adam_capturable_segment> segs(n);
+    for (size_t i = 0; i < n; i++) {
+        const double* s = &scalars[4 * i];
+        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
+                   exp_avg_sqs[i].data_ptr<float>(), steps[i].data_ptr<float>(), opt_ptr<float>(lrs[i]),
+                   (long long)params[i].numel(), s[0], s[1], s[2], s[3]};
+    }
+    if (api.r3dgs_adam_step_capturable((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step_capturable");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -361,6 +425,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("l1_ssim_backward", &l1_ssim_backward);
     m.def("l1_forward", &l1_forward);
     m.def("l1_backward", &l1_backward);
+    m.def("adam_step", &adam_step);
+    m.def("adam_step_capturable", &adam_step_capturable);
     m.def("library_version", []() {
         need_bound();
         return std::string(api.r3dgs_version());

@@ -124,6 +124,24 @@ if hasattr(_lib, "r3dgs_l1_ssim_forward"):   # fused L1 + D-SSIM loss (include/r
     _lib.r3dgs_l1_forward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
     _lib.r3dgs_l1_backward.restype = _i
     _lib.r3dgs_l1_backward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
+
+
+class _AdamSegment(C.Structure):   # r3dgs_adam_segment (include/r3dgs_optim.h)
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("n", C.c_longlong),
+                ("lerp_weight", _f), ("beta2", _f), ("addcmul_value", _f), ("bc2_sqrt", _f), ("eps", _f), ("step_size", _f)]
+
+
+class _AdamCapturableSegment(C.Structure):   # r3dgs_adam_capturable_segment (include/r3dgs_optim.h)
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("step", _vp), ("lr", _vp),
+                ("n", C.c_longlong), ("lr_value", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
+
+
+if hasattr(_lib, "r3dgs_adam_step"):   # fused Adam step (include/r3dgs_optim.h; absent from older A/B builds)
+    _lib.r3dgs_adam_step.restype = _i
+    _lib.r3dgs_adam_step.argtypes = [_i, C.POINTER(_AdamSegment), _vp]
+    _lib.r3dgs_adam_step_capturable.restype = _i
+    _lib.r3dgs_adam_step_capturable.argtypes = [_i, C.POINTER(_AdamCapturableSegment), _vp]
 _lib.r3dgs_profile_enable.argtypes = [_i]
 _lib.r3dgs_profile_stage_name.restype = C.c_char_p
 _lib.r3dgs_profile_stage_name.argtypes = [_i]
@@ -138,7 +156,8 @@ _EXT_FUNCS = ("r3dgs_last_error", "r3dgs_version", "r3dgs_geometry_bytes", "r3dg
               "r3dgs_image_bytes", "r3dgs_forward_hint", "r3dgs_reserve_hint_view", "r3dgs_forward_reserved",
               "r3dgs_pass_query", "r3dgs_backward", "r3dgs_mark_visible")
 _EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3dgs_l1_ssim_backward", "r3dgs_l1_workspace_bytes",
-                   "r3dgs_l1_forward", "r3dgs_l1_backward")   # optional: an older A/B build has no loss
+                   "r3dgs_l1_forward", "r3dgs_l1_backward",   # optional: an older A/B build has no loss
+                   "r3dgs_adam_step", "r3dgs_adam_step_capturable")   # ... nor a fused Adam
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -1086,3 +1105,53 @@ def l1_backward(x, y, grad):
     with _on_device(dev):
         _check(_lib.r3dgs_l1_backward(x.numel(), _ptr(x), _ptr(y), _ptr(grad), _ptr(dx), _stream()), "l1_backward")
     return dx
+
+
+# ---- fused Adam step (include/r3dgs_optim.h, csrc/optim.hip); the optimizer is r3dgs_optim.Adam, which checks the tensors
+# (one device, fp32, contiguous, matching sizes) and computes the scalars.  One launch per 32 tensors on the current stream,
+# no host synchronisation.
+
+def _need_optim():
+    if not hasattr(_lib, "r3dgs_adam_step"):
+        raise RuntimeError(f"{_LIB_PATH} has no fused Adam (r3dgs_adam_step): rebuild it with build.py")
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars):
+    """One Adam step of the tensors (lists of equal length, params[0]'s device).  scalars: a flat list of six Python floats
+    per tensor -- 1 - beta1, beta2, 1 - beta2, bc2_sqrt, eps, step_size (r3dgs_adam_segment) -- each rounded to fp32 once."""
+    _need_optim()
+    if _ext is not None:
+        return _ext.adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars)
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n and len(scalars) == 6 * n):
+        raise RuntimeError("adam_step: list lengths differ")
+    if n == 0:
+        return None
+    segs = (_AdamSegment * n)()
+    for i in range(n):
+        segs[i] = _AdamSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(),
+                               params[i].numel(), *scalars[6 * i:6 * i + 6])
+    with _on_device(params[0].device):
+        _check(_lib.r3dgs_adam_step(n, segs, _stream()), "adam_step")
+    return None
+
+
+def adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars):
+    """The capturable step: steps[i] a device float32 count (read + 1, then bumped), lrs[i] a 0-d device float32 lr or an
+    empty tensor; scalars: a flat list of lr_value, beta1, beta2, eps per tensor (r3dgs_adam_capturable_segment)."""
+    _need_optim()
+    if _ext is not None:
+        return _ext.adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars)
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(lrs) == n and len(scalars) == 4 * n):
+        raise RuntimeError("adam_step_capturable: list lengths differ")
+    if n == 0:
+        return None
+    segs = (_AdamCapturableSegment * n)()
+    for i in range(n):
+        segs[i] = _AdamCapturableSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(),
+                                         exp_avg_sqs[i].data_ptr(), steps[i].data_ptr(), _ptr(lrs[i]), params[i].numel(),
+                                         *scalars[4 * i:4 * i + 4])
+    with _on_device(params[0].device):
+        _check(_lib.r3dgs_adam_step_capturable(n, segs, _stream()), "adam_step_capturable")
+    return None
