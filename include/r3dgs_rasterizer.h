@@ -234,6 +234,48 @@ int r3dgs_backward(int P, const int* D, int M, int R, const float* background, i
                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                    float lambda_sh_sparsity, int debug, void* stream);
 
+/* ---- raster from the model's raw parameters (extension) ---------------------------------------------------------------
+ * The same three calls taking the parameters as the reference's GaussianModel stores them (scene/gaussian_model.py):
+ *   features_dc [P,1,3] and features_rest [P,M-1,3] (NULL iff M == 1) instead of one joined `shs` [P,M,3];
+ *   scaling_raw [P,3]: LOG scales; rotation_raw [P,4]: UNNORMALISED quaternions -- the kernels apply exp and
+ *   F.normalize's q = raw / max(||raw||, 1e-12) after the load (csrc/param_math.h) and, in the backward, their fp32 backward
+ *   to dL_dscale / dL_drot (formed and rounded exactly as r3dgs_backward forms them) before the store, so the gradients
+ *   returned are those of the tensors passed in: dL_dfeatures_dc [P,1,3], dL_dfeatures_rest [P,M-1,3], dL_dscaling_raw
+ *   [P,3], dL_drotation_raw [P,4].  Every element of every output is written, as for r3dgs_backward.
+ * Everything else -- blobs, tickets, R, the asynchronous contract, numerics of the remaining outputs -- is that of the call
+ * each is named after; the states are interchangeable only within a family (a forward_params state goes to
+ * backward_params).  Not offered here: precomputed colours or covariances and the ragged inference forward.
+ * r3dgs_activate_params writes the activated values with the very functions the kernels use (either pair may be NULL):
+ * scales_out [P,3], rotations_out [P,4]; r3dgs_forward(..., scales_out, rotations_out, ...) on them and on the joined SH
+ * tensor gives the image, radii and binning of r3dgs_forward_params bit for bit. */
+int r3dgs_forward_params(r3dgs_alloc_fn geometryBuffer, void* geometry_user, r3dgs_alloc_fn binningBuffer,
+                         void* binning_user, r3dgs_alloc_fn imageBuffer, void* image_user, int P, const int* D, int M,
+                         const float* background, int width, int height, const float* means3D, const float* features_dc,
+                         const float* features_rest, const float* opacities, const float* scaling_raw,
+                         float scale_modifier, const float* rotation_raw, const float* viewmatrix, const float* projmatrix,
+                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                         int* out_touched_pixels, float* out_transmittance, int* radii, int calculate_mean_transmittance,
+                         int debug, void* stream);
+long long r3dgs_forward_params_reserved(char* geom_buffer, char* binning_buffer, char* image_buffer, int reserve, int P,
+                                        const int* D, int M, const float* background, int width, int height,
+                                        const float* means3D, const float* features_dc, const float* features_rest,
+                                        const float* opacities, const float* scaling_raw, float scale_modifier,
+                                        const float* rotation_raw, const float* viewmatrix, const float* projmatrix,
+                                        const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                        float* out_color, int* out_touched_pixels, float* out_transmittance, int* radii,
+                                        int calculate_mean_transmittance, int debug, void* stream);
+int r3dgs_backward_params(int P, const int* D, int M, int R, const float* background, int width, int height,
+                          const float* means3D, const float* features_dc, const float* features_rest,
+                          const float* scaling_raw, float scale_modifier, const float* rotation_raw,
+                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                          float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                          const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dfeatures_dc, float* dL_dfeatures_rest,
+                          float* dL_dscaling_raw, float* dL_drotation_raw, float lambda_sh_sparsity, int debug,
+                          void* stream);
+int r3dgs_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales_out,
+                          float* rotations_out, void* stream);
+
 /* Debug accessor for bit-exact checks of the integer stages (SURVEY.md 8b "provide a debug accessor"):
  * copies, out of the opaque blobs of a finished forward, the sorted list in the REFERENCE's format --
  * keys[i] = (tile << 32) | depth_bits (rasterizer_impl.cu:110-113), point_list, per-tile ranges,

@@ -644,6 +644,10 @@ struct FwdCall {
     int* radii;
     int calculate_mean_transmittance, debug;
     hipStream_t stream;
+    // raw-parameter entry (r3dgs_forward_params*): scales / rotations are the model's raw parameters, shs is features_dc
+    // and shs_rest features_rest (common.h, behind FwdInputs)
+    const float* shs_rest;
+    int raw;
 };
 
 void validate_forward(const FwdCall& c)
@@ -700,6 +704,7 @@ FwdPlan make_fwd_plan(const FwdCall& c, uint32_t reserve)
     p.color_side = (side_env > 0 && !p.color_in_geom) ? 1 : 0;
     if (p.color_side) p.color_fuse = 0;
     p.tight = tight_rects();
+    p.raw_params = c.raw ? 1 : 0;
     return p;
 }
 
@@ -722,6 +727,7 @@ void fill_fwd_args(FwdPassArgs& a, const FwdPlan& p, const FwdCall& c, const Geo
     in.coeffs_num = p.ragged ? c.coeffsNum : nullptr;
     in.per_band_count = p.ragged ? c.perBand : nullptr;
     in.cumsum_count = p.ragged ? c.cumSum : nullptr;
+    a.shs_rest = c.raw ? c.shs_rest : nullptr;
     ViewParams& v = a.pre.view;
     v.view = c.viewmatrix;
     v.proj = c.projmatrix;
@@ -869,7 +875,8 @@ uint32_t fwd_flags(const FwdPlan& p, const FwdCall& c)
 {
     return (uint32_t)p.ragged | ((uint32_t)p.counters << 1) | ((uint32_t)p.fwd_ppl << 2) |
            ((uint32_t)p.layout.wide << 8) | ((uint32_t)(c.colors_precomp != nullptr) << 6) | ((uint32_t)p.color_fuse << 7) |
-           ((uint32_t)p.tight << 10) | ((uint32_t)p.color_in_geom << 11) | ((uint32_t)p.color_side << 12);
+           ((uint32_t)p.tight << 10) | ((uint32_t)p.color_in_geom << 11) | ((uint32_t)p.color_side << 12) |
+           ((uint32_t)p.raw_params << 13);
 }
 
 int current_device()
@@ -1063,6 +1070,8 @@ long long guarded_ll(F&& f)
     c.radii = radii;                                                                                                    \
     c.calculate_mean_transmittance = calculate_mean_transmittance;                                                      \
     c.debug = debug;                                                                                                    \
+    c.shs_rest = nullptr;                                                                                               \
+    c.raw = 0;                                                                                                          \
     c.stream = static_cast<hipStream_t>(stream)
 
 void check_ragged(const float* colors_precomp, int bandsNum, const int*& coeffsNum, const int*& perBand, const int*& cumSum)
@@ -1359,13 +1368,16 @@ long long r3dgs_reserve_overflow_events(int* last_num_rendered, int* last_reserv
     return (long long)g_adv.overflow_events;
 }
 
-int r3dgs_backward(int P, const int* D, int M, int R, const float* background, int width, int height,
-                   const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                   float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                   const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                   char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D,
-                   float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
-                   float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream)
+// r3dgs_backward and r3dgs_backward_params.  raw: scales / rotations are the model's raw parameters and dL_dscale / dL_drot
+// their gradients, shs / dL_dsh are features_dc / its gradient, shs_rest / dL_dsh_rest features_rest / its gradient.
+static int backward_any(int P, const int* D, int M, int R, const float* background, int width, int height,
+                        const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                        float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                        const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                        char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D,
+                        float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                        float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream,
+                        const float* shs_rest, float* dL_dsh_rest, int raw)
 {
     return guarded([&]() {
         using namespace r3;
@@ -1393,6 +1405,7 @@ int r3dgs_backward(int P, const int* D, int M, int R, const float* background, i
         plan.has_pairs = binning_buffer != nullptr ? 1 : 0;
         plan.units_cap = bwd_units_cap(plan.reserve, TileGrid{(uint32_t)plan.gx, (uint32_t)plan.gy});
         plan.f64_chain = f64_chain();
+        plan.raw_params = raw ? 1 : 0;
         const int dev = current_device();
         GeomState geom = GeomState::carve(geom_buffer, (size_t)P, cached_depth_temp((size_t)P));
         ImageState img = ImageState::carve(image_buffer, (size_t)width * height, (size_t)plan.gx * plan.gy);
@@ -1485,6 +1498,8 @@ int r3dgs_backward(int P, const int* D, int M, int R, const float* background, i
         pb.out.dL_dmean3D = dL_dmean3D;
         pb.out.dL_dcov3D = dL_dcov3D;
         pb.out.dL_dsh = dL_dsh;
+        pb.shs_rest = raw ? shs_rest : nullptr;
+        pb.dL_dsh_rest = raw ? dL_dsh_rest : nullptr;
         pb.out.dL_dscale = dL_dscale;
         pb.out.dL_drot = dL_drot;
         pb.out.dL_dconic = dL_dconic;
@@ -1506,13 +1521,120 @@ int r3dgs_backward(int P, const int* D, int M, int R, const float* background, i
         } else {
             const uint32_t flags = (uint32_t)plan.bwd_ppl | ((uint32_t)plan.has_pairs << 3) | ((uint32_t)plan.layout.wide << 4) |
                                    ((uint32_t)(a.blend.tile_order != nullptr) << 6) |   // one more kernel in the chain
-                                   ((uint32_t)plan.f64_chain << 7);
+                                   ((uint32_t)plan.f64_chain << 7) | ((uint32_t)plan.raw_params << 8);
             const CtxKey key{dev, 1, s, P, M, width, height, plan.reserve, flags};
             launch_graph(key, plan, a, s, [](const BwdPlan& p, BwdPassArgs* d, const BwdPassArgs& v, hipStream_t cs) {
                 NoHooks nh;
                 issue_backward(p, d, v, cs, nh);
             });
         }
+        return 0;
+    });
+}
+
+int r3dgs_backward(int P, const int* D, int M, int R, const float* background, int width, int height,
+                   const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                   float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                   const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                   char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D,
+                   float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                   float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream)
+{
+    return backward_any(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
+                        cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                        image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                        dL_dscale, dL_drot, lambda_sh_sparsity, debug, stream, nullptr, nullptr, 0);
+}
+
+// ---- the raw-parameter entry points (include/r3dgs_rasterizer.h) ------------------------------------------------------
+static void check_params(int P, const int* D, int M, const float* features_dc, const float* features_rest,
+                         const float* scaling_raw, const float* rotation_raw)
+{
+    if (P <= 0) return;
+    if (M < 1 || M > 16) throw r3::Error("SH coefficient count M must be in [1,16]");
+    if (!features_dc) throw r3::Error("raw-parameter path: features_dc is NULL");
+    if ((features_rest == nullptr) != (M == 1))
+        throw r3::Error("raw-parameter path: features_rest must be [P,M-1,3] (NULL iff M == 1)");
+    if (!D) throw r3::Error("per-Gaussian degrees must be provided with SHs");
+    if (!scaling_raw || !rotation_raw) throw r3::Error("raw-parameter path: scaling and rotation must be provided");
+}
+
+#define R3_PARAMS_CALL()                                                                                                \
+    const float* shs = features_dc;                                                                                     \
+    const float* colors_precomp = nullptr;                                                                              \
+    const float* cov3D_precomp = nullptr;                                                                               \
+    const float* scales = scaling_raw;                                                                                  \
+    const float* rotations = rotation_raw;                                                                              \
+    R3_FWD_CALL(nullptr, nullptr, nullptr, M);                                                                          \
+    c.shs_rest = features_rest;                                                                                         \
+    c.raw = 1
+
+int r3dgs_forward_params(r3dgs_alloc_fn geometryBuffer, void* geometry_user, r3dgs_alloc_fn binningBuffer, void* binning_user,
+                         r3dgs_alloc_fn imageBuffer, void* image_user, int P, const int* D, int M, const float* background,
+                         int width, int height, const float* means3D, const float* features_dc, const float* features_rest,
+                         const float* opacities, const float* scaling_raw, float scale_modifier, const float* rotation_raw,
+                         const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                         int prefiltered, float* out_color, int* out_touched_pixels, float* out_transmittance, int* radii,
+                         int calculate_mean_transmittance, int debug, void* stream)
+{
+    (void)prefiltered;
+    return guarded([&]() {
+        check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
+        R3_PARAMS_CALL();
+        return forward_exact(geometryBuffer, geometry_user, binningBuffer, binning_user, imageBuffer, image_user, c);
+    });
+}
+
+long long r3dgs_forward_params_reserved(char* geom_buffer, char* binning_buffer, char* image_buffer, int reserve, int P,
+                                        const int* D, int M, const float* background, int width, int height,
+                                        const float* means3D, const float* features_dc, const float* features_rest,
+                                        const float* opacities, const float* scaling_raw, float scale_modifier,
+                                        const float* rotation_raw, const float* viewmatrix, const float* projmatrix,
+                                        const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
+                                        int* out_touched_pixels, float* out_transmittance, int* radii,
+                                        int calculate_mean_transmittance, int debug, void* stream)
+{
+    (void)prefiltered;
+    return guarded_ll([&]() {
+        check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
+        R3_PARAMS_CALL();
+        return forward_reserved(geom_buffer, binning_buffer, image_buffer, reserve, c);
+    });
+}
+
+int r3dgs_backward_params(int P, const int* D, int M, int R, const float* background, int width, int height,
+                          const float* means3D, const float* features_dc, const float* features_rest, const float* scaling_raw,
+                          float scale_modifier, const float* rotation_raw, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
+                          char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                          float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dfeatures_dc,
+                          float* dL_dfeatures_rest, float* dL_dscaling_raw, float* dL_drotation_raw, float lambda_sh_sparsity,
+                          int debug, void* stream)
+{
+    const int st = guarded([&]() {
+        check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
+        if (P > 0 && (!dL_dfeatures_dc || (M > 1 && !dL_dfeatures_rest)))
+            throw r3::Error("raw-parameter path: a gradient output pointer is NULL");
+        return 0;
+    });
+    if (st < 0) return st;
+    return backward_any(P, D, M, R, background, width, height, means3D, features_dc, nullptr, scaling_raw, scale_modifier,
+                        rotation_raw, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
+                        binning_buffer, image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
+                        dL_dcov3D, dL_dfeatures_dc, dL_dscaling_raw, dL_drotation_raw, lambda_sh_sparsity, debug, stream,
+                        features_rest, dL_dfeatures_rest, 1);
+}
+
+int r3dgs_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales_out, float* rotations_out,
+                          void* stream)
+{
+    return guarded([&]() {
+        if (P <= 0) return 0;
+        if ((scaling_raw == nullptr) != (scales_out == nullptr) || (rotation_raw == nullptr) != (rotations_out == nullptr))
+            throw r3::Error("activate_params: an input without its output (or the reverse)");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        r3::launch_activate_params(P, scaling_raw, rotation_raw, scales_out, rotations_out, s);
+        r3::check_launch("activate_params", s, false);
         return 0;
     });
 }

@@ -29,6 +29,7 @@
 #include <string>
 
 #include "gauss_math.h"
+#include "param_math.h"
 
 namespace r3 {
 
@@ -527,6 +528,12 @@ struct FwdInputs {
     const int* per_band_count;
     const int* cumsum_count;
 };
+// Raw-parameter passes (r3dgs_forward_params / r3dgs_backward_params, FwdPlan / BwdPlan::raw_params; the *_params kernel
+// instantiations): `scales` holds log-scales and `rotations` unnormalised quaternions (activated after the load,
+// param_math.h), `shs` is features_dc [P,1,3] and the pass block carries features_rest [P,M-1,3] (null iff M == 1) in a
+// field of its own BEHIND everything the other passes use -- FwdPassArgs::shs_rest, PreBwdArgs::shs_rest / dL_dsh_rest --
+// so that no existing field moves (fields inside FwdInputs / BwdOutputs shifted every offset behind them, and the
+// register allocation of the existing instantiations with it: profiles/raw_params_kernel_resources.txt).
 
 struct BwdOutputs {
     float* dL_dmean2D;   // [P,3]
@@ -534,7 +541,7 @@ struct BwdOutputs {
     float* dL_dcolor;    // [P,3]
     float* dL_dmean3D;   // [P,3]
     float* dL_dcov3D;    // [P,6]
-    float* dL_dsh;       // [P,M,3]
+    float* dL_dsh;       // [P,M,3]  (raw-parameter backward: dL_dfeatures_dc [P,1,3]; the rest rows: PreBwdArgs::dL_dsh_rest)
     float* dL_dscale;    // [P,3]
     float* dL_drot;      // [P,4]
     float* dL_dconic;    // [P,4] optional (nullptr: not exported)
@@ -701,6 +708,9 @@ struct PreBwdArgs {       // preprocess_bwd.hip
     const float* sh_ddir; // GeomState::sh_ddir when the backward may use it (no sparsity term, not switched off), else null
     int stagger;   // start-up delay step of the first generation of workgroups, in 64-clock units (preprocess_bwd.hip)
     BwdOutputs out;
+    // raw-parameter backward only (see FwdInputs): out.dL_dscale / out.dL_drot are gradients of the RAW tensors
+    const float* shs_rest;   // features_rest [P,M-1,3]
+    float* dL_dsh_rest;      // its gradient
 };
 
 // The device-resident argument block of a forward / backward pass.
@@ -712,6 +722,7 @@ struct FwdPassArgs {
     RadixArgs radix[kMaxRadixPasses];
     RangesArgs ranges;
     BlendFwdArgs blend;
+    const float* shs_rest;   // raw-parameter forward only: features_rest [P,M-1,3] (see FwdInputs)
 };
 struct BwdPassArgs {
     BlendBwdArgs blend;
@@ -737,6 +748,7 @@ struct FwdPlan {
     int color_split[3];    // percent of the colour chunks in the histogram / scatter / bucket-sort launches
     int generic_depth_sort;  // rocPRIM sort + scan instead of the bucketed sort (never inside a graph)
     int tight;             // opacity-aware tile rects (default) or the reference's 3-sigma squares
+    int raw_params;        // the inputs are the model's raw parameters (see FwdInputs): the *_params instantiations
 };
 struct BwdPlan {
     int P, M, W, H, gx, gy;
@@ -746,6 +758,7 @@ struct BwdPlan {
     int bwd_ppl;
     int has_pairs;         // 0: the forward ran with an empty reservation (P > 0, no binning blob)
     int f64_chain;         // the per-Gaussian backward evaluates the covariance chain in double (gauss_math.h; default)
+    int raw_params;        // raw-parameter backward (BwdOutputs::dL_dsh_dc / dL_dsh_rest; activation backward applied)
 };
 
 // stage ids of the optional per-stage timers (capi.hip)
@@ -759,6 +772,8 @@ enum Stage { kPre = 0, kDepthSort, kBinning, kBlendFwd, kBlendBwd, kPreBwd, kCol
 void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs& v, hipStream_t s);
 void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, bool* present, hipStream_t s);
+void launch_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales, float* rotations,
+                            hipStream_t s);   // preprocess.hip: param_math.h's scale_act / quat_act per Gaussian
 
 void issue_header_reduce(const HeaderArgs* a, hipStream_t s);
 void prepare_depth_bucket_sort(int nb);   // LDS opt-in of the depth-sort kernels, once per device (not a stream op)

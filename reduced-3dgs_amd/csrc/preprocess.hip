@@ -78,6 +78,74 @@ __device__ __forceinline__ void stage_span(const float4* __restrict__ src4, int 
     }
 }
 
+// ---- SH rows that arrive as two tensors (raw-parameter entry: features_dc [P,1,3], features_rest [P,M-1,3]) -------------
+// The wave's 64 rows are one contiguous span of EACH tensor; both are copied into the LDS row layout above, so that
+// everything behind the staging is untouched.  Float f of a span whose rows are `rl` floats long (3 for dc, 3 (M - 1) for
+// rest) and start at float `k0` of the joined row (0 / 3) belongs to row f / rl: joined-span element row * 3M + k0 + f % rl.
+// ROWS48 (M == 16): LDS word 49 * row + k0 + f % rl = f + (49 - rl) * row + k0 -- one multiply-high per float.
+template <bool ROWS48>
+__device__ __forceinline__ int split_lds_index(int f, int rl, int k0, int M)
+{
+    if (ROWS48) {
+        // rl is 3 or 45 here (k0 says which): f / 3 and f / 45 for f < 2^16 by multiply and shift
+        const int row = k0 == 0 ? (int)(((uint32_t)f * 43691u) >> 17) : (int)(((uint32_t)f * 46604u) >> 21);
+        return f + (49 - rl) * row + k0;
+    }
+    const int row = f / rl;
+    return skew<false>(row * 3 * M + k0 + (f - row * rl));
+}
+
+// one of the two spans (len floats at src, 16-byte aligned and len % 4 == 0 when VEC) -> LDS
+template <bool ROWS48, bool VEC>
+__device__ __forceinline__ void stage_split_span(const float* __restrict__ src, int len, int rl, int k0, int M, float* dst,
+                                                 int lane)
+{
+    if (VEC) {
+        constexpr int kBatch = 6;
+        const float4* src4 = reinterpret_cast<const float4*>(src);
+        const int n4 = len >> 2;
+        for (int base = 0; base < n4; base += 64 * kBatch) {
+            float4 v[kBatch];
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int e4 = base + k * 64 + lane;
+                v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int e4 = base + k * 64 + lane;
+                if (e4 < n4) {
+                    const int f = e4 << 2;
+                    dst[split_lds_index<ROWS48>(f, rl, k0, M)] = v[k].x;
+                    dst[split_lds_index<ROWS48>(f + 1, rl, k0, M)] = v[k].y;
+                    dst[split_lds_index<ROWS48>(f + 2, rl, k0, M)] = v[k].z;
+                    dst[split_lds_index<ROWS48>(f + 3, rl, k0, M)] = v[k].w;
+                }
+            }
+        }
+    } else {
+        for (int f = lane; f < len; f += 64) dst[split_lds_index<ROWS48>(f, rl, k0, M)] = src[f];
+    }
+}
+
+// both spans of the wave's `nrows` rows starting at Gaussian wave_first
+template <bool ROWS48>
+__device__ __forceinline__ void stage_split_rows(const float* __restrict__ dc, const float* __restrict__ rest, int wave_first,
+                                                 int nrows, int M, float* dst, int lane)
+{
+    const int rl = 3 * (M - 1);
+    const float* s_dc = dc + 3L * wave_first;
+    const int n_dc = 3 * nrows, n_rest = rl * nrows;
+    // 16-byte aligned spans: wave_first is a multiple of 64, so both start aligned; full waves have lengths % 4 == 0
+    if ((nrows & 3) == 0) {
+        stage_split_span<ROWS48, true>(s_dc, n_dc, 3, 0, M, dst, lane);
+        if (M > 1) stage_split_span<ROWS48, true>(rest + (long)rl * wave_first, n_rest, rl, 3, M, dst, lane);
+    } else {
+        stage_split_span<ROWS48, false>(s_dc, n_dc, 3, 0, M, dst, lane);
+        if (M > 1) stage_split_span<ROWS48, false>(rest + (long)rl * wave_first, n_rest, rl, 3, M, dst, lane);
+    }
+}
+
 // forward.cu:19-36 getSHOffset (float3 units)
 __device__ __forceinline__ int ragged_offset(int idx, const int* coeffs, const int* perband, const int* cumsum, int* deg)
 {
@@ -95,8 +163,9 @@ __device__ __forceinline__ int ragged_offset(int idx, const int* coeffs, const i
     return off + (idx - cumsum[2]) * coeffs[3];
 }
 
-template <bool RAGGED, int BLOCK>
-__device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg);
+template <bool RAGGED, int BLOCK, bool SPLIT = false>
+__device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg,
+                                           const float* shs_rest = nullptr);
 
 // ---- kernel 1: geometry ---------------------------------------------------------------------------
 // cull, projection, conic, radius, tile rect, depth key, per-view counters.  Reads 44 B per Gaussian.  Its
@@ -105,6 +174,8 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
 // COLOR != 0 (large scenes, FwdPlan::color_in_geom): the workgroup goes on to colour its own 256 Gaussians (color_role
 // below; COLOR 2 = ragged SH) while their records are still in the L2 -- the separate colour stream otherwise re-opens every
 // 48-byte record for a 16-byte partial write, which HBM pays as a read-modify-write of the whole line.
+// COLOR >= 4 (r3dgs_forward_params): scales / rotations hold the model's RAW parameters and are activated after the load
+// (param_math.h); 4: no colour here, 5: colours its own Gaussians from the two SH tensors.
 template <int COLOR>
 __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs* dst, FwdPassArgs v)
 {
@@ -137,6 +208,11 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
             q[1] = qv.y;
             q[2] = qv.z;
             q[3] = qv.w;
+            if (COLOR >= 4) {
+                const float rq[4] = {q[0], q[1], q[2], q[3]};
+                for (int k = 0; k < 3; k++) sc[k] = scale_act(sc[k]);
+                quat_act(rq, q);
+            }
         }
         preprocess_one(cam, mx, my, mz, sc, q, c6p, a.in.opacities[i], &o, a.tight != 0);
         uint32_t dkey = 0xFFFFFFFFu;
@@ -199,7 +275,10 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
         }
         a.partials[blockIdx.x] = pp;
     }
-    if (COLOR) {
+    if (COLOR == 5) {
+        __syncthreads();
+        color_role<false, kPreBlock, true>(a, geom_smem, (int)blockIdx.x, (int)blockIdx.x + 1, 0, 1, v.shs_rest);
+    } else if (COLOR && COLOR < 4) {
         __syncthreads();
         if (COLOR == 2)
             color_role<true, kPreBlock>(a, geom_smem, (int)blockIdx.x, (int)blockIdx.x + 1, 0, 1);
@@ -220,8 +299,10 @@ constexpr size_t kColorLds = sizeof(float) * (kPreBlock / 64) * kWaveShFloats;
 // chunks [first + wg, last) in steps of n_wg, BLOCK Gaussians each (BLOCK = workgroup size); smem: BLOCK / 64 wave windows.
 // BLOCK = 64 (standalone kernel only): single-wave workgroups -- 12 per CU instead of 3 of four waves: no barrier couples
 // the waves' load / evaluate phases, so they drift apart and one wave's loads fly while another evaluates.
-template <bool RAGGED, int BLOCK>
-__device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg)
+// SPLIT: the rows come from two tensors, in.shs = features_dc and shs_rest (stage_split_rows); the LDS layout is the same.
+template <bool RAGGED, int BLOCK, bool SPLIT>
+__device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg,
+                                           const float* shs_rest)
 {
     float(*s_sh)[kWaveShFloats] = reinterpret_cast<float(*)[kWaveShFloats]>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -260,7 +341,15 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
     }
     // wave-uniform: does any lane of this wave need its SH row?
     const bool wave_needs = __ballot(need_sh) != 0ull;
-    if (wave_needs) {
+    if (SPLIT) {
+        if (wave_needs) {
+            const int nrows = max(0, min(64, P - wave_first));
+            if (rows48)
+                stage_split_rows<true>(a.in.shs, shs_rest, wave_first, nrows, M, s_sh[wave], lane);
+            else
+                stage_split_rows<false>(a.in.shs, shs_rest, wave_first, nrows, M, s_sh[wave], lane);
+        }
+    } else if (wave_needs) {
         const float* src = a.in.shs + span_first;
         float* dst = s_sh[wave];
         if (((span_first | span_len) & 3) == 0) {  // 16-B aligned span (always true for M = 16): dwordx4 loads
@@ -324,6 +413,14 @@ __global__ __launch_bounds__(BLOCK) void preprocess_color_kernel(const PreArgs* 
     color_role<RAGGED, BLOCK>(a, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x);
 }
 
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void preprocess_color_params_kernel(const FwdPassArgs* __restrict__ pa)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const PreArgs a = pa->pre;
+    color_role<false, BLOCK, true>(a, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x, pa->shs_rest);
+}
+
 // ---- depth-sort kernels carrying a share of the colour stream in extra workgroups -------------------------------
 // Workgroups [0, n_sort) run the depth-sort role, workgroups [n_sort, n_sort + n_color) the colour chunks
 // [c0, c1).  One dynamic LDS window serves whichever role a workgroup has.
@@ -347,6 +444,27 @@ __global__ __launch_bounds__(kPreBlock) void depth_sort_color_kernel(const FwdPa
     }
 }
 
+// the same with the colour role reading the two SH tensors of the raw-parameter entry
+template <int STEP>
+__global__ __launch_bounds__(kPreBlock) void depth_sort_color_params_kernel(const FwdPassArgs* __restrict__ pa, int n_sort,
+                                                                            int c0, int c1)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int wg = (int)blockIdx.x;
+    if (wg < n_sort) {
+        const DepthArgs d = pa->depth;
+        if (STEP == 0)
+            depth_hist_role(d, pa->header, smem, wg);
+        else if (STEP == 1)
+            depth_scatter_role(d, smem, wg);
+        else
+            depth_bucket_group_role(d, smem, wg, n_sort);
+    } else {
+        const PreArgs a = pa->pre;
+        color_role<false, kPreBlock, true>(a, smem, c0, c1, wg - n_sort, (int)gridDim.x - n_sort, pa->shs_rest);
+    }
+}
+
 __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const DepthArgs* __restrict__ ap)
 {
     const DepthArgs d = *ap;
@@ -356,7 +474,11 @@ __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const Dep
 void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs& v, hipStream_t s)
 {
     const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
-    if (p.color_in_geom && p.ragged)
+    if (p.raw_params && p.color_in_geom)
+        hipLaunchKernelGGL(preprocess_geom_kernel<5>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
+    else if (p.raw_params)
+        hipLaunchKernelGGL(preprocess_geom_kernel<4>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
+    else if (p.color_in_geom && p.ragged)
         hipLaunchKernelGGL(preprocess_geom_kernel<2>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
     else if (p.color_in_geom)
         hipLaunchKernelGGL(preprocess_geom_kernel<1>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
@@ -371,7 +493,13 @@ void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s)
     const int want = p.color_grid > 0 ? p.color_grid * (kPreBlock / block) : blocks;
     const int grid = blocks > want ? want : blocks;
     const size_t lds = kColorLds / (kPreBlock / block);
-    if (block == 64) {
+    if (p.raw_params) {
+        const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
+        if (block == 64)
+            hipLaunchKernelGGL((preprocess_color_params_kernel<64>), dim3(grid), dim3(64), lds, s, pa);
+        else
+            hipLaunchKernelGGL((preprocess_color_params_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), lds, s, pa);
+    } else if (block == 64) {
         if (p.ragged)
             hipLaunchKernelGGL((preprocess_color_kernel<true, 64>), dim3(grid), dim3(64), lds, s, a);
         else
@@ -390,6 +518,13 @@ static void launch_sort_color(const FwdPassArgs* pa, int n_sort, int n_color, in
                        n_sort, c0, c1);
 }
 
+template <int STEP>
+static void launch_sort_color_params(const FwdPassArgs* pa, int n_sort, int n_color, int c0, int c1, size_t lds, hipStream_t s)
+{
+    hipLaunchKernelGGL((depth_sort_color_params_kernel<STEP>), dim3(n_sort + n_color), dim3(kPreBlock), lds, s, pa, n_sort,
+                       c0, c1);
+}
+
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 template <int STEP, bool RAGGED>
@@ -397,6 +532,14 @@ static void opt_in_lds(size_t bytes)
 {
     if (bytes > 48 * 1024)
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_kernel<STEP, RAGGED>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+
+template <int STEP>
+static void opt_in_lds_params(size_t bytes)
+{
+    if (bytes > 48 * 1024)
+        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_params_kernel<STEP>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
@@ -419,6 +562,9 @@ void prepare_depth_bucket_sort(int nb)
     opt_in_lds<1, true>(sc);
     opt_in_lds<2, false>(bs);
     opt_in_lds<2, true>(bs);
+    opt_in_lds_params<0>(h);
+    opt_in_lds_params<1>(sc);
+    opt_in_lds_params<2>(bs);
     if (kColorLds > 48 * 1024) {
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_geom_kernel<1>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
@@ -427,6 +573,10 @@ void prepare_depth_bucket_sort(int nb)
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<false, kPreBlock>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<true, kPreBlock>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
+        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_geom_kernel<5>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
+        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_params_kernel<kPreBlock>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
     }
     prepared_nb = nb;
@@ -452,7 +602,12 @@ void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStre
     const size_t lds0 = n_color(0) ? max_sz(depth_hist_lds(nb), kColorLds) : depth_hist_lds(nb);
     const size_t lds1 = n_color(1) ? max_sz(depth_scatter_lds(nb), kColorLds) : depth_scatter_lds(nb);
     const size_t lds2 = n_color(2) ? max_sz(kBucketSortLds, kColorLds) : kBucketSortLds;
-    if (p.ragged) {
+    if (p.raw_params) {
+        launch_sort_color_params<0>(pa, rows, n_color(0), c[0], c[1], lds0, s);
+        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
+        launch_sort_color_params<1>(pa, rows, n_color(1), c[1], c[2], lds1, s);
+        launch_sort_color_params<2>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], lds2, s);
+    } else if (p.ragged) {
         launch_sort_color<0, true>(pa, rows, n_color(0), c[0], c[1], lds0, s);
         hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
         launch_sort_color<1, true>(pa, rows, n_color(1), c[1], c[2], lds1, s);
@@ -479,6 +634,31 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(int P, const float* m
 void launch_mark_visible(int P, const float* means3D, const float* view, bool* present, hipStream_t s)
 {
     hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, view, present);
+}
+
+// r3dgs_activate_params: the activated values the raw-parameter kernels use, by the very functions they call
+__global__ __launch_bounds__(256) void activate_params_kernel(int P, const float* __restrict__ scaling_raw,
+                                                              const float* __restrict__ rotation_raw,
+                                                              float* __restrict__ scales, float* __restrict__ rotations)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    if (scaling_raw && scales)
+        for (int k = 0; k < 3; k++) scales[3 * (size_t)i + k] = scale_act(scaling_raw[3 * (size_t)i + k]);
+    if (rotation_raw && rotations) {
+        const float4 qv = reinterpret_cast<const float4*>(rotation_raw)[i];
+        const float rq[4] = {qv.x, qv.y, qv.z, qv.w};
+        float q[4];
+        quat_act(rq, q);
+        reinterpret_cast<float4*>(rotations)[i] = make_float4(q[0], q[1], q[2], q[3]);
+    }
+}
+
+void launch_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales, float* rotations,
+                            hipStream_t s)
+{
+    hipLaunchKernelGGL(activate_params_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, scaling_raw, rotation_raw, scales,
+                       rotations);
 }
 
 }  // namespace r3

@@ -54,6 +54,78 @@ struct ShRowLdsRW {
     }
 };
 
+// ---- SH rows as two tensors (raw-parameter backward: features_dc [P,1,3] / features_rest [P,M-1,3] in, their gradients out)
+// Same scheme as the forward's colour role (preprocess.hip split_lds_index): float f of a span whose rows are `rl` floats long
+// (3 for dc, 3 (M - 1) for rest) and start at float `k0` of the joined row (0 / 3) is joined-span element
+// (f / rl) * 3M + k0 + f % rl; the LDS row layout -- the contract with sh_backward -- is the one above.
+template <bool ROWS48>
+__device__ __forceinline__ int split_lds_index(int f, int rl, int k0, int M)
+{
+    if (ROWS48) {   // rl is 3 or 45 (k0 says which): f / 3 and f / 45 for f < 2^16 by multiply and shift
+        const int row = k0 == 0 ? (int)(((uint32_t)f * 43691u) >> 17) : (int)(((uint32_t)f * 46604u) >> 21);
+        return f + (49 - rl) * row + k0;
+    }
+    const int row = f / rl;
+    return bskew<false>(row * 3 * M + k0 + (f - row * rl));
+}
+
+// one span (len floats, 16-byte aligned and len % 4 == 0 when VEC) global -> LDS
+template <bool ROWS48, bool VEC>
+__device__ __forceinline__ void stage_split_span(const float* __restrict__ src, int len, int rl, int k0, int M, float* lds,
+                                                 int lane)
+{
+    if (VEC) {
+        constexpr int kBatch = 6;
+        const float4* src4 = reinterpret_cast<const float4*>(src);
+        const int n4 = len >> 2;
+        for (int base = 0; base < n4; base += 64 * kBatch) {
+            float4 v[kBatch];
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int e4 = base + k * 64 + lane;
+                v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int e4 = base + k * 64 + lane;
+                if (e4 < n4) {
+                    const int f = e4 << 2;
+                    lds[split_lds_index<ROWS48>(f, rl, k0, M)] = v[k].x;
+                    lds[split_lds_index<ROWS48>(f + 1, rl, k0, M)] = v[k].y;
+                    lds[split_lds_index<ROWS48>(f + 2, rl, k0, M)] = v[k].z;
+                    lds[split_lds_index<ROWS48>(f + 3, rl, k0, M)] = v[k].w;
+                }
+            }
+        }
+    } else {
+        for (int f = lane; f < len; f += 64) lds[split_lds_index<ROWS48>(f, rl, k0, M)] = src[f];
+    }
+}
+
+// one span LDS -> global (the gradient rows), or zeros when the wave built no rows
+template <bool ROWS48, bool VEC>
+__device__ __forceinline__ void unstage_split_span(float* __restrict__ dst, int len, int rl, int k0, int M, const float* lds,
+                                                   int lane, bool rows)
+{
+    if (VEC) {
+        float4* dst4 = reinterpret_cast<float4*>(dst);
+        const int n4 = len >> 2;
+        if (rows) {
+            for (int e4 = lane; e4 < n4; e4 += 64) {
+                const int f = e4 << 2;
+                dst4[e4] = make_float4(lds[split_lds_index<ROWS48>(f, rl, k0, M)], lds[split_lds_index<ROWS48>(f + 1, rl, k0, M)],
+                                       lds[split_lds_index<ROWS48>(f + 2, rl, k0, M)], lds[split_lds_index<ROWS48>(f + 3, rl, k0, M)]);
+            }
+        } else {
+            for (int e4 = lane; e4 < n4; e4 += 64) dst4[e4] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    } else if (rows) {
+        for (int f = lane; f < len; f += 64) dst[f] = lds[split_lds_index<ROWS48>(f, rl, k0, M)];
+    } else {
+        for (int f = lane; f < len; f += 64) dst[f] = 0.f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Per-Gaussian sums of the per-(tile, Gaussian)-pair gradients written by the backward blend.
 // The slab is in emission order, i.e. a Gaussian's pairs are contiguous, so this is a segmented sum over a
@@ -224,7 +296,11 @@ void issue_pair_reduce(const BwdPlan& p, const PairReduceArgs* a, hipStream_t s)
 }
 
 // F64: the covariance chain in double (gauss_math.h cov2d_backward_f64 / cov3d_backward_f64; the default)
-template <bool ROWS48, bool F64>
+// RAW (r3dgs_backward_params): in.scales / in.rotations hold the model's raw parameters -- activated after the load, and
+// dL_dscale / dL_drot, formed and rounded to fp32 exactly as without RAW, pass through the fp32 activation backward of
+// param_math.h before the store; the SH rows come from in.shs (features_dc) / shs_rest and their gradient rows leave as
+// out.dL_dsh / dL_dsh_rest.
+template <bool ROWS48, bool F64, bool RAW = false>
 __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdArgs* __restrict__ ap)
 {
     __shared__ float s_sh[kBwdBlock / 64][kBwdWaveShFloats];
@@ -252,7 +328,18 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         const int steps = (int)(blockIdx.x / (256u * (256 / kBwdBlock))) * a.stagger;
         for (int k = 0; k < steps; k += 127) __builtin_amdgcn_s_sleep(127);
     }
-    if (has_sh && wave_vis && !cached) {
+    if (RAW) {
+        if (wave_vis && !cached) {
+            const int rl = 3 * (M - 1);
+            if ((nrows & 3) == 0) {   // both spans start 16-byte aligned (wave_first % 64 == 0); full waves: lengths % 4 == 0
+                stage_split_span<ROWS48, true>(a.in.shs + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane);
+                if (M > 1) stage_split_span<ROWS48, true>(a.shs_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane);
+            } else {
+                stage_split_span<ROWS48, false>(a.in.shs + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane);
+                if (M > 1) stage_split_span<ROWS48, false>(a.shs_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane);
+            }
+        }
+    } else if (has_sh && wave_vis && !cached) {
         const float* src = a.in.shs + span_first;
         if (((span_first | span_len) & 3) == 0) {   // 16-B aligned span (always for M = 16): dwordx4 loads, six in
             const float4* src4 = reinterpret_cast<const float4*>(src);   // flight before the first LDS store (twelve, as in
@@ -357,11 +444,17 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
             dcol[2] = acc9[8];
         }
         float sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c6[6];
+        float qn = 1.f;   // RAW: norm of the raw quaternion
         if (a.in.cov3D_precomp) {
             for (int k = 0; k < 6; k++) c6[k] = a.in.cov3D_precomp[6 * i + k];
         } else {
             for (int k = 0; k < 3; k++) sc[k] = a.in.scales[3 * i + k];
             for (int k = 0; k < 4; k++) q[k] = a.in.rotations[4 * i + k];
+            if (RAW) {
+                const float rq[4] = {q[0], q[1], q[2], q[3]};
+                for (int k = 0; k < 3; k++) sc[k] = scale_act(sc[k]);
+                qn = quat_act(rq, q);
+            }
             cov3d_from_scale_rot(sc, cam.scale_modifier, q, c6);  // recomputed, not stored by the forward
         }
         double dcov6d[6];
@@ -396,6 +489,11 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
                 cov3d_backward_f64(sc, cam.scale_modifier, q, dcov6d, dscale, dq);
             else
                 cov3d_backward(sc, cam.scale_modifier, q, dcov6, dscale, dq);
+            if (RAW) {   // gradients of the activated values (fp32, as stored without RAW) -> gradients of the raw parameters
+                for (int k = 0; k < 3; k++) dscale[k] = scale_act_bwd(dscale[k], sc[k]);
+                const float gq[4] = {dq[0], dq[1], dq[2], dq[3]};
+                quat_act_bwd(q, qn, gq, dq);
+            }
         }
         dop = opacity_backward(dop, r.op);
     }
@@ -405,7 +503,18 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         }
     }
     __syncthreads();
-    if (has_sh) {
+    if (RAW) {
+        const int rl = 3 * (M - 1);
+        if ((nrows & 3) == 0) {
+            unstage_split_span<ROWS48, true>(a.out.dL_dsh + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
+            if (M > 1)
+                unstage_split_span<ROWS48, true>(a.dL_dsh_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane, wave_vis);
+        } else {
+            unstage_split_span<ROWS48, false>(a.out.dL_dsh + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
+            if (M > 1)
+                unstage_split_span<ROWS48, false>(a.dL_dsh_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane, wave_vis);
+        }
+    } else if (has_sh) {
         float* dst = a.out.dL_dsh + span_first;
         if (((span_first | span_len) & 3) == 0) {   // dwordx4 stores of the gradient rows (or of zeros)
             float4* dst4 = reinterpret_cast<float4*>(dst);
@@ -470,6 +579,20 @@ void issue_preprocess_backward(const BwdPlan& p, const PreBwdArgs* a, hipStream_
 {
     const int blocks = (p.P + kBwdBlock - 1) / kBwdBlock;
     static const int lds_pad = env_int("R3DGS_PREBWD_LDS_PAD", 0, 0, 65536);
+    if (p.raw_params) {
+        if (p.M == 16) {
+            if (p.f64_chain)
+                hipLaunchKernelGGL((preprocess_bwd_kernel<true, true, true>), dim3(blocks), dim3(kBwdBlock), lds_pad, s, a);
+            else
+                hipLaunchKernelGGL((preprocess_bwd_kernel<true, false, true>), dim3(blocks), dim3(kBwdBlock), lds_pad, s, a);
+        } else {
+            if (p.f64_chain)
+                hipLaunchKernelGGL((preprocess_bwd_kernel<false, true, true>), dim3(blocks), dim3(kBwdBlock), lds_pad, s, a);
+            else
+                hipLaunchKernelGGL((preprocess_bwd_kernel<false, false, true>), dim3(blocks), dim3(kBwdBlock), lds_pad, s, a);
+        }
+        return;
+    }
     if (p.M == 16) {
         if (p.f64_chain)
             hipLaunchKernelGGL((preprocess_bwd_kernel<true, true>), dim3(blocks), dim3(kBwdBlock), lds_pad, s, a);

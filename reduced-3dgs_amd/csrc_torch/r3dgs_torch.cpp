@@ -62,6 +62,10 @@ struct Api {
     R3_FN(r3dgs_l1_backward)
     R3_FN(r3dgs_adam_step)
     R3_FN(r3dgs_adam_step_capturable)
+    R3_FN(r3dgs_forward_params)
+    R3_FN(r3dgs_forward_params_reserved)
+    R3_FN(r3dgs_backward_params)
+    R3_FN(r3dgs_activate_params)
 #undef R3_FN
     bool bound = false;
 } api;
@@ -101,6 +105,11 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_OPT(r3dgs_l1_backward)
     R3_OPT(r3dgs_adam_step)
     R3_OPT(r3dgs_adam_step_capturable)
+    // the raw-parameter entry points: absent from an older A/B build, whose calls then refuse
+    R3_OPT(r3dgs_forward_params)
+    R3_OPT(r3dgs_forward_params_reserved)
+    R3_OPT(r3dgs_backward_params)
+    R3_OPT(r3dgs_activate_params)
 #undef R3_OPT
     api.bound = true;
 }
@@ -138,6 +147,8 @@ Tensor dev_i32(const Tensor& t, const c10::Device& dev)
     if (t.scalar_type() != at::kInt) throw std::runtime_error(std::string("expected int32, got ") + c10::toString(t.scalar_type()));
     return t.contiguous();
 }
+
+void* cur_stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
 
 std::mutex g_mu;
 std::map<std::tuple<int, int, int, int, int>, size_t> g_sizes;   // (kind, a, b, c, d) -> bytes
@@ -258,6 +269,213 @@ std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, co
     std::vector<Tensor> out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
     if (want_conic) out.push_back(dL_dconic);
     return out;
+}
+
+// ---- raster from the model's raw parameters (r3dgs_*_params): the same marshalling as diff_gaussian_rasterization/_C.py's
+// rasterize_gaussian_params*; refusals (shapes, dtypes, contiguity) carry the same messages.
+
+void need_params()
+{
+    need_bound();
+    if (!api.r3dgs_forward_params_reserved)
+        throw std::runtime_error("the loaded libr3dgs_hip.so has no raw-parameter entry points: rebuild it with build.py");
+}
+
+// a raw parameter tensor: on `dev`, fp32, contiguous AS PASSED (a copy would defeat the point of the path)
+const float* param_ptr(const Tensor& t, const c10::Device& dev, const char* name)
+{
+    if (t.device() != dev) throw std::runtime_error(std::string(name) + ": expected a tensor on " + dev.str() + ", got " + t.device().str());
+    if (t.scalar_type() != at::kFloat)
+        throw std::runtime_error(std::string(name) + ": the raw-parameter path needs float32, got " + c10::toString(t.scalar_type()));
+    if (!t.is_contiguous()) throw std::runtime_error(std::string(name) + ": the raw-parameter path needs a contiguous tensor");
+    return t.numel() ? t.data_ptr<float>() : nullptr;
+}
+
+struct ParamPtrs {
+    int P, M;
+    const float *xyz, *dc, *rest, *opacity, *scaling, *rotation;
+};
+
+ParamPtrs check_params(const Tensor& xyz, const Tensor& features_dc, const Tensor& features_rest, const Tensor& opacity,
+                       const Tensor& scaling, const Tensor& rotation, const Tensor& degrees)
+{
+    if (xyz.dim() != 2 || xyz.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
+    const c10::Device dev = xyz.device();
+    if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
+    ParamPtrs p;
+    p.P = (int)xyz.size(0);
+    if (features_dc.dim() != 3 || features_dc.size(0) != p.P || features_dc.size(1) != 1 || features_dc.size(2) != 3)
+        throw std::runtime_error("features_dc must have dimensions (num_points, 1, 3)");
+    const bool no_rest = !features_rest.defined() || features_rest.numel() == 0;
+    if (!no_rest && (features_rest.dim() != 3 || features_rest.size(0) != p.P || features_rest.size(2) != 3))
+        throw std::runtime_error("features_rest must have dimensions (num_points, M-1, 3)");
+    p.M = no_rest ? 1 : 1 + (int)features_rest.size(1);
+    if (p.M > 16) throw std::runtime_error("features_rest must have dimensions (num_points, M-1, 3) with M <= 16");
+    if (scaling.dim() != 2 || scaling.size(0) != p.P || scaling.size(1) != 3)
+        throw std::runtime_error("scaling must have dimensions (num_points, 3)");
+    if (rotation.dim() != 2 || rotation.size(0) != p.P || rotation.size(1) != 4)
+        throw std::runtime_error("rotation must have dimensions (num_points, 4)");
+    if (opacity.numel() != p.P) throw std::runtime_error("opacity must have dimensions (num_points, 1)");
+    if (degrees.numel() != p.P) throw std::runtime_error("degrees must have one entry per point");
+    p.xyz = param_ptr(xyz, dev, "means3D");
+    p.dc = param_ptr(features_dc, dev, "features_dc");
+    p.rest = no_rest ? nullptr : param_ptr(features_rest, dev, "features_rest");
+    p.opacity = param_ptr(opacity, dev, "opacity");
+    p.scaling = param_ptr(scaling, dev, "scaling");
+    p.rotation = param_ptr(rotation, dev, "rotation");
+    return p;
+}
+
+// -> as forward_reserved: (ticket, reserve, num_rendered, flags, out_color, radii, geom, binning, img)
+std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_params_reserved(
+    const Tensor& background, const Tensor& xyz, const Tensor& features_dc, const Tensor& features_rest, const Tensor& degrees,
+    const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, double scale_modifier, const Tensor& viewmatrix,
+    const Tensor& projmatrix, double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& campos,
+    bool prefiltered, bool trains, bool strict, int64_t reserve_override)
+{
+    need_params();
+    const ParamPtrs p = check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees);
+    const c10::Device dev = xyz.device();
+    const int P = p.P, H = (int)image_height, W = (int)image_width;
+    const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
+    const Tensor cp = dev_f32(campos, dev), deg = dev_i32(degrees, dev);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    api.r3dgs_forward_hint(trains ? 1 : 0);
+    const int reserve = reserve_override > 0 ? (int)reserve_override : api.r3dgs_reserve_hint_view(P, W, H, opt_ptr<float>(vm));
+    if (reserve < 0) fail("rasterize_gaussian_params");
+    Tensor none;
+    if (reserve == 0 || P == 0) return {0LL, 0, -1, 0, none, none, none, none, none};
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev), i32 = f32.dtype(at::kInt), u8 = f32.dtype(at::kByte);
+    Tensor out_color = at::empty({3, H, W}, f32), radii = at::empty({P}, i32);
+    Tensor geom = at::empty({(int64_t)blob_bytes(trains ? 0 : 1, P)}, u8);
+    Tensor binning = at::empty({(int64_t)blob_bytes(2, P, W, H, reserve)}, u8);
+    Tensor img = at::empty({(int64_t)blob_bytes(3, W, H)}, u8);
+    const long long ticket = api.r3dgs_forward_params_reserved(
+        reinterpret_cast<char*>(geom.data_ptr()), reinterpret_cast<char*>(binning.data_ptr()),
+        reinterpret_cast<char*>(img.data_ptr()), reserve, P, opt_ptr<int>(deg), p.M, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest,
+        p.opacity, p.scaling, (float)scale_modifier, p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp),
+        (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), nullptr, nullptr,
+        radii.data_ptr<int>(), 0, 0, cur_stream_of(dev));
+    if (ticket < 0) fail("rasterize_gaussian_params");
+    int rendered = -1, flags = 0;
+    if (strict && ticket > 0) {
+        int visible = 0, cap = 0, st;
+        {
+            pybind11::gil_scoped_release nogil;
+            st = api.r3dgs_pass_query(ticket, 1, &rendered, &visible, &cap, &flags);
+        }
+        if (st < 0) fail("num_rendered");
+        if (st != 1) rendered = -1;
+    }
+    return {ticket, reserve, rendered, flags, out_color, radii, geom, binning, img};
+}
+
+// the exact-size path (r3dgs_forward_params): the three blobs are byte tensors allocated from the library's callbacks
+struct BlobSlot {
+    Tensor t;
+    c10::Device dev;
+    bool failed = false;
+    explicit BlobSlot(c10::Device d) : dev(d) {}
+};
+char* blob_alloc(size_t bytes, void* user)
+{
+    BlobSlot* b = static_cast<BlobSlot*>(user);
+    try {
+        b->t = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(b->dev));
+        return reinterpret_cast<char*>(b->t.data_ptr());
+    } catch (...) {   // an exception cannot cross the C frame
+        b->failed = true;
+        return nullptr;
+    }
+}
+
+// -> (num_rendered, out_color, radii, geom, binning, img)
+std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_params(
+    const Tensor& background, const Tensor& xyz, const Tensor& features_dc, const Tensor& features_rest, const Tensor& degrees,
+    const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, double scale_modifier, const Tensor& viewmatrix,
+    const Tensor& projmatrix, double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& campos,
+    bool prefiltered, bool trains, bool debug)
+{
+    need_params();
+    const ParamPtrs p = check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees);
+    const c10::Device dev = xyz.device();
+    const int P = p.P, H = (int)image_height, W = (int)image_width;
+    const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
+    const Tensor cp = dev_f32(campos, dev), deg = dev_i32(degrees, dev);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev), i32 = f32.dtype(at::kInt);
+    Tensor out_color = at::empty({3, H, W}, f32), radii = at::empty({P}, i32);
+    BlobSlot geom(dev), binning(dev), img(dev);
+    api.r3dgs_forward_hint(trains ? 1 : 0);
+    const int rendered = api.r3dgs_forward_params(
+        blob_alloc, &geom, blob_alloc, &binning, blob_alloc, &img, P, opt_ptr<int>(deg), p.M, opt_ptr<float>(bg), W, H, p.xyz, p.dc,
+        p.rest, p.opacity, p.scaling, (float)scale_modifier, p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm),
+        opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), nullptr, nullptr,
+        radii.data_ptr<int>(), 0, debug ? 1 : 0, cur_stream_of(dev));
+    if (geom.failed || binning.failed || img.failed) throw std::runtime_error("rasterize_gaussian_params: a state buffer could not be allocated");
+    if (rendered < 0) fail("rasterize_gaussian_params");
+    const auto u8 = f32.dtype(at::kByte);
+    auto blob = [&](BlobSlot& b) { return b.t.defined() ? b.t : at::empty({0}, u8); };
+    return {rendered, out_color, radii, blob(geom), blob(binning), blob(img)};
+}
+
+// -> (dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_dfeatures_dc, dL_dfeatures_rest, dL_dscaling, dL_drotation): gradients of
+// the tensors passed in, each written whole by the library into at::empty storage of the leaf's own shape
+std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz, const Tensor& radii, const Tensor& features_dc,
+                                    const Tensor& features_rest, const Tensor& degrees, const Tensor& opacity,
+                                    const Tensor& scaling, const Tensor& rotation, double scale_modifier, const Tensor& viewmatrix,
+                                    const Tensor& projmatrix, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color,
+                                    const Tensor& campos, const Tensor& geomBuffer, int64_t capacity, const Tensor& binningBuffer,
+                                    const Tensor& imageBuffer, double lambda_sh_sparsity, bool debug)
+{
+    need_params();
+    const ParamPtrs p = check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees);
+    const c10::Device dev = xyz.device();
+    const int P = p.P, M = p.M;
+    const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    if (P == 0) {
+        return {at::zeros({0, 3}, f32), at::zeros({0, 1}, f32), at::zeros({0, 3}, f32), at::zeros({0, 1, 3}, f32),
+                at::zeros({0, M - 1, 3}, f32), at::zeros({0, 3}, f32), at::zeros({0, 4}, f32)};
+    }
+    Tensor dL_dmeans3D = at::empty({P, 3}, f32), dL_dmeans2D = at::empty({P, 3}, f32), dL_dopacity = at::empty({P, 1}, f32);
+    Tensor dL_ddc = at::empty({P, 1, 3}, f32), dL_drest = at::empty({P, M - 1, 3}, f32);
+    Tensor dL_dscaling = at::empty({P, 3}, f32), dL_drotation = at::empty({P, 4}, f32);
+    // what the C ABI also writes and this path has no leaf for (precomputed colours / covariances): one scratch tensor
+    Tensor scratch = at::empty({P, 9}, f32);
+    const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
+    const Tensor cp = dev_f32(campos, dev), g = dev_f32(dL_dout_color, dev), deg = dev_i32(degrees, dev), rad = dev_i32(radii, dev);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    auto blob = [](const Tensor& t) { return t.defined() && t.numel() != 0 ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
+    const int st = api.r3dgs_backward_params(
+        P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest, p.scaling, (float)scale_modifier,
+        p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy,
+        opt_ptr<int>(rad), blob(geomBuffer), blob(binningBuffer), blob(imageBuffer), opt_ptr<float>(g),
+        dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), scratch.data_ptr<float>(),
+        dL_dmeans3D.data_ptr<float>(), scratch.data_ptr<float>() + 3 * (size_t)P, dL_ddc.data_ptr<float>(),
+        M > 1 ? dL_drest.data_ptr<float>() : nullptr, dL_dscaling.data_ptr<float>(), dL_drotation.data_ptr<float>(),
+        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream_of(dev));
+    if (st < 0) fail("rasterize_gaussian_params_backward");
+    return {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation};
+}
+
+// -> (scales [P,3], rotations [P,4]) by csrc/param_math.h, the values the raw-parameter kernels use
+std::tuple<Tensor, Tensor> activate_params(const Tensor& scaling, const Tensor& rotation)
+{
+    need_params();
+    const c10::Device dev = scaling.device();
+    if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
+    const int P = (int)scaling.size(0);
+    if (scaling.dim() != 2 || scaling.size(1) != 3) throw std::runtime_error("scaling must have dimensions (num_points, 3)");
+    if (rotation.dim() != 2 || rotation.size(0) != P || rotation.size(1) != 4)
+        throw std::runtime_error("rotation must have dimensions (num_points, 4)");
+    const float* sp = param_ptr(scaling, dev, "scaling");
+    const float* rp = param_ptr(rotation, dev, "rotation");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor s = at::empty_like(scaling), q = at::empty_like(rotation);
+    if (P && api.r3dgs_activate_params(P, sp, rp, s.data_ptr<float>(), q.data_ptr<float>(), cur_stream_of(dev)) < 0)
+        fail("activate_params");
+    return {s, q};
 }
 
 // markVisible (rasterize_points.cu:307-326)
@@ -421,6 +639,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("forward_reserved", &forward_reserved);
     m.def("backward", &backward);
     m.def("mark_visible", &mark_visible);
+    m.def("forward_params", &forward_params);
+    m.def("forward_params_reserved", &forward_params_reserved);
+    m.def("backward_params", &backward_params);
+    m.def("activate_params", &activate_params);
     m.def("l1_ssim_forward", &l1_ssim_forward);
     m.def("l1_ssim_backward", &l1_ssim_backward);
     m.def("l1_forward", &l1_forward);

@@ -89,6 +89,17 @@ _lib.r3dgs_backward.argtypes = ([_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _v
                                  _vp, _vp, _vp, _vp] + [_vp] * 10 + [_f, _i, _vp])
 _lib.r3dgs_export_binning.restype = _i
 _lib.r3dgs_export_binning.argtypes = [_i, _i, _i, _i, _i] + [_vp] * 10
+if hasattr(_lib, "r3dgs_forward_params"):   # raster from the model's raw parameters (absent from older A/B builds)
+    _FWD_PARAMS_TAIL = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+    _lib.r3dgs_forward_params.restype = _i
+    _lib.r3dgs_forward_params.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i] + _FWD_PARAMS_TAIL
+    _lib.r3dgs_forward_params_reserved.restype = C.c_longlong
+    _lib.r3dgs_forward_params_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i] + _FWD_PARAMS_TAIL
+    _lib.r3dgs_backward_params.restype = _i
+    _lib.r3dgs_backward_params.argtypes = ([_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f,
+                                            _vp, _vp, _vp, _vp] + [_vp] * 11 + [_f, _i, _vp])
+    _lib.r3dgs_activate_params.restype = _i
+    _lib.r3dgs_activate_params.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
 
 _lib.r3dgs_colour_variance_accumulate.restype = _i
 _lib.r3dgs_colour_variance_accumulate.argtypes = [_i, _vp, _i, _i] + [_vp] * 12
@@ -158,6 +169,8 @@ _EXT_FUNCS = ("r3dgs_last_error", "r3dgs_version", "r3dgs_geometry_bytes", "r3dg
 _EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3dgs_l1_ssim_backward", "r3dgs_l1_workspace_bytes",
                    "r3dgs_l1_forward", "r3dgs_l1_backward",   # optional: an older A/B build has no loss
                    "r3dgs_adam_step", "r3dgs_adam_step_capturable")   # ... nor a fused Adam
+_EXT_PARAMS_FUNCS = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r3dgs_backward_params",
+                     "r3dgs_activate_params")   # ... nor the raw-parameter entry points
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -167,7 +180,7 @@ if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
         _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value
-                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS if hasattr(_lib, f))})
+                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS if hasattr(_lib, f))})
         _ext = _ext_loaded
     except ImportError:
         if _binding_request == "torch":
@@ -684,6 +697,200 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     _check(st, "rasterize_gaussians_backward")
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     return out + (dL_dconic,) if _want_conic else out
+
+
+# ---- raster from the model's raw parameters (include/r3dgs_rasterizer.h r3dgs_*_params) ---------------------------------
+# The tensors travel as GaussianModel stores them: _xyz, _features_dc [P,1,3], _features_rest [P,M-1,3], _opacity, _scaling
+# (log), _rotation (unnormalised).  The kernels apply the activations; the backward returns gradients of exactly these
+# tensors, each written whole by the library into storage of the leaf's own shape -- no cat, narrow or copy on either side.
+# A tensor that would need a copy (not contiguous, not float32) is refused instead of converted.
+
+def _need_params():
+    if not hasattr(_lib, "r3dgs_forward_params"):
+        raise RuntimeError("the loaded libr3dgs_hip.so has no raw-parameter entry points: rebuild it with build.py")
+
+
+def _param(t, dev, name):
+    if t.device != dev:
+        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: the raw-parameter path needs float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name}: the raw-parameter path needs a contiguous tensor")
+    return t
+
+
+def _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees):
+    """-> (P, M, device); the refusals of the raw-parameter path (same messages as csrc_torch/r3dgs_torch.cpp)."""
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    dev = xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    P = int(xyz.size(0))
+    if features_dc.dim() != 3 or tuple(features_dc.shape) != (P, 1, 3):
+        raise RuntimeError("features_dc must have dimensions (num_points, 1, 3)")
+    no_rest = features_rest is None or features_rest.numel() == 0
+    if not no_rest and (features_rest.dim() != 3 or features_rest.size(0) != P or features_rest.size(2) != 3):
+        raise RuntimeError("features_rest must have dimensions (num_points, M-1, 3)")
+    M = 1 if no_rest else 1 + int(features_rest.size(1))
+    if M > 16:
+        raise RuntimeError("features_rest must have dimensions (num_points, M-1, 3) with M <= 16")
+    if tuple(scaling.shape) != (P, 3):
+        raise RuntimeError("scaling must have dimensions (num_points, 3)")
+    if tuple(rotation.shape) != (P, 4):
+        raise RuntimeError("rotation must have dimensions (num_points, 4)")
+    if opacity.numel() != P:
+        raise RuntimeError("opacity must have dimensions (num_points, 1)")
+    if degrees.numel() != P:
+        raise RuntimeError("degrees must have one entry per point")
+    for t, name in ((xyz, "means3D"), (features_dc, "features_dc"), (opacity, "opacity"), (scaling, "scaling"),
+                    (rotation, "rotation")) + (() if no_rest else ((features_rest, "features_rest"),)):
+        _param(t, dev, name)
+    return P, M, dev
+
+
+def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degrees, opacity, scaling, rotation,
+                              scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, campos,
+                              prefiltered, debug, exact=False, _reserve=None, _strict_override=None):
+    """rasterize_gaussians from the model's raw parameters -> (num_rendered, out_color[3,H,W], radii[P], geomBuffer,
+    binningBuffer, imgBuffer); same asynchronous / exact-size / strict-mode behaviour."""
+    _need_params()
+    P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
+    H, W = int(image_height), int(image_width)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    if P == 0:
+        e = torch.empty(0, **u8)
+        return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+    hint = getattr(_tls, "next_forward_trains", None)
+    trains = torch.is_grad_enabled() if hint is None else hint
+    _tls.next_forward_trains = None
+    strict = _strict if _strict_override is None else bool(_strict_override)
+    rest = _NO_TENSOR if M == 1 else features_rest
+    if viewmatrix is not None and viewmatrix.is_contiguous() and viewmatrix.dtype == torch.float32:
+        _track_view(viewmatrix)
+    if _ext is not None:
+        common = (_t(background), xyz, features_dc, rest, degrees, opacity, scaling, rotation, float(scale_modifier),
+                  _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy), H, W, _t(campos), bool(prefiltered), bool(trains))
+        if not exact and not debug:
+            ticket, reserve, rendered, flags, out_color, radii, geom, binning, img = _ext.forward_params_reserved(
+                *common, strict, int(_reserve or 0))
+            if ticket:
+                _stats["reserved_passes"] += 1
+                nr = NumRendered(ticket, reserve, rendered if rendered >= 0 else None)
+                nr._flags = flags
+                if not strict:
+                    _watch_overflow()
+                    return nr, out_color, radii, geom, binning, img
+                if not nr.truncated:
+                    return nr, out_color, radii, geom, binning, img
+                _stats["redone_passes"] += 1
+                del geom, binning, img
+        rendered, out_color, radii, geom, binning, img = _ext.forward_params(*common, bool(debug))
+        _stats["exact_passes"] += 1
+        pairs = int(_lib.r3dgs_forward_pairs())
+        return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom, binning, img
+    out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    deg = _dev_i32(degrees, dev)
+    _lib.r3dgs_forward_hint(int(trains))
+    with _on_device(dev):
+        args = (P, _ptr(deg), M, _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest), _ptr(opacity), _ptr(scaling),
+                float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx), float(tan_fovy),
+                int(bool(prefiltered)), _ptr(out_color), None, None, _ptr(radii), 0, int(bool(debug)), _stream())
+        reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, _ptr(vm))
+        if _reserve is not None:
+            reserve = int(_reserve)
+        if reserve > 0:
+            geom = torch.empty(_blob_bytes("geom" if trains else "geom_lean", P), **u8)
+            binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
+            img = torch.empty(_blob_bytes("img", W, H), **u8)
+            ticket = _lib.r3dgs_forward_params_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *args)
+            if ticket < 0:
+                _check(-1, "rasterize_gaussian_params")
+            _stats["reserved_passes"] += 1
+            nr = NumRendered(ticket, reserve)
+            if not strict:
+                _watch_overflow()
+                return nr, out_color, radii, geom, binning, img
+            if not nr.truncated:
+                return nr, out_color, radii, geom, binning, img
+            _stats["redone_passes"] += 1
+            del geom, binning, img
+        geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
+        rendered = _lib.r3dgs_forward_params(geom.cb, None, binning.cb, None, img.cb, None, *args)
+    for blob in (geom, binning, img):
+        if blob.error is not None:
+            raise blob.error
+    _check(rendered, "rasterize_gaussian_params")
+    _stats["exact_passes"] += 1
+    pairs = int(_lib.r3dgs_forward_pairs())
+    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom.tensor, binning.tensor, img.tensor
+
+
+def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation,
+                                       scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, campos,
+                                       geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug):
+    """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dxyz[P,3], dL_dfeatures_dc[P,1,3], dL_dfeatures_rest[P,M-1,3],
+    dL_dscaling[P,3], dL_drotation[P,4]): gradients of the tensors passed in (raw scaling / rotation included)."""
+    _need_params()
+    P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
+    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    opts = dict(dtype=torch.float32, device=dev)
+    if P == 0:
+        z = lambda *s: torch.zeros(s, **opts)
+        return z(0, 3), z(0, 1), z(0, 3), z(0, 1, 3), z(0, M - 1, 3), z(0, 3), z(0, 4)
+    rest = _NO_TENSOR if M == 1 else features_rest
+    if isinstance(R, NumRendered):
+        cap = R.capacity
+    else:
+        cap = _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+    if _ext is not None:
+        return tuple(_ext.backward_params(_t(background), xyz, _t(radii), features_dc, rest, degrees, opacity, scaling, rotation,
+                                          float(scale_modifier), _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy),
+                                          dL_dout_color, _t(campos), geomBuffer, int(cap), binningBuffer, imageBuffer,
+                                          float(lambda_sh_sparsity), bool(debug)))
+    e = lambda *s: torch.empty(s, **opts)   # every element is written by the library
+    dL_dmeans3D, dL_dmeans2D, dL_dopacity = e(P, 3), e(P, 3), e(P, 1)
+    dL_ddc, dL_drest, dL_dscaling, dL_drotation = e(P, 1, 3), e(P, M - 1, 3), e(P, 3), e(P, 4)
+    scratch = e(P, 9)   # dL_dcolor [P,3] + dL_dcov3D [P,6]: written by the C ABI, no leaf on this path
+    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    g, deg, rad = _dev_f32(dL_dout_color, dev), _dev_i32(degrees, dev), _dev_i32(radii, dev)
+    with _on_device(dev):
+        st = _lib.r3dgs_backward_params(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest),
+                                        _ptr(scaling), float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp),
+                                        float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
+                                        _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), None, _ptr(dL_dopacity),
+                                        scratch.data_ptr(), _ptr(dL_dmeans3D), scratch.data_ptr() + 12 * P, _ptr(dL_ddc),
+                                        _ptr(dL_drest), _ptr(dL_dscaling), _ptr(dL_drotation), float(lambda_sh_sparsity),
+                                        int(bool(debug)), _stream())
+    _check(st, "rasterize_gaussian_params_backward")
+    return dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation
+
+
+def activate_params(scaling, rotation):
+    """(exp(scaling), F.normalize(rotation)) evaluated by the functions the raw-parameter kernels use (csrc/param_math.h):
+    the existing entry points fed these give the fused path's image and binning bit for bit."""
+    _need_params()
+    dev = scaling.device
+    if dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    P = int(scaling.size(0))
+    if scaling.dim() != 2 or scaling.size(1) != 3:
+        raise RuntimeError("scaling must have dimensions (num_points, 3)")
+    if tuple(rotation.shape) != (P, 4):
+        raise RuntimeError("rotation must have dimensions (num_points, 4)")
+    _param(scaling, dev, "scaling")
+    _param(rotation, dev, "rotation")
+    if _ext is not None:
+        return tuple(_ext.activate_params(scaling, rotation))
+    s, q = torch.empty_like(scaling), torch.empty_like(rotation)
+    if P:
+        with _on_device(dev):
+            _check(_lib.r3dgs_activate_params(P, _ptr(scaling), _ptr(rotation), _ptr(s), _ptr(q), _stream()), "activate_params")
+    return s, q
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

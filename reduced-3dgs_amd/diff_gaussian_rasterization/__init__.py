@@ -104,6 +104,58 @@ def rasterize_gaussians(means3D, means2D, sh, degrees, colors_precomp, opacities
                                      cov3Ds_precomp, raster_settings, lambda_sh_sparsity)
 
 
+class _RasterizeGaussianParams(torch.autograd.Function):
+    """Autograd boundary of the rasterizer fed with the model's RAW parameters, as the reference's GaussianModel stores
+    them: xyz, means2D, features_dc [P,1,3], features_rest [P,M-1,3], degrees, opacity (raw), scaling (log), rotation
+    (unnormalised), raster_settings, lambda_sh_sparsity  ->  (color[3,H,W], radii[P]).  exp / normalize / cat happen inside
+    the kernels; the backward hands the library's outputs straight back as the gradients of these tensors."""
+
+    @staticmethod
+    def forward(ctx, xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation, raster_settings,
+                lambda_sh_sparsity):
+        rs = raster_settings
+        args = (rs.bg, xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
+                rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.campos, rs.prefiltered, rs.debug)
+        _C.hint_next_forward(any(ctx.needs_input_grad))
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_native(
+            _C.rasterize_gaussian_params, args, rs.debug, "snapshot_fw.dump")
+        ctx.raster_settings = rs
+        ctx.num_rendered = num_rendered
+        ctx.lambda_sh_sparsity = lambda_sh_sparsity
+        ctx.save_for_backward(xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, radii, geomBuffer,
+                              binningBuffer, imgBuffer)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii):
+        rs = ctx.raster_settings
+        (xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, radii, geomBuffer, binningBuffer,
+         imgBuffer) = ctx.saved_tensors
+        if grad_out_color is None:  # the image did not take part in the loss
+            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=xyz.dtype, device=xyz.device)
+        args = (rs.bg, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.campos, geomBuffer,
+                ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
+        (grad_means2D, grad_opacity, grad_xyz, grad_dc, grad_rest, grad_scaling, grad_rotation) = _call_native(
+            _C.rasterize_gaussian_params_backward, args, rs.debug, "snapshot_bw.dump")
+        if features_rest.numel() == 0:
+            grad_rest = None
+        # one slot per forward input; None for degrees, raster_settings, lambda_sh_sparsity
+        return (grad_xyz, grad_means2D, grad_dc, grad_rest, None, grad_opacity, grad_scaling, grad_rotation, None, None)
+
+
+def rasterize_gaussian_params(xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation, raster_settings,
+                              lambda_sh_sparsity=0.):
+    """The rasterizer from GaussianModel's raw tensors (_xyz, _features_dc, _features_rest, _degrees, _opacity, _scaling,
+    _rotation) -> (color, radii); gradients flow to exactly those tensors."""
+    if features_rest is None:
+        features_rest = torch.Tensor([])
+    return _RasterizeGaussianParams.apply(xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation,
+                                          raster_settings, lambda_sh_sparsity)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

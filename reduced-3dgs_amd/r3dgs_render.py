@@ -1,0 +1,105 @@
+"""r3dgs_render -- `render()` with the keyword surface and result dictionary of the reference's
+gaussian_renderer.render, rasterizing straight from the model's raw parameters when it can.
+
+The reference's render() activates the model in torch on every call -- exp(_scaling), F.normalize(_rotation),
+cat(_features_dc, _features_rest) -- and autograd undoes it again in the backward (slices of the joined SH gradient copied
+into the two parameters' .grad).  Here the rasterizer's per-Gaussian kernels apply the activations and read / write SH as
+the two tensors the model stores (diff_gaussian_rasterization.rasterize_gaussian_params), so none of that glue runs.
+
+    from r3dgs_render import render          # instead of: from gaussian_renderer import render
+
+The fused path is taken when the call asks for nothing it does not cover; otherwise -- pipe.compute_cov3D_python,
+pipe.convert_SHs_python, override_color, variable_sh_bands -- the call does what the reference's does, through the existing
+package entry points.  `pc` is anything shaped like the reference's GaussianModel: _xyz, _features_dc, _features_rest,
+_opacity, _scaling, _rotation, _degrees, active_sh_degree, max_sh_degree (and get_* / get_covariance / per_band_count for
+the fallback routes).
+"""
+import math
+
+import torch
+
+from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C,
+                                         rasterize_gaussian_params)
+
+
+def _settings(camera, pc, pipe, bg_color, scaling_modifier):
+    return GaussianRasterizationSettings(
+        image_height=int(camera.image_height), image_width=int(camera.image_width),
+        tanfovx=math.tan(camera.FoVx * 0.5), tanfovy=math.tan(camera.FoVy * 0.5), bg=bg_color,
+        scale_modifier=scaling_modifier, viewmatrix=camera.world_view_transform, projmatrix=camera.full_proj_transform,
+        sh_degree=pc.active_sh_degree, campos=camera.camera_center, prefiltered=False, debug=bool(pipe.debug))
+
+
+def fused_path_applies(pc, pipe, override_color=None, variable_sh_bands=False):
+    """True when render() will rasterize from the raw parameters: nothing precomputed in Python, dense SH, and parameter
+    tensors the kernels can read in place (float32, contiguous)."""
+    if override_color is not None or variable_sh_bands or pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        return False
+    tensors = (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation)
+    return all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
+
+
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, lambda_sh_sparsity=0.,
+           measure_fps=False, variable_sh_bands=False):
+    """Render the scene seen by `viewpoint_camera`.  bg_color must be a device tensor.
+    -> {"render", "viewspace_points", "visibility_filter", "radii", "FPS"}"""
+    xyz = pc._xyz
+    # a zero tensor whose gradient is the screen-space gradient of the means (densification statistics)
+    screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0
+    try:
+        screenspace_points.retain_grad()
+    except Exception:
+        pass
+    rs = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    fused = fused_path_applies(pc, pipe, override_color, variable_sh_bands)
+
+    if not fused:
+        scales = rotations = cov3D_precomp = shs = colors_precomp = None
+        if pipe.compute_cov3D_python:
+            cov3D_precomp = pc.get_covariance(scaling_modifier)
+        else:
+            scales, rotations = pc.get_scaling, pc.get_rotation
+        if override_color is not None:
+            colors_precomp = override_color
+        elif pipe.convert_SHs_python:
+            from utils.sh_utils import eval_sh   # the training repository's own SH evaluation
+            feats = pc.get_features
+            shs_view = feats.transpose(1, 2).view(-1, 3, (pc.max_sh_degree + 1) ** 2)
+            dirs = pc.get_xyz - viewpoint_camera.camera_center.repeat(feats.shape[0], 1)
+            dirs = dirs / dirs.norm(dim=1, keepdim=True)
+            colors_precomp = torch.clamp_min(eval_sh(pc.active_sh_degree, shs_view, dirs) + 0.5, 0.0)
+        else:
+            shs = pc.get_features
+            if variable_sh_bands:   # the ragged, degree-sorted buffer of the inference path
+                shs = torch.cat([t.flatten() for t in shs])
+
+    fps = 0
+    if measure_fps:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+    if fused:
+        image, radii = rasterize_gaussian_params(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._degrees,
+                                                 pc._opacity, pc._scaling, pc._rotation, rs, lambda_sh_sparsity)
+    elif variable_sh_bands:
+        dev = xyz.device
+        per_band = torch.tensor(pc.per_band_count, device=dev, dtype=torch.int)
+        cumsum = torch.cumsum(per_band, dim=0).to(dtype=torch.int)
+        coeffs = torch.tensor([i * i for i in range(1, len(pc.per_band_count) + 1)], device=dev, dtype=torch.int)
+        none = torch.Tensor([])
+        _, image, radii, _, _, _ = _C.rasterize_gaussians_variableSH_bands(
+            rs.bg, pc.get_xyz, none, pc._opacity, scales, rotations, rs.scale_modifier, none, rs.viewmatrix, rs.projmatrix,
+            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs, per_band, cumsum, coeffs, pc._degrees, rs.campos,
+            rs.prefiltered, rs.debug)
+    else:
+        image, radii = GaussianRasterizer(raster_settings=rs)(
+            means3D=pc.get_xyz, means2D=screenspace_points, shs=shs, degrees=pc._degrees, colors_precomp=colors_precomp,
+            opacities=pc._opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
+            lambda_sh_sparsity=lambda_sh_sparsity)
+    if measure_fps:
+        t1.record()
+        torch.cuda.synchronize()
+        fps = 1 / t0.elapsed_time(t1)
+
+    # culled Gaussians (radius 0) take no part in the densification statistics
+    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+            "FPS": fps}
