@@ -126,12 +126,43 @@ __device__ __forceinline__ void stage_entry(LdsRec& dst, const float4& a, const 
 #undef R3_LDS_V
 }
 
+// The forward does not need c.yzw; it parks the entry's 1-based list position in c.y instead, so that the position comes
+// back with the record's last word (one ds_read_b64) as a VGPR: n_contrib = pos is then a full-rate v_mov from a VGPR instead
+// of an s_add + v_mov from an SGPR (half rate), paid once per chunk and lane here instead of once per blended entry.
+__device__ __forceinline__ void stage_entry_fwd(LdsRec& dst, const float4& a, const float4& b, const float4& c, uint32_t pos1)
+{
+    typedef float v2f __attribute__((ext_vector_type(2)));
+#define R3_LDS_V(T) volatile T __attribute__((address_space(3)))*
+    R3_LDS_V(float) d = (R3_LDS_V(float))reinterpret_cast<float*>(&dst);
+    *(R3_LDS_V(v2f))d = v2f{a.x, a.y};
+    *(R3_LDS_V(v2f))(d + 2) = v2f{(-0.5f * kLog2e) * a.z, -kLog2e * a.w};
+    d[4] = (-0.5f * kLog2e) * b.x;
+    d[5] = b.y;
+    *(R3_LDS_V(v2f))(d + 6) = v2f{b.z, b.w};
+    d[8] = c.x;
+    d[9] = __uint_as_float(pos1);
+#undef R3_LDS_V
+}
+
+__device__ __forceinline__ uint32_t staged_pos1(const LdsRec& r) { return __float_as_uint(r.c.y); }
+
 // consecutive logical ids on one XCD: hardware places workgroup b on XCD b % 8 (speed only, never correctness)
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nblocks)
 {
     const uint32_t per = nblocks >> 3;
     if (b >= per * 8) return b;  // tail
     return (b & 7u) * per + (b >> 3);
+}
+
+// mask &= ~(1 << j) on the scalar unit in ONE instruction (the compiler's  m & (m - 1)  is s_add_u32 + s_addc_u32 + s_and_b64;
+// the scalar unit of a CU is shared by its four SIMDs and more than half busy in the forward)
+__device__ __forceinline__ void clear_bit(unsigned long long& mask, int j)
+{
+#ifdef R3_OLD_TRIP_FORMS
+    mask &= ~(1ull << j);
+#else
+    asm("s_bitset0_b64 %0, %1" : "+s"(mask) : "s"(j));
+#endif
 }
 
 #define R3_DPP_ADD(v, ctrl, rmask) \
@@ -222,18 +253,22 @@ constexpr int kFwdBatch = 4;   // entries per trip of the forward's entry loop: 
 template <int N, int PPL>
 __device__ __forceinline__ unsigned long long fwd_batches(unsigned long long anymask, const unsigned long long* qmask,
                                                           const LdsRec* s_rec, const float* pxf, const float* pyf,
-                                                          uint32_t first_pos, FwdPix* pix)
+                                                          FwdPix* pix)
 {
-    while (__builtin_popcountll(anymask) >= N) {
+    // the survivors are counted once and the count carried in a scalar register: `popcount(mask) >= N` per trip is an
+    // s_bcnt1 and a 64-bit VECTOR compare (there is no scalar one for "greater")
+    for (int left = __builtin_popcountll(anymask); left >= N; left -= N) {
         int j[N];
         QSplat sp[N];
+        uint32_t pos1[N];
         float al[N][PPL];
         bool inb[N][PPL];
 #pragma unroll
         for (int i = 0; i < N; i++) {
             j[i] = __builtin_ctzll(anymask);
-            anymask &= anymask - 1ull;
+            clear_bit(anymask, j[i]);
             sp[i] = load_splat(s_rec[j[i]]);
+            pos1[i] = staged_pos1(s_rec[j[i]]);
         }
 #pragma unroll
         for (int i = 0; i < N; i++)
@@ -245,7 +280,7 @@ __device__ __forceinline__ unsigned long long fwd_batches(unsigned long long any
             for (int q = 0; q < PPL; q++)
                 if (PPL == 1 || ((qmask[q] >> j[i]) & 1ull)) {   // one quadrant per wave: anymask IS its mask
                     float Tb;
-                    fwd_apply(sp[i], al[i][q], inb[i][q], first_pos + (uint32_t)j[i] + 1u, pix[q], &Tb);
+                    fwd_apply(sp[i], al[i][q], inb[i][q], pos1[i], pix[q], &Tb);
                 }
     }
     return anymask;
@@ -318,7 +353,7 @@ __global__ __launch_bounds__(64) void blend_fwd_kernel(const BlendFwdArgs* __res
             }
         }
         __syncthreads();
-        stage_entry(s_rec[lane], nxa, nxb, nxc);
+        stage_entry_fwd(s_rec[lane], nxa, nxb, nxc, base - range.x + (uint32_t)lane + 1u);
         if (COUNTERS) s_id[lane] = nxid;
         // region pre-test: lane j decides for entry j which of this wave's quadrants it can reach at all
         unsigned long long qmask[PPL], anymask = 0ull;
@@ -357,14 +392,14 @@ __global__ __launch_bounds__(64) void blend_fwd_kernel(const BlendFwdArgs* __res
         // is paid once per batch: the forward is as sensitive to those as to vector instructions (one entry per trip 0.176 ms,
         // two 0.171, two without per-entry "is there a second one" tests 0.159, four 0.158).
         if (!COUNTERS) {
-            anymask = fwd_batches<kFwdBatch, PPL>(anymask, qmask, s_rec, pxf, pyf, base - range.x, pix);
-            anymask = fwd_batches<2, PPL>(anymask, qmask, s_rec, pxf, pyf, base - range.x, pix);
+            anymask = fwd_batches<kFwdBatch, PPL>(anymask, qmask, s_rec, pxf, pyf, pix);
+            anymask = fwd_batches<2, PPL>(anymask, qmask, s_rec, pxf, pyf, pix);
         }
         while (anymask) {  // surviving entries, front to back
             const int j = __builtin_ctzll(anymask);
-            anymask &= anymask - 1ull;
+            clear_bit(anymask, j);
             const QSplat s = load_splat(s_rec[j]);
-            const uint32_t pos1 = base - range.x + (uint32_t)j + 1u;
+            const uint32_t pos1 = staged_pos1(s_rec[j]);
             int cnt = 0;
             float tsum = 0.f;
 #pragma unroll
@@ -469,6 +504,10 @@ __global__ __launch_bounds__(64, R3_BWD_OCC) void blend_bwd_kernel(BwdPassArgs* 
     R3_TL_BEGIN(blockIdx.x)
     const BlendBwdArgs a = FIRST ? v.blend : dst->blend;
     __shared__ float s_grad[kChunk * kGradStride];
+#ifndef R3_OLD_TRIP_FORMS
+    __shared__ float4 s_zero[3];   // nine zeros (and three spare): what the sums of an entry are reset from, see below
+    if (threadIdx.x < 3) s_zero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
     constexpr int PARTS = 4 / PPL;
     const int lane = threadIdx.x;
     uint32_t wg, seg = 0u, nseg = 1u, walk_log2 = 0u;
@@ -596,8 +635,10 @@ __global__ __launch_bounds__(64, R3_BWD_OCC) void blend_bwd_kernel(BwdPassArgs* 
                     qmask[q] = __ballot(have && region_may_contribute(mine, qx0[q], qx0[q] + 7.f, qy0[q], qy0[q] + 7.f));
                 }
                 // entries behind the quadrant's deepest contributor / behind this unit's segment (scalar arithmetic)
-                const uint32_t left = qlast[q] > (uint32_t)cbase ? qlast[q] - (uint32_t)cbase : 0u;
-                if (left < (uint32_t)kChunk) qmask[q] &= (1ull << left) - 1ull;
+                // (signed: written as an unsigned saturating difference this has no scalar instruction and came out as
+                // v_mov + v_sub clamp + v_cmp + v_readfirstlane per quadrant and chunk)
+                const int left = max((int)qlast[q] - cbase, 0);
+                if (left < kChunk) qmask[q] &= (1ull << left) - 1ull;
                 anymask |= qmask[q];
             }
         }
@@ -636,7 +677,22 @@ __global__ __launch_bounds__(64, R3_BWD_OCC) void blend_bwd_kernel(BwdPassArgs* 
                 asm("" : "+s"(joff));   // stays a scalar multiply + v_add (else: one quarter-rate v_mad_u64_u32)
                 if (writer) s_grad_slot[joff] = z;
                 contributed |= 1ull << j;
+#ifndef R3_OLD_TRIP_FORMS
+                {   // The nine sums are cleared by three broadcast LDS reads of zeros (2 x b128 + b32) instead of nine v_mov:
+                    // the kernel is bound by VALU issue and the LDS pipe is not, the reads return ahead of the next entry's
+                    // record (same queue, issued first), and no VGPR is added (the address register of s_rec serves).
+                    // 33 -> 24 VALU per reduced entry; metric shape 1512 -> 1526 it/s (profiles/blend_inner_loop_ab.txt, visit 1).
+                    typedef float v4f __attribute__((ext_vector_type(4)));
+                    const volatile v4f __attribute__((address_space(3)))* zp =
+                        (const volatile v4f __attribute__((address_space(3)))*)reinterpret_cast<float*>(s_zero);
+                    const v4f z0 = zp[0], z1 = zp[1];
+                    const float z2 = *(const volatile float __attribute__((address_space(3)))*)(zp + 2);
+                    sg.sx = z0.x; sg.sy = z0.y; sg.sxx = z0.z; sg.sxy = z0.w;
+                    sg.syy = z1.x; sg.sm = z1.y; sg.r = z1.z; sg.g = z1.w; sg.b = z2;
+                }
+#else
                 sg.sx = sg.sy = sg.sxx = sg.sxy = sg.syy = sg.sm = sg.r = sg.g = sg.b = 0.f;
+#endif
             }
         }
         __syncthreads();

@@ -166,9 +166,29 @@ R3_HD float fwd_alpha(const QSplat& s, float pxf, float pyf, bool* in_bound)
 R3_HD int fwd_apply(const QSplat& s, float alpha, bool in_bound, uint32_t pos1, FwdPix& p, float* T_before)
 {
     if (!(in_bound && alpha >= 1.0f / 255.0f)) return 0;
-    const float w = alpha * p.T;
-    const float Tn = p.T - w;                 // T * (1 - alpha), forward.cu:547
+#if (defined(__HIP_DEVICE_COMPILE__) || defined(R3_TRIP_FORMS_ON_HOST)) && !defined(R3_OLD_TRIP_FORMS)
+    // Same two roundings as below (the compiler contracts  T - alpha T  into fma(-alpha, T, T) and forms w on its own), in
+    // an order that lets the running product be updated in place: w is formed while T still holds the old value, so the
+    // new one needs no temporary and no v_mov back into T after the blend (one VALU instruction per passing entry).
+    // R3_OLD_TRIP_FORMS keeps the earlier form for tests/test_blend_trip_forms.py, which runs both on the CPU with
+    // contraction on (R3_TRIP_FORMS_ON_HOST) and compares bits.
+    float w = alpha * p.T;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(w));
+#endif
     *T_before = p.T;
+    const float Tn = __builtin_fmaf(-alpha, p.T, p.T);
+#else
+    const float w = alpha * p.T;
+#if defined(R3_TRIP_FORMS_ON_HOST)
+    // what the device compiler makes of the line below: it fuses a multiply that has other uses (w stays a product of its
+    // own), the host compiler does not, so the test build of the old form spells the device's contraction out
+    const float Tn = __builtin_fmaf(-alpha, p.T, p.T);
+#else
+    const float Tn = p.T - w;                 // T * (1 - alpha), forward.cu:547
+#endif
+    *T_before = p.T;
+#endif
     p.T = Tn;
     if (!(Tn >= 0.0001f)) return 2;           // saturated here, earlier, or outside the image: not blended
     p.C0 += s.r * w;
