@@ -490,17 +490,20 @@ struct ViewParams {
     float scale_modifier;
 };
 
-__device__ __forceinline__ Camera load_camera(const ViewParams& v)
+// `view`, `proj`, `campos`: v's three pointers, as they are or cast to the global address space (global_ptr() above; the loads
+// are then scalar loads instead of FLAT ones)
+template <class Ptr>
+__device__ __forceinline__ Camera load_camera_from(Ptr view, Ptr proj, Ptr campos, const ViewParams& v)
 {
     Camera c;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        c.view[k] = v.view[k];
-        c.proj[k] = v.proj[k];
+        c.view[k] = view[k];
+        c.proj[k] = proj[k];
     }
-    c.campos[0] = v.campos[0];
-    c.campos[1] = v.campos[1];
-    c.campos[2] = v.campos[2];
+    c.campos[0] = campos[0];
+    c.campos[1] = campos[1];
+    c.campos[2] = campos[2];
     c.tan_fovx = v.tan_fovx;
     c.tan_fovy = v.tan_fovy;
     c.focal_y = v.H / (2.0f * v.tan_fovy);  // rasterizer_impl.cu:386-387
@@ -512,6 +515,7 @@ __device__ __forceinline__ Camera load_camera(const ViewParams& v)
     c.scale_modifier = v.scale_modifier;
     return c;
 }
+__device__ __forceinline__ Camera load_camera(const ViewParams& v) { return load_camera_from(v.view, v.proj, v.campos, v); }
 
 struct FwdInputs {
     int P, M;

@@ -71,19 +71,20 @@ __device__ __forceinline__ int split_lds_index(int f, int rl, int k0, int M)
 
 // one span (len floats, 16-byte aligned and len % 4 == 0 when VEC) global -> LDS
 template <bool ROWS48, bool VEC>
-__device__ __forceinline__ void stage_split_span(const float* __restrict__ src, int len, int rl, int k0, int M, float* lds,
+__device__ __forceinline__ void stage_split_span(const R3_GLOBAL float* __restrict__ src, int len, int rl, int k0, int M, float* lds,
                                                  int lane)
 {
     if (VEC) {
         constexpr int kBatch = 6;
-        const float4* src4 = reinterpret_cast<const float4*>(src);
+        const R3_GLOBAL float4* src4 = reinterpret_cast<const R3_GLOBAL float4*>(src);
         const int n4 = len >> 2;
         for (int base = 0; base < n4; base += 64 * kBatch) {
             float4 v[kBatch];
 #pragma unroll
             for (int k = 0; k < kBatch; k++) {
                 const int e4 = base + k * 64 + lane;
-                v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (e4 < n4) v[k] = src4[e4];
             }
 #pragma unroll
             for (int k = 0; k < kBatch; k++) {
@@ -104,11 +105,11 @@ __device__ __forceinline__ void stage_split_span(const float* __restrict__ src, 
 
 // one span LDS -> global (the gradient rows), or zeros when the wave built no rows
 template <bool ROWS48, bool VEC>
-__device__ __forceinline__ void unstage_split_span(float* __restrict__ dst, int len, int rl, int k0, int M, const float* lds,
+__device__ __forceinline__ void unstage_split_span(R3_GLOBAL float* __restrict__ dst, int len, int rl, int k0, int M, const float* lds,
                                                    int lane, bool rows)
 {
     if (VEC) {
-        float4* dst4 = reinterpret_cast<float4*>(dst);
+        R3_GLOBAL float4* dst4 = reinterpret_cast<R3_GLOBAL float4*>(dst);
         const int n4 = len >> 2;
         if (rows) {
             for (int e4 = lane; e4 < n4; e4 += 64) {
@@ -170,7 +171,7 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
     const uint32_t knext = (uint32_t)__shfl_down((int)key, 1);
     const uint32_t key0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);   // the group's first run (all lanes active here)
     if (valid && (lane == 63 || knext != key)) {  // last lane of a run: holds the run's sum inside this group
-        const uint32_t gid = a.order ? a.order[key] : key;
+        const uint32_t gid = a.order ? global_ptr(a.order)[key] : key;
         // does the run reach across the borders of this group?  The neighbouring pairs' keys say so (runs are contiguous:
         // same key <=> same run); asking the Gaussian's record for its pair range was a dependent gather per run
         const bool from_before = key == key0 && key_before == key;
@@ -182,9 +183,9 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
         if (!from_before && !into_next) {
 #ifdef R3_ACC_IN_SLAB   // experiment: the run sum stays where the run ends (a write next to the rows this wave just read) and the
                         // per-Gaussian kernel gathers it by pair_start instead of reading a row this store scattered
-            float4* dst = reinterpret_cast<float4*>(const_cast<float*>(a.pair_grad) + (size_t)e * kPairStride);
+            auto* dst = reinterpret_cast<R3_GLOBAL float4*>(global_ptr(const_cast<float*>(a.pair_grad)) + (size_t)e * kPairStride);
 #else
-            float4* dst = reinterpret_cast<float4*>(a.acc + (size_t)gid * kAccStride);   // 48-B row: three 16-B stores
+            auto* dst = reinterpret_cast<R3_GLOBAL float4*>(global_ptr(a.acc) + (size_t)gid * kAccStride);   // 48-B row: three 16-B stores
 #endif
 #ifndef R3_NO_ZERO_ROW_SKIP
             // A run without a contributing pair (all nine sums exactly zero: a third of the visible Gaussians of the metric scene,
@@ -206,16 +207,16 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
             if (kAccStride >= 16) dst[3] = make_float4(0.f, 0.f, 0.f, 0.f);   // 64-byte rows: the whole burst is written
 #endif
         } else {
-            float* wp = a.wave_part + (size_t)(e >> 6) * 2 * kPieceStride;
+            R3_GLOBAL float* wp = global_ptr(a.wave_part) + (size_t)(e >> 6) * 2 * kPieceStride;
 #ifdef R3_WP_VEC
             if (from_before) {  // continues a run of the previous group: this group's leading piece
-                float4* w4 = reinterpret_cast<float4*>(wp);
+                auto* w4 = reinterpret_cast<R3_GLOBAL float4*>(wp);
                 w4[0] = make_float4(v[0], v[1], v[2], v[3]);
                 w4[1] = make_float4(v[4], v[5], v[6], v[7]);
                 w4[2] = make_float4(v[8], 0.f, 0.f, 0.f);
             }
             if (into_next) {  // continues into the next group: trailing piece
-                float4* w4 = reinterpret_cast<float4*>(wp + kPieceStride);
+                auto* w4 = reinterpret_cast<R3_GLOBAL float4*>(wp + kPieceStride);
                 w4[0] = make_float4(v[0], v[1], v[2], v[3]);
                 w4[1] = make_float4(v[4], v[5], v[6], v[7]);
                 w4[2] = make_float4(v[8], 0.f, 0.f, 0.f);
@@ -241,12 +242,12 @@ __attribute__((amdgpu_waves_per_eu(R3_PR_WAVES, R3_PR_WAVES)))
 __global__ __launch_bounds__(256) void pair_reduce_kernel(const PairReduceArgs* __restrict__ ap)
 {
     const PairReduceArgs a = *ap;
-    const uint32_t R = a.hdr->num_pairs;
+    const uint32_t R = global_ptr(a.hdr)->num_pairs;
     constexpr uint32_t kPerBlock = 256u * kReduceGroups;
   for (uint32_t blk = blockIdx.x; blk * kPerBlock < R; blk += gridDim.x) {   // logical blocks strided over the grid (common.h)
-    const float* __restrict__ pair_grad = a.pair_grad;
-    unsigned char* __restrict__ pair_flag = a.pair_flag;
-    const uint32_t* __restrict__ pair_gid = a.pair_rank;
+    const R3_GLOBAL float* __restrict__ pair_grad = global_ptr(a.pair_grad);
+    R3_GLOBAL unsigned char* __restrict__ pair_flag = global_ptr(a.pair_flag);
+    const R3_GLOBAL uint32_t* __restrict__ pair_gid = global_ptr(a.pair_rank);
     const uint32_t rank_mask = a.rank_mask;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t e0 = blk * kPerBlock + (uint32_t)wave * (64u * kReduceGroups) + (uint32_t)lane;
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const PairReduceArgs* 
         if (flag[g]) {  // ~1/3 of the pairs contribute; the rest of the slab is stale memory, never read
 #endif
             pair_flag[e] = 0;  // consumed: all flags are zero again when this kernel ends (next backward pass)
-            const float4* src = reinterpret_cast<const float4*>(pair_grad + (size_t)e * kPairStride);
+            const auto* src = reinterpret_cast<const R3_GLOBAL float4*>(pair_grad + (size_t)e * kPairStride);
             const float4 r0 = src[0], r1 = src[1];
             v[g][0] = r0.x; v[g][1] = r0.y; v[g][2] = r0.z; v[g][3] = r0.w;
             v[g][4] = r1.x; v[g][5] = r1.y; v[g][6] = r1.z; v[g][7] = r1.w;
@@ -310,17 +311,81 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     const int i = blockIdx.x * kBwdBlock + tid;
     const bool valid = i < P;
     const int wave_first = blockIdx.x * kBwdBlock + wave * 64;
-    const Camera cam = load_camera(a.view);
+    // Every pointer of the block goes through global_ptr() (common.h): as FLAT accesses the loads below counted on the LDS
+    // counter too and each of the kernel's 24 waits drained both counters; as GLOBAL ones the camera and the header words are
+    // scalar loads, and the waits for the LDS rows leave the memory loads in flight.
+    const Camera cam = load_camera_from(global_ptr(a.view.view), global_ptr(a.view.proj), global_ptr(a.view.campos), a.view);
     const bool has_sh = a.in.shs != nullptr;
+    const auto* hdr = global_ptr(a.header);
+    const uint32_t num_pairs = hdr->num_pairs, n_visible = hdr->visible, hdr_sh_cache = hdr->sh_cache;   // wave-uniform
+    // the forward left the SH direction derivatives and there is no sparsity term: the SH rows are not read at all
+    const bool cached = has_sh && a.sh_ddir != nullptr && hdr_sh_cache != 0u;
 
-    const bool vis = valid && a.radii[i] > 0;
+    // ---- load phase: every input of lane i whose address is a function of i alone is requested here, before the first use
+    // of any of them, so that a lane pays one round trip to memory behind `radii` instead of the chain record -> pair count -> acc row
+    // -> scales / rotations -> degree -> direction derivatives (eight dependent trips, each behind a full drain).  The tests
+    // that used to guard the loads are applied to the loaded values below.  Left where they were: the wave_part pieces of a
+    // run that spans several 64-pair groups (their address comes out of the record: the one dependent load), and the SH rows
+    // of the row-reading path (a wave's staging loop, issued behind these loads).  The derivatives wait for the header word
+    // that says whether the blob holds them (a blob without them ends in front of that array).
+    // Culled lanes: radii first and the rest for the visible lanes only -- two trips, no byte read for a culled Gaussian (the
+    // default); or -DR3_PREBWD_LOAD_CULLED=1: every lane i < P loads everything at once -- one trip, ~20 % more bytes read at
+    // the metric shape, 180 B instead of 4 per culled Gaussian.  Measured equal at 500 k and 2 M (profiles/prebwd_loads.txt);
+    // a view of a trained scene culls most of its Gaussians, so the form that reads nothing for them is the one built.
+#ifndef R3_PREBWD_LOAD_CULLED
+#define R3_PREBWD_LOAD_CULLED 0
+#endif
+    // (The arrays and the record stay uninitialised on the lanes that load nothing -- they are read only where `vis` holds:
+    // merged with constants, the compiler copies each loaded register at the end of the phase, which waits for all of them.)
+    int radius = 0, deg = 0;
+    uint32_t ntile = 0u;
+    GRec r;
+    float4 a0, a1, a2;
+    float m3[3], sc[3], q[4], c6[6], d9in[9];
+    const auto load_lane = [&]() {
+        r = global_ptr(a.rec)[i];
+        ntile = global_ptr(a.tiles)[i];
+#ifndef R3_ACC_IN_SLAB
+        const auto* arow = reinterpret_cast<const R3_GLOBAL float4*>(global_ptr(a.acc) + (size_t)i * kAccStride);
+        a0 = arow[0];
+        a1 = arow[1];
+        a2 = arow[2];
+#endif
+        for (int k = 0; k < 3; k++) m3[k] = global_ptr(a.in.means3D)[3 * i + k];
+        if (!a.in.cov3D_precomp) {
+            for (int k = 0; k < 3; k++) sc[k] = global_ptr(a.in.scales)[3 * i + k];
+            for (int k = 0; k < 4; k++) q[k] = global_ptr(a.in.rotations)[4 * i + k];
+        }
+        if (has_sh) deg = global_ptr(a.in.degrees)[i];
+        if (cached) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) d9in[k] = global_ptr(a.sh_ddir)[9 * (size_t)i + k];
+        }
+        if (a.in.cov3D_precomp) {   // (a block of its own and the last one: the registers of its six words are free on the other
+                                    // path, and a load issued behind a block that reused one would wait for every load before it)
+            for (int k = 0; k < 6; k++) c6[k] = global_ptr(a.in.cov3D_precomp)[6 * i + k];
+            sc[0] = sc[1] = sc[2] = 0.f;
+            q[0] = 1.f;
+            q[1] = q[2] = q[3] = 0.f;
+        }
+    };
+#if R3_PREBWD_LOAD_CULLED
+    if (valid) {
+        radius = global_ptr(a.radii)[i];
+        load_lane();
+    }
+    const bool vis = valid && radius > 0;
+#else
+    if (valid) radius = global_ptr(a.radii)[i];
+    const bool vis = valid && radius > 0;
+    if (vis) load_lane();
+#endif
+
     const int nrows = max(0, min(64, P - wave_first));
     const int span_len = has_sh ? nrows * 3 * M : 0;
     const long span_first = 3L * M * wave_first;
     float* lds = s_sh[wave];
     const bool wave_vis = __ballot(vis) != 0ull;
-    // the forward left the SH direction derivatives and there is no sparsity term: the SH rows are not read at all
-    const bool cached = has_sh && a.sh_ddir != nullptr && a.header->sh_cache != 0u;
     // The workgroups that start together (three per CU) would load their SH rows together, compute together and store
     // together: HBM idle while they compute, the SIMDs idle while they wait.  The second and third of a CU start a step
     // later each.  (Only when the rows are read: without that phase the stagger costs 2 us instead of saving 4.)
@@ -331,18 +396,20 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     if (RAW) {
         if (wave_vis && !cached) {
             const int rl = 3 * (M - 1);
+            const auto* dc = global_ptr(a.in.shs) + 3L * wave_first;
+            const auto* rest = global_ptr(a.shs_rest) + (long)rl * wave_first;
             if ((nrows & 3) == 0) {   // both spans start 16-byte aligned (wave_first % 64 == 0); full waves: lengths % 4 == 0
-                stage_split_span<ROWS48, true>(a.in.shs + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane);
-                if (M > 1) stage_split_span<ROWS48, true>(a.shs_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane);
+                stage_split_span<ROWS48, true>(dc, 3 * nrows, 3, 0, M, lds, lane);
+                if (M > 1) stage_split_span<ROWS48, true>(rest, rl * nrows, rl, 3, M, lds, lane);
             } else {
-                stage_split_span<ROWS48, false>(a.in.shs + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane);
-                if (M > 1) stage_split_span<ROWS48, false>(a.shs_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane);
+                stage_split_span<ROWS48, false>(dc, 3 * nrows, 3, 0, M, lds, lane);
+                if (M > 1) stage_split_span<ROWS48, false>(rest, rl * nrows, rl, 3, M, lds, lane);
             }
         }
     } else if (has_sh && wave_vis && !cached) {
-        const float* src = a.in.shs + span_first;
+        const R3_GLOBAL float* src = global_ptr(a.in.shs) + span_first;
         if (((span_first | span_len) & 3) == 0) {   // 16-B aligned span (always for M = 16): dwordx4 loads, six in
-            const float4* src4 = reinterpret_cast<const float4*>(src);   // flight before the first LDS store (twelve, as in
+            const auto* src4 = reinterpret_cast<const R3_GLOBAL float4*>(src);   // flight before the first LDS store (twelve, as in
             const int n4 = span_len >> 2;                                // the forward's colour kernel, cost a wave of occupancy)
             constexpr int kBatch = 6;
             for (int base = 0; base < n4; base += 64 * kBatch) {
@@ -350,7 +417,8 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
 #pragma unroll
                 for (int k = 0; k < kBatch; k++) {
                     const int e4 = base + k * 64 + lane;
-                    v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (e4 < n4) v[k] = src4[e4];
                 }
 #pragma unroll
                 for (int k = 0; k < kBatch; k++) {
@@ -384,23 +452,22 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     int K = 0;
     const ShRowLdsRW<ROWS48> row{ROWS48 ? lds + 49 * lane : lds, ROWS48 ? 0 : lane * 3 * M};
     if (vis) {
-        const float mx = a.in.means3D[3 * i], my = a.in.means3D[3 * i + 1], mz = a.in.means3D[3 * i + 2];
-        const GRec r = a.rec[i];
+        const float mx = m3[0], my = m3[1], mz = m3[2];
         // 2D-stage gradient row: final in acc[], or in <= tiles/64 + 2 ordered pieces.  A Gaussian whose pairs did not
         // all fit the pass's pair reservation (num_rendered > reserve: the farthest pairs were dropped and the pass is
         // flagged) gets zero 2D-stage gradients instead of a partial sum.
-        const uint32_t start = r.pair_start, ntile = a.tiles[i];
-        if (a.wave_part && start != 0xFFFFFFFFu && start + ntile <= a.header->num_pairs) {
+        const uint32_t start = r.pair_start;
+        if (a.wave_part && start != 0xFFFFFFFFu && start + ntile <= num_pairs) {
             float acc9[kPairGrad];
             const uint32_t last = start + ntile - 1u;
             const uint32_t w0 = start >> 6, w1 = last >> 6;
             if (w0 == w1) {
 #ifdef R3_ACC_IN_SLAB
-                const float4* ap = reinterpret_cast<const float4*>(a.pair_grad + (size_t)last * kPairStride);
-#else
-                const float4* ap = reinterpret_cast<const float4*>(a.acc + (size_t)i * kAccStride);
+                const auto* arow = reinterpret_cast<const R3_GLOBAL float4*>(global_ptr(a.pair_grad) + (size_t)last * kPairStride);
+                a0 = arow[0];
+                a1 = arow[1];
+                a2 = arow[2];
 #endif
-                float4 a0 = ap[0], a1 = ap[1], a2 = ap[2];
 #ifndef R3_NO_ZERO_ROW_SKIP
                 if (__float_as_uint(a2.y) != a.stamp0 || __float_as_uint(a2.z) != a.stamp1)   // not written by this pass: zeros
                     a0 = a1 = a2 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -408,26 +475,27 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
                 acc9[0] = a0.x; acc9[1] = a0.y; acc9[2] = a0.z; acc9[3] = a0.w;
                 acc9[4] = a1.x; acc9[5] = a1.y; acc9[6] = a1.z; acc9[7] = a1.w;
                 acc9[8] = a2.x;
-            } else {
+            } else {   // the one dependent load of the kernel: which groups hold the run's pieces comes out of the record
+                const R3_GLOBAL float* wave_part = global_ptr(a.wave_part);
 #ifdef R3_WP_VEC
-                const float4* w4 = reinterpret_cast<const float4*>(a.wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride);
+                const auto* w4 = reinterpret_cast<const R3_GLOBAL float4*>(wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride);
                 float4 p0 = w4[0], p1 = w4[1], p2 = w4[2];
                 acc9[0] = p0.x; acc9[1] = p0.y; acc9[2] = p0.z; acc9[3] = p0.w;
                 acc9[4] = p1.x; acc9[5] = p1.y; acc9[6] = p1.z; acc9[7] = p1.w;
                 acc9[8] = p2.x;
                 for (uint32_t w = w0 + 1; w <= w1; w++) {  // leading piece of every following group
-                    w4 = reinterpret_cast<const float4*>(a.wave_part + (size_t)w * 2 * kPieceStride);
+                    w4 = reinterpret_cast<const R3_GLOBAL float4*>(wave_part + (size_t)w * 2 * kPieceStride);
                     p0 = w4[0]; p1 = w4[1]; p2 = w4[2];
                     acc9[0] += p0.x; acc9[1] += p0.y; acc9[2] += p0.z; acc9[3] += p0.w;
                     acc9[4] += p1.x; acc9[5] += p1.y; acc9[6] += p1.z; acc9[7] += p1.w;
                     acc9[8] += p2.x;
                 }
 #else
-                const float* wp = a.wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride;  // trailing piece of w0
+                const R3_GLOBAL float* wp = wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride;  // trailing piece of w0
 #pragma unroll
                 for (int k = 0; k < kPairGrad; k++) acc9[k] = wp[k];
                 for (uint32_t w = w0 + 1; w <= w1; w++) {  // leading piece of every following group
-                    wp = a.wave_part + (size_t)w * 2 * kPieceStride;
+                    wp = wave_part + (size_t)w * 2 * kPieceStride;
 #pragma unroll
                     for (int k = 0; k < kPairGrad; k++) acc9[k] += wp[k];
                 }
@@ -443,13 +511,8 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
             dcol[1] = acc9[7];
             dcol[2] = acc9[8];
         }
-        float sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c6[6];
         float qn = 1.f;   // RAW: norm of the raw quaternion
-        if (a.in.cov3D_precomp) {
-            for (int k = 0; k < 6; k++) c6[k] = a.in.cov3D_precomp[6 * i + k];
-        } else {
-            for (int k = 0; k < 3; k++) sc[k] = a.in.scales[3 * i + k];
-            for (int k = 0; k < 4; k++) q[k] = a.in.rotations[4 * i + k];
+        if (!a.in.cov3D_precomp) {
             if (RAW) {
                 const float rq[4] = {q[0], q[1], q[2], q[3]};
                 for (int k = 0; k < 3; k++) sc[k] = scale_act(sc[k]);
@@ -468,17 +531,13 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         project_backward(cam, mx, my, mz, g2x, g2y, dmean);
         if (has_sh) {
             float mult = 0.f;
-            if (a.lambda_sh != 0.f) {
-                const uint32_t V = a.header->visible;
-                mult = a.lambda_sh / (float)((int)V * 15 * 3);
-            }
-            const int deg = a.in.degrees[i];
+            if (a.lambda_sh != 0.f) mult = a.lambda_sh / (float)((int)n_visible * 15 * 3);
             K = (deg + 1) * (deg + 1);
             if (cached) {
                 float d9[9];
 #pragma unroll
                 for (int k = 0; k < 9; k++)   // (a Gaussian binned into no tile got no colour and left nothing: its dcol is 0)
-                    d9[k] = (deg > 0 && ntile > 0u) ? a.sh_ddir[9 * (size_t)i + k] : 0.f;
+                    d9[k] = (deg > 0 && ntile > 0u) ? d9in[k] : 0.f;
                 sh_backward<true>(deg, row, row, d9, mx, my, mz, cam.campos, r.width_clamp >> 16, dcol, 0.f, dmean);
             } else {
                 sh_backward<false>(deg, row, row, nullptr, mx, my, mz, cam.campos, r.width_clamp >> 16, dcol, mult, dmean);
@@ -505,19 +564,19 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     __syncthreads();
     if (RAW) {
         const int rl = 3 * (M - 1);
+        R3_GLOBAL float* dc = global_ptr(a.out.dL_dsh) + 3L * wave_first;
+        R3_GLOBAL float* rest = global_ptr(a.dL_dsh_rest) + (long)rl * wave_first;
         if ((nrows & 3) == 0) {
-            unstage_split_span<ROWS48, true>(a.out.dL_dsh + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
-            if (M > 1)
-                unstage_split_span<ROWS48, true>(a.dL_dsh_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane, wave_vis);
+            unstage_split_span<ROWS48, true>(dc, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
+            if (M > 1) unstage_split_span<ROWS48, true>(rest, rl * nrows, rl, 3, M, lds, lane, wave_vis);
         } else {
-            unstage_split_span<ROWS48, false>(a.out.dL_dsh + 3L * wave_first, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
-            if (M > 1)
-                unstage_split_span<ROWS48, false>(a.dL_dsh_rest + (long)rl * wave_first, rl * nrows, rl, 3, M, lds, lane, wave_vis);
+            unstage_split_span<ROWS48, false>(dc, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
+            if (M > 1) unstage_split_span<ROWS48, false>(rest, rl * nrows, rl, 3, M, lds, lane, wave_vis);
         }
     } else if (has_sh) {
-        float* dst = a.out.dL_dsh + span_first;
+        R3_GLOBAL float* dst = global_ptr(a.out.dL_dsh) + span_first;
         if (((span_first | span_len) & 3) == 0) {   // dwordx4 stores of the gradient rows (or of zeros)
-            float4* dst4 = reinterpret_cast<float4*>(dst);
+            auto* dst4 = reinterpret_cast<R3_GLOBAL float4*>(dst);
             const int n4 = span_len >> 2;
             if (wave_vis) {
                 for (int e4 = lane; e4 < n4; e4 += 64) {
@@ -540,33 +599,33 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         }
     }
     if (valid) {
-        float* o;
-        o = a.out.dL_dmean2D + 3 * (size_t)i;
+        R3_GLOBAL float* o;
+        o = global_ptr(a.out.dL_dmean2D) + 3 * (size_t)i;
         o[0] = g2x;
         o[1] = g2y;
         o[2] = 0.f;
-        a.out.dL_dopacity[i] = dop;
-        o = a.out.dL_dcolor + 3 * (size_t)i;
+        global_ptr(a.out.dL_dopacity)[i] = dop;
+        o = global_ptr(a.out.dL_dcolor) + 3 * (size_t)i;
         o[0] = dcol[0];
         o[1] = dcol[1];
         o[2] = dcol[2];
-        o = a.out.dL_dmean3D + 3 * (size_t)i;
+        o = global_ptr(a.out.dL_dmean3D) + 3 * (size_t)i;
         o[0] = dmean[0];
         o[1] = dmean[1];
         o[2] = dmean[2];
-        o = a.out.dL_dcov3D + 6 * (size_t)i;
+        o = global_ptr(a.out.dL_dcov3D) + 6 * (size_t)i;
         for (int k = 0; k < 6; k++) o[k] = dcov6[k];
-        o = a.out.dL_dscale + 3 * (size_t)i;
+        o = global_ptr(a.out.dL_dscale) + 3 * (size_t)i;
         o[0] = dscale[0];
         o[1] = dscale[1];
         o[2] = dscale[2];
-        o = a.out.dL_drot + 4 * (size_t)i;
+        o = global_ptr(a.out.dL_drot) + 4 * (size_t)i;
         o[0] = dq[0];
         o[1] = dq[1];
         o[2] = dq[2];
         o[3] = dq[3];
         if (a.out.dL_dconic) {
-            o = a.out.dL_dconic + 4 * (size_t)i;
+            o = global_ptr(a.out.dL_dconic) + 4 * (size_t)i;
             o[0] = gcon[0];
             o[1] = gcon[1];
             o[2] = 0.f;
