@@ -455,24 +455,14 @@ __global__ __launch_bounds__(64) void blend_fwd_kernel(const BlendFwdArgs* __res
     R3_TLF_END(range.y - range.x)
 }
 
-template <int PPL>
-static void launch_fwd_ppl(const FwdPlan& p, const BlendFwdArgs* a, hipStream_t s)
-{
-    const uint32_t nblocks = (uint32_t)(p.gx * p.gy * (4 / PPL));   // == a->nblocks
-    if (p.counters)
-        hipLaunchKernelGGL((blend_fwd_kernel<PPL, true>), dim3(nblocks), dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL((blend_fwd_kernel<PPL, false>), dim3(nblocks), dim3(64), 0, s, a);
-}
-
+// One pixel per lane, four workgroups per tile: 2 / 4 pixels per lane measured 0.188 / 0.225 against 0.179 ms.
 void issue_blend_forward(const FwdPlan& p, const BlendFwdArgs* a, hipStream_t s)
 {
-    if (p.fwd_ppl == 4)
-        launch_fwd_ppl<4>(p, a, s);
-    else if (p.fwd_ppl == 2)
-        launch_fwd_ppl<2>(p, a, s);
+    const uint32_t nblocks = (uint32_t)(p.gx * p.gy * 4);   // == a->nblocks
+    if (p.counters)
+        hipLaunchKernelGGL((blend_fwd_kernel<1, true>), dim3(nblocks), dim3(64), 0, s, a);
     else
-        launch_fwd_ppl<1>(p, a, s);
+        hipLaunchKernelGGL((blend_fwd_kernel<1, false>), dim3(nblocks), dim3(64), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -484,9 +474,6 @@ constexpr int kGradStride = 9;   // the 9 sums of a list entry (odd stride: the 
 // 6 waves per SIMD (80 VGPRs, three spilled values outside the entry loop).  With round 2's 96-register body 5 and 6
 // measured the same; since the accumulated-colour recurrence and the offset products took 10 registers out of the
 // loop, 6 is the faster by 1 % (0.3602 / 0.3603 vs 0.3644 / 0.3627 ms, two runs each, same box).
-#ifndef R3_BWD_OCC
-#define R3_BWD_OCC 6
-#endif
 // One workgroup = one UNIT: a tile, or -- for a tile whose list the pass splits (common.h) -- entries [lo, hi) of
 // its list.  A segment that ends in front of a pixel's last contributor starts that pixel from the forward's checkpoint at
 // `hi`: T there, and the colour that lies behind it = (final colour - colour in front of hi) / T, projected on the pixel's
@@ -497,7 +484,7 @@ constexpr int kGradStride = 9;   // the 9 sums of a list entry (odd stride: the 
 // reads its own arguments from the kernarg segment; otherwise unit_order_kernel did and the arguments come from the block
 // (a graph replay refreshes the by-value arguments of its first node only).
 template <int PPL, bool REUSE, bool FIRST>
-__global__ __launch_bounds__(64, R3_BWD_OCC) void blend_bwd_kernel(BwdPassArgs* dst, BwdPassArgs v)
+__global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdPassArgs v)
 {
     __shared__ LdsRec s_rec[kChunk];
     if (FIRST && blockIdx.x == 0) install_block_from_kernarg(dst, (int)threadIdx.x, 64);

@@ -77,70 +77,53 @@ thread_local std::string g_last_error;
 thread_local int g_last_forward_pairs = 0;   // r3dgs_forward_pairs()
 thread_local int g_next_forward_trains = 1;  // r3dgs_forward_hint(): holds for this thread's forwards until set again
 
+// A switch of the library: on unless its environment variable says 0 (read at the first use), and settable through the C
+// ABI afterwards.
+struct Toggle {
+    const char* env;
+    std::atomic<int> v{-1};
+    int get()
+    {
+        int x = v.load();
+        if (x < 0) {
+            x = env_int(env, 1, 0, 1);
+            v.store(x);
+        }
+        return x;
+    }
+    int set(int on)   // on < 0: query only; returns the value before the call
+    {
+        const int before = get();
+        if (on >= 0) v.store(on ? 1 : 0);
+        return before;
+    }
+};
+
 // Opacity-aware tile rects (gauss_math.h tighten_rect) are the default; R3DGS_TIGHT_RECT=0 / r3dgs_set_tight_rects(0)
 // bins into the reference's 3-sigma squares (identical lists to the reference's: the bit-exact binning tests).
-std::atomic<int> g_tight_rects{-1};
-int tight_rects()
-{
-    int v = g_tight_rects.load();
-    if (v < 0) {
-        v = env_int("R3DGS_TIGHT_RECT", 1, 0, 1);
-        g_tight_rects.store(v);
-    }
-    return v;
-}
+Toggle g_tight_rects{"R3DGS_TIGHT_RECT"};
+int tight_rects() { return g_tight_rects.get(); }
 
 // The backward blend starts its tiles heaviest first (blend.hip unit_order_kernel); R3DGS_TILE_ORDER=0 /
 // r3dgs_set_tile_order(0): row-major bands, one per XCD, as the forward (A/B runs, the bit-identity test).
-std::atomic<int> g_tile_order{-1};
-int heaviest_tiles_first()
-{
-    int v = g_tile_order.load();
-    if (v < 0) {
-        v = env_int("R3DGS_TILE_ORDER", 1, 0, 1);
-        g_tile_order.store(v);
-    }
-    return v;
-}
+Toggle g_tile_order{"R3DGS_TILE_ORDER"};
+int heaviest_tiles_first() { return g_tile_order.get(); }
 
-// Without a sparsity term the backward takes the SH direction derivatives the forward left (GeomState::sh_ddir) instead of
 // Long tile lists are walked by several workgroups of the backward blend, from checkpoints the forward blend leaves
 // (common.h, blend.hip); R3DGS_BWD_SEG=0 / r3dgs_set_bwd_segments(0): one workgroup per tile whatever its list
 // (A/B runs, the bit-identity tests of the launch order).
-std::atomic<int> g_bwd_segments{-1};
-int bwd_segments()
-{
-    int v = g_bwd_segments.load();
-    if (v < 0) {
-        v = env_int("R3DGS_BWD_SEG", 1, 0, 1);
-        g_bwd_segments.store(v);
-    }
-    return v;
-}
+Toggle g_bwd_segments{"R3DGS_BWD_SEG"};
+int bwd_segments() { return g_bwd_segments.get(); }
+
+// Without a sparsity term the backward takes the SH direction derivatives the forward left (GeomState::sh_ddir) instead of
 // reading every SH row again; R3DGS_SH_CACHE=0 / r3dgs_set_sh_cache(0): it reads the rows (A/B runs, the bit-identity test).
-std::atomic<int> g_sh_cache{-1};
-int sh_derivative_cache()
-{
-    int v = g_sh_cache.load();
-    if (v < 0) {
-        v = env_int("R3DGS_SH_CACHE", 1, 0, 1);
-        g_sh_cache.store(v);
-    }
-    return v;
-}
+Toggle g_sh_cache{"R3DGS_SH_CACHE"};
+int sh_derivative_cache() { return g_sh_cache.get(); }
 
 // The per-Gaussian backward evaluates the covariance chain (backward.cu:228-306, 311-374) in double and rounds once
 // (gauss_math.h); R3DGS_F64_CHAIN=0 / r3dgs_set_f64_chain(0): the reference's fp32 arithmetic (A/B runs).
-std::atomic<int> g_f64_chain{-1};
-int f64_chain()
-{
-    int v = g_f64_chain.load();
-    if (v < 0) {
-        v = env_int("R3DGS_F64_CHAIN", 1, 0, 1);
-        g_f64_chain.store(v);
-    }
-    return v;
-}
+Toggle g_f64_chain{"R3DGS_F64_CHAIN"};
+int f64_chain() { return g_f64_chain.get(); }
 
 bool env_is(const char* name, const char* value)
 {
@@ -461,30 +444,6 @@ void evict_graphs_locked()
     }
 }
 
-// Second stream of a forward whose colour stream runs BESIDE the depth sort and the binning instead of inside the sort's
-// launches (FwdPlan::color_side, large scenes): forked after the geometry kernel, joined before the blend.  One per device;
-// the fork / join events carry no timing and may be re-recorded while an earlier wait is pending (a wait refers to the
-// record that preceded it).  Inside a stream capture the two event waits make the side stream part of the captured graph.
-struct SideStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-};
-std::mutex g_side_mu;
-std::unordered_map<int, SideStream> g_side;
-SideStream& side_stream()
-{
-    int dev = 0;
-    R3_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_side_mu);
-    SideStream& ss = g_side[dev];
-    if (!ss.stream) {
-        R3_HIP(hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking));
-        R3_HIP(hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming));
-        R3_HIP(hipEventCreateWithFlags(&ss.join, hipEventDisableTiming));
-    }
-    return ss;
-}
-
 bool graphs_enabled()
 {
     static const bool on = !env_is("R3DGS_GRAPH", "0");
@@ -511,26 +470,13 @@ void issue_forward(const FwdPlan& p, FwdPassArgs* d, const FwdPassArgs& args, hi
         if (!args.depth.fuse_header) issue_header_reduce(&d->header, s);
     }
     if (phases & 2) {
-        SideStream* side = nullptr;
-        // (one fork / join event pair per device: two host threads issuing forwards at once would interleave record and
-        // wait of each other's passes, so the issue of a pass that uses the side stream is serialised -- opt-in A/B path)
-        static std::mutex side_issue_mu;
-        std::unique_lock<std::mutex> side_lk(side_issue_mu, std::defer_lock);
-        if (p.color_side) {   // the colour stream on a stream of its own, beside the sort and the binning
-            side_lk.lock();
-            side = &side_stream();
-            R3_HIP(hipEventRecord(side->fork, s));
-            R3_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-            issue_preprocess_color(p, &d->pre, side->stream);
-            R3_HIP(hipEventRecord(side->join, side->stream));
-        }
         h.begin(kDepthSort, s);
         if (p.generic_depth_sort)
             run_generic_depth_sort(p.P, *g_host, s);
         else
             issue_depth_sort_and_color(p, d, s);   // the SH -> RGB stream rides in spare workgroups of these kernels
         h.end(kDepthSort, "depth sort + scan", s);
-        if (p.generic_depth_sort && !p.color_in_geom && !p.color_side) {
+        if (p.generic_depth_sort) {   // no sort kernel of ours to carry the colour chunks
             h.begin(kColor, s);
             issue_preprocess_color(p, &d->pre, s);
             h.end(kColor, "SH colours", s);
@@ -538,7 +484,6 @@ void issue_forward(const FwdPlan& p, FwdPassArgs* d, const FwdPassArgs& args, hi
         h.begin(kBinning, s);
         issue_tile_binning(p, d, s);
         h.end(kBinning, "tile binning", s);
-        if (side) R3_HIP(hipStreamWaitEvent(s, side->join, 0));
         h.begin(kBlendFwd, s);
         issue_blend_forward(p, &d->blend, s);
         h.end(kBlendFwd, "blend forward", s);
@@ -665,7 +610,6 @@ void validate_forward(const FwdCall& c)
 
 FwdPlan make_fwd_plan(const FwdCall& c, uint32_t reserve)
 {
-    static const int ppl0 = env_int("R3DGS_FWD_PPL", 1, 1, 4);   // 1 / 2 / 4 measured: 0.179 / 0.188 / 0.225 ms
     // workgroups of the colour stream per launch that carries it: P / 512 between 512 and 4096 (measured: 1024 vs 512 at
     // 500 k: stage 0.086 vs 0.088 ms; 4096 vs 512 at 2 M: 0.259 vs 0.299 ms); R3DGS_COLOR_GRID overrides
     static const int color_grid_env = env_int("R3DGS_COLOR_GRID", -1, 0, 1 << 20);
@@ -683,26 +627,17 @@ FwdPlan make_fwd_plan(const FwdCall& c, uint32_t reserve)
     p.nb = depth_bucket_count((size_t)c.P);
     p.ragged = (c.coeffsNum != nullptr && !c.colors_precomp) ? 1 : 0;
     p.counters = c.calculate_mean_transmittance ? 1 : 0;
-    p.fwd_ppl = ppl0 == 3 ? 2 : ppl0;
     p.color_grid = color_grid_env >= 0 ? color_grid_env : std::min(4096, std::max(512, c.P / 512));
-    static const int fuse = env_int("R3DGS_COLOR_FUSE", 1, 0, 1);
     // share of the colour chunks carried by the histogram / scatter / bucket-sort launches: 25 / 45 / 30 % up to 1 M Gaussians
     // (round 6, profiles/r06_sweep_colour_split.txt: depth sort + colour 0.0896 against 0.0929 ms with round 5's 20 / 35 / 45 at
     // 500 k, both alternating rounds), 25 / 25 / 50 % above (2 M: stage 0.257 vs 0.266 ms, 6 M: 0.762 vs 0.778)
     static const int split0_env = env_int("R3DGS_COLOR_SPLIT0", -1, 0, 100), split1_env = env_int("R3DGS_COLOR_SPLIT1", -1, 0, 100);
     const bool big = c.P > (1 << 20);
     const int split0 = split0_env >= 0 ? split0_env : 25, split1 = split1_env >= 0 ? split1_env : big ? 25 : 45;
-    p.color_fuse = fuse;
     p.color_split[0] = split0;
     p.color_split[1] = split0 + split1 > 100 ? 100 - split0 : split1;
     p.color_split[2] = 100 - p.color_split[0] - p.color_split[1];
     p.generic_depth_sort = (generic_env || c.P >= (1 << 24)) ? 1 : 0;   // the bucket histogram packs the count in 24 bits
-    static const int in_geom_env = env_int("R3DGS_COLOR_IN_GEOM", -1, -1, 1);
-    p.color_in_geom = in_geom_env > 0 ? 1 : 0;
-    if (p.color_in_geom) p.color_fuse = 0;
-    static const int side_env = env_int("R3DGS_COLOR_STREAM", -1, -1, 1);
-    p.color_side = (side_env > 0 && !p.color_in_geom) ? 1 : 0;
-    if (p.color_side) p.color_fuse = 0;
     p.tight = tight_rects();
     p.raw_params = c.raw ? 1 : 0;
     return p;
@@ -858,7 +793,7 @@ void fill_fwd_args(FwdPassArgs& a, const FwdPlan& p, const FwdCall& c, const Geo
     f.W = c.width;
     f.H = c.height;
     f.gx = p.gx;
-    f.nblocks = (uint32_t)(p.gx * p.gy * (4 / p.fwd_ppl));
+    f.nblocks = (uint32_t)(p.gx * p.gy * 4);
     f.bg = c.background;
     f.out_color = c.out_color;
     f.final_T = img.final_T;
@@ -873,10 +808,8 @@ void fill_fwd_args(FwdPassArgs& a, const FwdPlan& p, const FwdCall& c, const Geo
 
 uint32_t fwd_flags(const FwdPlan& p, const FwdCall& c)
 {
-    return (uint32_t)p.ragged | ((uint32_t)p.counters << 1) | ((uint32_t)p.fwd_ppl << 2) |
-           ((uint32_t)p.layout.wide << 8) | ((uint32_t)(c.colors_precomp != nullptr) << 6) | ((uint32_t)p.color_fuse << 7) |
-           ((uint32_t)p.tight << 10) | ((uint32_t)p.color_in_geom << 11) | ((uint32_t)p.color_side << 12) |
-           ((uint32_t)p.raw_params << 13);
+    return (uint32_t)p.ragged | ((uint32_t)p.counters << 1) | ((uint32_t)(c.colors_precomp != nullptr) << 2) |
+           ((uint32_t)p.tight << 3) | ((uint32_t)p.raw_params << 4) | ((uint32_t)p.layout.wide << 5);   // wide: 0 / 1 / 2
 }
 
 int current_device()
@@ -1016,27 +949,17 @@ long long forward_reserved(char* geom_buffer, char* binning_buffer, char* image_
     return (long long)ticket;
 }
 
-template <class F>
-int guarded(F&& f)
+// Every entry point's body: clears r3dgs_last_error(), and turns an exception into the message and the entry point's
+// failure value (-1 for the int / long long ones, 0 for the *_bytes queries).
+template <class F, class R = decltype(std::declval<F>()())>
+R guarded(F&& f, R failure = R(-1))
 {
     try {
         g_last_error.clear();
         return f();
     } catch (const std::exception& e) {
         g_last_error = e.what();
-        return -1;
-    }
-}
-
-template <class F>
-long long guarded_ll(F&& f)
-{
-    try {
-        g_last_error.clear();
-        return f();
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return -1;
+        return failure;
     }
 }
 
@@ -1098,35 +1021,22 @@ const char* r3dgs_last_error(void) { return g_last_error.c_str(); }
 // without one it returns 0 and sets r3dgs_last_error().
 size_t r3dgs_geometry_bytes(int P)
 {
-    try {
-        g_last_error.clear();
-        return r3::required_bytes<r3::GeomState>((size_t)P, cached_depth_temp((size_t)(P > 0 ? P : 1)));
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return 0;
-    }
+    return guarded([&]() { return r3::required_bytes<r3::GeomState>((size_t)P, cached_depth_temp((size_t)(P > 0 ? P : 1))); },
+                   (size_t)0);
 }
 size_t r3dgs_geometry_bytes_lean(int P)
 {
-    try {
-        g_last_error.clear();
-        return geometry_blob_bytes((size_t)P, cached_depth_temp((size_t)(P > 0 ? P : 1)), true);
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return 0;
-    }
+    return guarded([&]() { return geometry_blob_bytes((size_t)P, cached_depth_temp((size_t)(P > 0 ? P : 1)), true); }, (size_t)0);
 }
 size_t r3dgs_binning_bytes(int P, int width, int height, int reserve)
 {
-    try {
-        g_last_error.clear();
-        const int gx = (width + r3::kTile - 1) / r3::kTile, gy = (height + r3::kTile - 1) / r3::kTile;
-        const r3::PairLayout l = r3::pair_layout(P, (size_t)gx * gy);
-        return r3::required_bytes<r3::BinState>((size_t)(reserve > 0 ? reserve : 1), l.wide, r3::TileGrid{(uint32_t)gx, (uint32_t)gy});
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return 0;
-    }
+    return guarded(
+        [&]() {
+            const int gx = (width + r3::kTile - 1) / r3::kTile, gy = (height + r3::kTile - 1) / r3::kTile;
+            const r3::PairLayout l = r3::pair_layout(P, (size_t)gx * gy);
+            return r3::required_bytes<r3::BinState>((size_t)(reserve > 0 ? reserve : 1), l.wide, r3::TileGrid{(uint32_t)gx, (uint32_t)gy});
+        },
+        (size_t)0);
 }
 size_t r3dgs_image_bytes(int width, int height)
 {
@@ -1231,7 +1141,7 @@ long long r3dgs_forward_reserved(char* geom_buffer, char* binning_buffer, char* 
                                  int* radii, int calculate_mean_transmittance, int debug, void* stream)
 {
     (void)prefiltered;
-    return guarded_ll([&]() {
+    return guarded([&]() {
         R3_FWD_CALL(nullptr, nullptr, nullptr, M);
         return forward_reserved(geom_buffer, binning_buffer, image_buffer, reserve, c);
     });
@@ -1249,7 +1159,7 @@ long long r3dgs_inference_forward_reserved(char* geom_buffer, char* binning_buff
                                            int* radii, int calculate_mean_transmittance, int debug, void* stream)
 {
     (void)prefiltered;
-    return guarded_ll([&]() {
+    return guarded([&]() {
         check_ragged(colors_precomp, bandsNum, coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount);
         R3_FWD_CALL(coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount, 16);
         return forward_reserved(geom_buffer, binning_buffer, image_buffer, reserve, c);
@@ -1299,42 +1209,17 @@ int r3dgs_pass_pairs(long long ticket, int wait)
 
 int r3dgs_forward_pairs(void) { return g_last_forward_pairs; }
 
-int r3dgs_set_tight_rects(int on)   // on < 0: query only
-{
-    const int before = tight_rects();
-    if (on >= 0) g_tight_rects.store(on ? 1 : 0);
-    return before;
-}
+int r3dgs_set_tight_rects(int on) { return g_tight_rects.set(on); }   // on < 0: query only
 
 void r3dgs_forward_hint(int will_backward) { g_next_forward_trains = will_backward ? 1 : 0; }
 
-int r3dgs_set_sh_cache(int on)   // on < 0: query only
-{
-    const int before = sh_derivative_cache();
-    if (on >= 0) g_sh_cache.store(on ? 1 : 0);
-    return before;
-}
+int r3dgs_set_sh_cache(int on) { return g_sh_cache.set(on); }   // on < 0: query only
 
-int r3dgs_set_f64_chain(int on)   // on < 0: query only
-{
-    const int before = f64_chain();
-    if (on >= 0) g_f64_chain.store(on ? 1 : 0);
-    return before;
-}
+int r3dgs_set_f64_chain(int on) { return g_f64_chain.set(on); }   // on < 0: query only
 
-int r3dgs_set_bwd_segments(int on)   // on < 0: query only
-{
-    const int before = bwd_segments();
-    if (on >= 0) g_bwd_segments.store(on ? 1 : 0);
-    return before;
-}
+int r3dgs_set_bwd_segments(int on) { return g_bwd_segments.set(on); }   // on < 0: query only
 
-int r3dgs_set_tile_order(int on)   // on < 0: query only
-{
-    const int before = heaviest_tiles_first();
-    if (on >= 0) g_tile_order.store(on ? 1 : 0);
-    return before;
-}
+int r3dgs_set_tile_order(int on) { return g_tile_order.set(on); }   // on < 0: query only
 
 int r3dgs_export_rects(int P, char* geom_buffer, unsigned short* rects, void* stream)
 {
@@ -1486,7 +1371,6 @@ static int backward_any(int P, const int* D, int M, int R, const float* backgrou
         pb.tiles = geom.tiles;
         pb.acc = geom.acc;
         pb.wave_part = plan.has_pairs ? bin.wave_part : nullptr;
-        pb.pair_grad = plan.has_pairs ? bin.pair_grad : nullptr;
         pb.stamp0 = pr.stamp0;
         pb.stamp1 = pr.stamp1;
         pb.header = geom.header;
@@ -1595,7 +1479,7 @@ long long r3dgs_forward_params_reserved(char* geom_buffer, char* binning_buffer,
                                         int calculate_mean_transmittance, int debug, void* stream)
 {
     (void)prefiltered;
-    return guarded_ll([&]() {
+    return guarded([&]() {
         check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
         R3_PARAMS_CALL();
         return forward_reserved(geom_buffer, binning_buffer, image_buffer, reserve, c);

@@ -36,22 +36,14 @@ namespace r3 {
 constexpr size_t kAlign = 256;
 constexpr int kPairGrad = 9;  // floats per (tile, Gaussian) pair parked by the backward blend:
                               // dmean2D.xy, dconic.xyw, dopacity, dcolor.rgb
-#ifndef R3_ACC_STRIDE
-#define R3_ACC_STRIDE 12
-#endif
-#ifndef R3_PAIR_STRIDE
-#define R3_PAIR_STRIDE 12
-#endif
-// floats per piece of wave_part (the leading / trailing partial run sum of a 64-pair group): 9 packed (the round-2 layout, nine
-// 4-byte stores by one lane), or 12 with -DR3_WP_VEC (experiment: three 16-byte stores and loads per piece)
-#ifdef R3_WP_VEC
-constexpr int kPieceStride = 12;
-#else
+// floats per piece of wave_part (the leading / trailing partial run sum of a 64-pair group): 9 packed, nine 4-byte stores by
+// one lane
 constexpr int kPieceStride = 9;
-#endif
-constexpr int kAccStride = R3_ACC_STRIDE;    // floats per Gaussian in the reduced 2D-stage gradient row (9 used)
-constexpr int kPairStride = R3_PAIR_STRIDE;  // floats per row of the per-pair slab: 48-B rows, written / read as three float4
-                                // (36-B rows measured 2.4x write amplification: partial lines, nine dword accesses)
+constexpr int kAccStride = 12;   // floats per Gaussian in the reduced 2D-stage gradient row (9 sums + the pass's 2-word stamp)
+constexpr int kPairStride = 12;  // floats per row of the per-pair slab: 48-B rows, written / read as three float4
+                                 // (36-B rows measured 2.4x write amplification: partial lines, nine dword accesses)
+static_assert(kAccStride >= 12 && kAccStride % 4 == 0 && kPairStride >= 12 && kPairStride % 4 == 0,
+              "the kernels move three float4 per row");
 
 // Per-view counters.  Every preprocess workgroup stores one PrePartial (no atomics, nothing to pre-clear: the first
 // GPU profile showed 7.8k same-address atomics costing ~90 us, a sharded version still needed a fill of the header
@@ -103,10 +95,7 @@ static_assert(sizeof(PassInfo) == 32, "PassInfo = 32 B");
 constexpr int kMinDepthBuckets = 1024;
 constexpr int kMaxDepthBuckets = 16384;
 constexpr int kBucketCap = 4096;     // (key, id) pairs one workgroup sorts in LDS (32 KB)
-#ifndef R3_HIST_BATCH
-#define R3_HIST_BATCH 4096
-#endif
-constexpr int kHistBatch = R3_HIST_BATCH;   // Gaussians a histogram / scatter workgroup handles per round (16 per thread)
+constexpr int kHistBatch = 4096;   // Gaussians a histogram / scatter workgroup handles per round (16 per thread)
 // Gaussians per histogram / scatter workgroup: rounds of kHistBatch, as many as keep the row count near 256 (one
 // workgroup per CU: their nb-entry LDS tables leave room for no more at large nb).  Every such workgroup carries
 // nb-entry tables (its histogram row, its scan of the bucket totals), so with a fixed 4096 Gaussians per workgroup
@@ -705,7 +694,6 @@ struct PreBwdArgs {       // preprocess_bwd.hip
     const uint32_t* tiles;
     const float* acc;
     const float* wave_part;
-    const float* pair_grad;   // -DR3_ACC_IN_SLAB (experiment): the run sums stay in the slab, in the row of the run's last pair
     uint32_t stamp0, stamp1;  // as PairReduceArgs
     const GeomHeader* header;
     float lambda_sh;
@@ -744,11 +732,7 @@ struct FwdPlan {
     PairLayout layout;
     int nb;                // depth buckets
     int ragged, counters;  // ragged SH addressing; counter mode (calculate_mean_transmittance)
-    int color_in_geom;     // the geometry kernel's workgroups colour their own Gaussians (large scenes; preprocess.hip)
-    int color_side;        // the colour kernel runs on a second stream beside the depth sort and the binning (capi.hip)
-    int fwd_ppl;           // pixels per lane of the forward blend
     int color_grid;        // workgroups of the SH -> RGB stream (per launch that carries it)
-    int color_fuse;        // 1: the colour chunks ride in spare workgroups of the depth-sort kernels
     int color_split[3];    // percent of the colour chunks in the histogram / scatter / bucket-sort launches
     int generic_depth_sort;  // rocPRIM sort + scan instead of the bucketed sort (never inside a graph)
     int tight;             // opacity-aware tile rects (default) or the reference's 3-sigma squares

@@ -163,23 +163,16 @@ __device__ __forceinline__ int ragged_offset(int idx, const int* coeffs, const i
     return off + (idx - cumsum[2]) * coeffs[3];
 }
 
-template <bool RAGGED, int BLOCK, bool SPLIT = false>
-__device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg,
-                                           const float* shs_rest = nullptr);
-
 // ---- kernel 1: geometry ---------------------------------------------------------------------------
 // cull, projection, conic, radius, tile rect, depth key, per-view counters.  Reads 44 B per Gaussian.  Its
-// outputs are everything the depth sort / binning needs, so the SH -> RGB kernel below can run on a side
-// stream underneath the (launch-latency-bound) sort.
-// COLOR != 0 (large scenes, FwdPlan::color_in_geom): the workgroup goes on to colour its own 256 Gaussians (color_role
-// below; COLOR 2 = ragged SH) while their records are still in the L2 -- the separate colour stream otherwise re-opens every
-// 48-byte record for a 16-byte partial write, which HBM pays as a read-modify-write of the whole line.
-// COLOR >= 4 (r3dgs_forward_params): scales / rotations hold the model's RAW parameters and are activated after the load
-// (param_math.h); 4: no colour here, 5: colours its own Gaussians from the two SH tensors.
+// outputs are everything the depth sort / binning needs, so the SH -> RGB stream can ride in spare workgroups of
+// the (launch-latency-bound) sort's kernels.
+// COLOR is 0, or 4 (r3dgs_forward_params): scales / rotations hold the model's RAW parameters and are activated after the
+// load (param_math.h).  The two keep these numbers because the committed profiles and bench.py cite the kernels by name.
 template <int COLOR>
 __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs* dst, FwdPassArgs v)
 {
-    extern __shared__ __attribute__((aligned(16))) char geom_smem[];
+    static_assert(COLOR == 0 || COLOR == 4, "0: activated inputs, 4: raw parameters");
     // first kernel of the forward: it gets the pass block by value, installs it for the kernels behind it ...
     if (blockIdx.x == 0) install_block_from_kernarg(dst, (int)threadIdx.x, kPreBlock);
     const PreArgs a = v.pre;   // ... and reads its own arguments from the kernarg segment (scalar loads)
@@ -208,7 +201,7 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
             q[1] = qv.y;
             q[2] = qv.z;
             q[3] = qv.w;
-            if (COLOR >= 4) {
+            if (COLOR == 4) {
                 const float rq[4] = {q[0], q[1], q[2], q[3]};
                 for (int k = 0; k < 3; k++) sc[k] = scale_act(sc[k]);
                 quat_act(rq, q);
@@ -275,16 +268,6 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
         }
         a.partials[blockIdx.x] = pp;
     }
-    if (COLOR == 5) {
-        __syncthreads();
-        color_role<false, kPreBlock, true>(a, geom_smem, (int)blockIdx.x, (int)blockIdx.x + 1, 0, 1, v.shs_rest);
-    } else if (COLOR && COLOR < 4) {
-        __syncthreads();
-        if (COLOR == 2)
-            color_role<true, kPreBlock>(a, geom_smem, (int)blockIdx.x, (int)blockIdx.x + 1, 0, 1);
-        else
-            color_role<false, kPreBlock>(a, geom_smem, (int)blockIdx.x, (int)blockIdx.x + 1, 0, 1);
-    }
 }
 
 // ---- kernel 2: colour -------------------------------------------------------------------------------
@@ -296,13 +279,12 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
 // workgroups no room -- the depth scatter kernel took 46 us instead of 14 us beside it.
 constexpr size_t kColorLds = sizeof(float) * (kPreBlock / 64) * kWaveShFloats;
 
-// chunks [first + wg, last) in steps of n_wg, BLOCK Gaussians each (BLOCK = workgroup size); smem: BLOCK / 64 wave windows.
-// BLOCK = 64 (standalone kernel only): single-wave workgroups -- 12 per CU instead of 3 of four waves: no barrier couples
-// the waves' load / evaluate phases, so they drift apart and one wave's loads fly while another evaluates.
+// chunks [first + wg, last) in steps of n_wg, BLOCK Gaussians each (BLOCK = workgroup size, always kPreBlock); smem: BLOCK / 64
+// wave windows.
 // SPLIT: the rows come from two tensors, in.shs = features_dc and shs_rest (stage_split_rows); the LDS layout is the same.
-template <bool RAGGED, int BLOCK, bool SPLIT>
+template <bool RAGGED, int BLOCK, bool SPLIT = false>
 __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg,
-                                           const float* shs_rest)
+                                           const float* shs_rest = nullptr)
 {
     float(*s_sh)[kWaveShFloats] = reinterpret_cast<float(*)[kWaveShFloats]>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -404,7 +386,7 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
   }
 }
 
-// standalone colour kernel (generic depth sort path, R3DGS_COLOR_FUSE=0): small persistent grid
+// standalone colour kernel (generic depth sort path only): small persistent grid
 template <bool RAGGED, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void preprocess_color_kernel(const PreArgs* __restrict__ ap)
 {
@@ -474,40 +456,23 @@ __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const Dep
 void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs& v, hipStream_t s)
 {
     const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
-    if (p.raw_params && p.color_in_geom)
-        hipLaunchKernelGGL(preprocess_geom_kernel<5>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
-    else if (p.raw_params)
+    if (p.raw_params)
         hipLaunchKernelGGL(preprocess_geom_kernel<4>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
-    else if (p.color_in_geom && p.ragged)
-        hipLaunchKernelGGL(preprocess_geom_kernel<2>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
-    else if (p.color_in_geom)
-        hipLaunchKernelGGL(preprocess_geom_kernel<1>, dim3(blocks), dim3(kPreBlock), kColorLds, s, dst, v);
     else
         hipLaunchKernelGGL(preprocess_geom_kernel<0>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
 }
 
 void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s)
 {
-    static const int block = env_int("R3DGS_COLOR_BLOCK", 256, 64, 256) == 64 ? 64 : 256;   // workgroup size of THIS kernel
-    const int blocks = (p.P + block - 1) / block;
-    const int want = p.color_grid > 0 ? p.color_grid * (kPreBlock / block) : blocks;
-    const int grid = blocks > want ? want : blocks;
-    const size_t lds = kColorLds / (kPreBlock / block);
+    const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
+    const int grid = p.color_grid > 0 && blocks > p.color_grid ? p.color_grid : blocks;
     if (p.raw_params) {
         const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
-        if (block == 64)
-            hipLaunchKernelGGL((preprocess_color_params_kernel<64>), dim3(grid), dim3(64), lds, s, pa);
-        else
-            hipLaunchKernelGGL((preprocess_color_params_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), lds, s, pa);
-    } else if (block == 64) {
-        if (p.ragged)
-            hipLaunchKernelGGL((preprocess_color_kernel<true, 64>), dim3(grid), dim3(64), lds, s, a);
-        else
-            hipLaunchKernelGGL((preprocess_color_kernel<false, 64>), dim3(grid), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((preprocess_color_params_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, pa);
     } else if (p.ragged) {
-        hipLaunchKernelGGL((preprocess_color_kernel<true, kPreBlock>), dim3(grid), dim3(kPreBlock), lds, s, a);
+        hipLaunchKernelGGL((preprocess_color_kernel<true, kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, a);
     } else {
-        hipLaunchKernelGGL((preprocess_color_kernel<false, kPreBlock>), dim3(grid), dim3(kPreBlock), lds, s, a);
+        hipLaunchKernelGGL((preprocess_color_kernel<false, kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, a);
     }
 }
 
@@ -566,15 +531,9 @@ void prepare_depth_bucket_sort(int nb)
     opt_in_lds_params<1>(sc);
     opt_in_lds_params<2>(bs);
     if (kColorLds > 48 * 1024) {
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_geom_kernel<1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_geom_kernel<2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<false, kPreBlock>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<true, kPreBlock>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_geom_kernel<5>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_params_kernel<kPreBlock>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
@@ -584,19 +543,14 @@ void prepare_depth_bucket_sort(int nb)
 
 // Bucketed depth sort with the SH -> RGB stream riding in spare workgroups of three of its four kernels.  The colour
 // chunks are split p.color_split[0..2] percent over the histogram / scatter / bucket-sort launches (each share about
-// as long as the sort role it hides behind); with fusion off (p.color_fuse == 0) the colour kernel runs on its own
-// after the sort.
+// as long as the sort role it hides behind).
 void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStream_t s)
 {
     const int rows = (int)depth_hist_rows((size_t)p.P), nb = p.nb;
     const int chunks = (p.P + kPreBlock - 1) / kPreBlock;
     int c[4] = {0, 0, 0, chunks};
-    if (p.color_fuse) {
-        c[1] = (int)((long long)chunks * p.color_split[0] / 100);
-        c[2] = c[1] + (int)((long long)chunks * p.color_split[1] / 100);
-    } else {
-        c[1] = c[2] = c[3] = 0;
-    }
+    c[1] = (int)((long long)chunks * p.color_split[0] / 100);
+    c[2] = c[1] + (int)((long long)chunks * p.color_split[1] / 100);
     const int cw = p.color_grid > 0 ? p.color_grid : 512;
     auto n_color = [&](int k) { const int n = c[k + 1] - c[k]; return n < cw ? n : cw; };
     const size_t lds0 = n_color(0) ? max_sz(depth_hist_lds(nb), kColorLds) : depth_hist_lds(nb);
@@ -618,7 +572,6 @@ void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStre
         launch_sort_color<1, false>(pa, rows, n_color(1), c[1], c[2], lds1, s);
         launch_sort_color<2, false>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], lds2, s);
     }
-    if (!p.color_fuse && !p.color_in_geom && !p.color_side) issue_preprocess_color(p, &pa->pre, s);
 }
 
 // rasterizer_impl.cu:62-74 checkFrustum: present[i] = (view * p).z > 0.2

@@ -20,11 +20,8 @@ namespace r3 {
 // Workgroup size of preprocess_bwd_kernel.  One wave per workgroup (round 4): every wave owns its LDS window and its 64
 // Gaussians anyway, and without a four-wave barrier the twelve waves of a CU drift apart, so loads, evaluation and the
 // dL_dsh row stores of different waves overlap: 0.194 -> 0.181 ms at 2 M Gaussians, 0.574 -> 0.539 at 6 M, unchanged at
-// 500 k (0.062-0.064 either way); 128: in between.  -DR3_PREBWD_BLOCK=256 for the round-3 shape.
-#ifndef R3_PREBWD_BLOCK
-#define R3_PREBWD_BLOCK 64
-#endif
-constexpr int kBwdBlock = R3_PREBWD_BLOCK;
+// 500 k (0.062-0.064 either way); 128: in between.
+constexpr int kBwdBlock = 64;
 constexpr int kBwdWaveShFloats = 64 * 48 + (64 * 48) / 32;
 
 // Where float e of the wave's span (64 rows x 3M floats, row after row) sits in LDS.  The lanes of a wave read the same
@@ -176,22 +173,12 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
         // same key <=> same run); asking the Gaussian's record for its pair range was a dependent gather per run
         const bool from_before = key == key0 && key_before == key;
         const bool into_next = lane == 63 && key_after == key;
-#ifdef R3_EXP_PR_NOSTORE   // timing experiment only (wrong results): what the scattered 48-byte run-sum stores cost --
-        // 17 of pair_reduce's 41 us at 500 k, 52 of 116 at 2 M, 152 of 282 at 6 M (profiles/r06_exp_pair_reduce_stores.txt)
-        if (v[0] != 12345.678f) return;
-#endif
         if (!from_before && !into_next) {
-#ifdef R3_ACC_IN_SLAB   // experiment: the run sum stays where the run ends (a write next to the rows this wave just read) and the
-                        // per-Gaussian kernel gathers it by pair_start instead of reading a row this store scattered
-            auto* dst = reinterpret_cast<R3_GLOBAL float4*>(global_ptr(const_cast<float*>(a.pair_grad)) + (size_t)e * kPairStride);
-#else
             auto* dst = reinterpret_cast<R3_GLOBAL float4*>(global_ptr(a.acc) + (size_t)gid * kAccStride);   // 48-B row: three 16-B stores
-#endif
-#ifndef R3_NO_ZERO_ROW_SKIP
             // A run without a contributing pair (all nine sums exactly zero: a third of the visible Gaussians of the metric scene,
             // more in a densified one) stores nothing: the reader takes a row that does not carry THIS pass's stamp for zeros.
             // 40-54 % of this kernel is these scattered stores (profiles/r06_exp_pair_reduce_stores.txt); pair_reduce 41 -> 39 us
-            // at 500 k, 127 -> 92 at 2 M, 282 -> 187 at 6 M.  -DR3_NO_ZERO_ROW_SKIP: every run stores its row (A/B builds).
+            // at 500 k, 127 -> 92 at 2 M, 282 -> 187 at 6 M.
             bool nz = false;
 #pragma unroll
             for (int k = 0; k < kPairGrad; k++) nz |= v[k] != 0.f;
@@ -200,28 +187,8 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
                 dst[1] = make_float4(v[4], v[5], v[6], v[7]);
                 dst[2] = make_float4(v[8], __uint_as_float(a.stamp0), __uint_as_float(a.stamp1), 0.f);
             }
-#else
-            dst[0] = make_float4(v[0], v[1], v[2], v[3]);
-            dst[1] = make_float4(v[4], v[5], v[6], v[7]);
-            dst[2] = make_float4(v[8], 0.f, 0.f, 0.f);
-            if (kAccStride >= 16) dst[3] = make_float4(0.f, 0.f, 0.f, 0.f);   // 64-byte rows: the whole burst is written
-#endif
         } else {
             R3_GLOBAL float* wp = global_ptr(a.wave_part) + (size_t)(e >> 6) * 2 * kPieceStride;
-#ifdef R3_WP_VEC
-            if (from_before) {  // continues a run of the previous group: this group's leading piece
-                auto* w4 = reinterpret_cast<R3_GLOBAL float4*>(wp);
-                w4[0] = make_float4(v[0], v[1], v[2], v[3]);
-                w4[1] = make_float4(v[4], v[5], v[6], v[7]);
-                w4[2] = make_float4(v[8], 0.f, 0.f, 0.f);
-            }
-            if (into_next) {  // continues into the next group: trailing piece
-                auto* w4 = reinterpret_cast<R3_GLOBAL float4*>(wp + kPieceStride);
-                w4[0] = make_float4(v[0], v[1], v[2], v[3]);
-                w4[1] = make_float4(v[4], v[5], v[6], v[7]);
-                w4[2] = make_float4(v[8], 0.f, 0.f, 0.f);
-            }
-#else
             if (from_before) {  // continues a run of the previous group: this group's leading piece
 #pragma unroll
                 for (int k = 0; k < kPairGrad; k++) wp[k] = v[k];
@@ -230,15 +197,10 @@ __device__ __forceinline__ void pair_reduce_group(const PairReduceArgs& a, uint3
 #pragma unroll
                 for (int k = 0; k < kPairGrad; k++) wp[kPieceStride + k] = v[k];
             }
-#endif
         }
     }
 }
 
-// R3_PR_WAVES (experiment): waves per SIMD the register allocation is held to (80 VGPRs = 6 by default)
-#ifdef R3_PR_WAVES
-__attribute__((amdgpu_waves_per_eu(R3_PR_WAVES, R3_PR_WAVES)))
-#endif
 __global__ __launch_bounds__(256) void pair_reduce_kernel(const PairReduceArgs* __restrict__ ap)
 {
     const PairReduceArgs a = *ap;
@@ -268,11 +230,7 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const PairReduceArgs* 
         const uint32_t e = e0 + 64u * g;
 #pragma unroll
         for (int k = 0; k < kPairGrad; k++) v[g][k] = 0.f;
-#ifdef R3_EXP_PR_NOLOAD    // timing experiment only (wrong results): what fetching the flagged slab rows costs
-        if (flag[g] && e == 0xFFFFFFF0u) {
-#else
         if (flag[g]) {  // ~1/3 of the pairs contribute; the rest of the slab is stale memory, never read
-#endif
             pair_flag[e] = 0;  // consumed: all flags are zero again when this kernel ends (next backward pass)
             const auto* src = reinterpret_cast<const R3_GLOBAL float4*>(pair_grad + (size_t)e * kPairStride);
             const float4 r0 = src[0], r1 = src[1];
@@ -328,13 +286,10 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     // run that spans several 64-pair groups (their address comes out of the record: the one dependent load), and the SH rows
     // of the row-reading path (a wave's staging loop, issued behind these loads).  The derivatives wait for the header word
     // that says whether the blob holds them (a blob without them ends in front of that array).
-    // Culled lanes: radii first and the rest for the visible lanes only -- two trips, no byte read for a culled Gaussian (the
-    // default); or -DR3_PREBWD_LOAD_CULLED=1: every lane i < P loads everything at once -- one trip, ~20 % more bytes read at
-    // the metric shape, 180 B instead of 4 per culled Gaussian.  Measured equal at 500 k and 2 M (profiles/prebwd_loads.txt);
-    // a view of a trained scene culls most of its Gaussians, so the form that reads nothing for them is the one built.
-#ifndef R3_PREBWD_LOAD_CULLED
-#define R3_PREBWD_LOAD_CULLED 0
-#endif
+    // Culled lanes: radii first and the rest for the visible lanes only -- two trips, no byte read for a culled Gaussian.
+    // Loading everything for every lane i < P at once (one trip, ~20 % more bytes read at the metric shape, 180 B instead of 4
+    // per culled Gaussian) measured equal at 500 k and 2 M (profiles/prebwd_loads.txt); a view of a trained scene culls most
+    // of its Gaussians, so the form that reads nothing for them is the one built.
     // (The arrays and the record stay uninitialised on the lanes that load nothing -- they are read only where `vis` holds:
     // merged with constants, the compiler copies each loaded register at the end of the phase, which waits for all of them.)
     int radius = 0, deg = 0;
@@ -345,12 +300,10 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     const auto load_lane = [&]() {
         r = global_ptr(a.rec)[i];
         ntile = global_ptr(a.tiles)[i];
-#ifndef R3_ACC_IN_SLAB
         const auto* arow = reinterpret_cast<const R3_GLOBAL float4*>(global_ptr(a.acc) + (size_t)i * kAccStride);
         a0 = arow[0];
         a1 = arow[1];
         a2 = arow[2];
-#endif
         for (int k = 0; k < 3; k++) m3[k] = global_ptr(a.in.means3D)[3 * i + k];
         if (!a.in.cov3D_precomp) {
             for (int k = 0; k < 3; k++) sc[k] = global_ptr(a.in.scales)[3 * i + k];
@@ -369,17 +322,9 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
             q[1] = q[2] = q[3] = 0.f;
         }
     };
-#if R3_PREBWD_LOAD_CULLED
-    if (valid) {
-        radius = global_ptr(a.radii)[i];
-        load_lane();
-    }
-    const bool vis = valid && radius > 0;
-#else
     if (valid) radius = global_ptr(a.radii)[i];
     const bool vis = valid && radius > 0;
     if (vis) load_lane();
-#endif
 
     const int nrows = max(0, min(64, P - wave_first));
     const int span_len = has_sh ? nrows * 3 * M : 0;
@@ -462,35 +407,13 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
             const uint32_t last = start + ntile - 1u;
             const uint32_t w0 = start >> 6, w1 = last >> 6;
             if (w0 == w1) {
-#ifdef R3_ACC_IN_SLAB
-                const auto* arow = reinterpret_cast<const R3_GLOBAL float4*>(global_ptr(a.pair_grad) + (size_t)last * kPairStride);
-                a0 = arow[0];
-                a1 = arow[1];
-                a2 = arow[2];
-#endif
-#ifndef R3_NO_ZERO_ROW_SKIP
                 if (__float_as_uint(a2.y) != a.stamp0 || __float_as_uint(a2.z) != a.stamp1)   // not written by this pass: zeros
                     a0 = a1 = a2 = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
                 acc9[0] = a0.x; acc9[1] = a0.y; acc9[2] = a0.z; acc9[3] = a0.w;
                 acc9[4] = a1.x; acc9[5] = a1.y; acc9[6] = a1.z; acc9[7] = a1.w;
                 acc9[8] = a2.x;
             } else {   // the one dependent load of the kernel: which groups hold the run's pieces comes out of the record
                 const R3_GLOBAL float* wave_part = global_ptr(a.wave_part);
-#ifdef R3_WP_VEC
-                const auto* w4 = reinterpret_cast<const R3_GLOBAL float4*>(wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride);
-                float4 p0 = w4[0], p1 = w4[1], p2 = w4[2];
-                acc9[0] = p0.x; acc9[1] = p0.y; acc9[2] = p0.z; acc9[3] = p0.w;
-                acc9[4] = p1.x; acc9[5] = p1.y; acc9[6] = p1.z; acc9[7] = p1.w;
-                acc9[8] = p2.x;
-                for (uint32_t w = w0 + 1; w <= w1; w++) {  // leading piece of every following group
-                    w4 = reinterpret_cast<const R3_GLOBAL float4*>(wave_part + (size_t)w * 2 * kPieceStride);
-                    p0 = w4[0]; p1 = w4[1]; p2 = w4[2];
-                    acc9[0] += p0.x; acc9[1] += p0.y; acc9[2] += p0.z; acc9[3] += p0.w;
-                    acc9[4] += p1.x; acc9[5] += p1.y; acc9[6] += p1.z; acc9[7] += p1.w;
-                    acc9[8] += p2.x;
-                }
-#else
                 const R3_GLOBAL float* wp = wave_part + (size_t)w0 * 2 * kPieceStride + kPieceStride;  // trailing piece of w0
 #pragma unroll
                 for (int k = 0; k < kPairGrad; k++) acc9[k] = wp[k];
@@ -499,7 +422,6 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
 #pragma unroll
                     for (int k = 0; k < kPairGrad; k++) acc9[k] += wp[k];
                 }
-#endif
             }
             g2x = acc9[0];
             g2y = acc9[1];

@@ -1,4 +1,4 @@
-"""Per-kernel means of the rocprofv3 --pmc passes written by tools/gpu_round.sh (PMC="...;...") into
+"""Per-kernel means of the rocprofv3 --pmc passes written by tools/refresh_profiles.sh into
 $R3DGS_OUT/pmc*/..._counter_collection.csv (default out/)  ->  one JSON {kernel: {counter: mean per launch}}.
 
     python tools/pmc_summary.py [out.json [dir-prefix]]   (default: $R3DGS_OUT/pmc_summary.json from $R3DGS_OUT/pmc*;
