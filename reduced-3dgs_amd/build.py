@@ -43,7 +43,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "optim.hip": EXACT,
     "capi.hip": [],
 }
-HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
+HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
+           os.path.join("..", "..", "include", "r3dgs_quantised.h"),
            os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),
            os.path.join("..", "..", "include", "r3dgs_optim.h")]
 

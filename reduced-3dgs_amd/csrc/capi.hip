@@ -21,6 +21,7 @@
 //   * `debug` and the per-stage timers issue the same chain with direct launches and synchronise / record events
 //     between stages (the reference's CHECK_CUDA).
 #include "../../include/r3dgs_rasterizer.h"
+#include "../../include/r3dgs_quantised.h"
 
 #include <time.h>
 
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "common.h"
+#include "quant_math.h"
 
 namespace r3 {
 int env_int(const char* env, int dflt, int lo, int hi)
@@ -593,10 +595,28 @@ struct FwdCall {
     // and shs_rest features_rest (common.h, behind FwdInputs)
     const float* shs_rest;
     int raw;
+    // quantised entry (r3dgs_quantised_forward*): the model is `quant` (common.h, behind shs_rest); the five model pointers
+    // above are NULL and the band tables are the ragged path's
+    int quantised = 0;
+    QuantInputs quant = {};
 };
 
 void validate_forward(const FwdCall& c)
 {
+    if (c.quantised) {
+        const QuantInputs& q = c.quant;
+        if (!q.xyz || !q.geom_ids || !q.sh_ids || !q.codebooks || !c.viewmatrix || !c.projmatrix || !c.cam_pos || !c.background ||
+            !c.out_color)
+            throw Error("a required pointer is NULL");
+        // what the kernels' loads assume: one 8-byte load of a Gaussian's geometry ids, dwordx4 loads of the codebooks
+        if (reinterpret_cast<uintptr_t>(q.geom_ids) % 8 || reinterpret_cast<uintptr_t>(q.codebooks) % 16 ||
+            reinterpret_cast<uintptr_t>(q.xyz) % (q.xyz_is_half ? 2 : 4))
+            throw Error("quantised model: geom_ids must be 8-byte aligned, codebooks 16-byte, xyz to its element");
+        if (c.width <= 0 || c.height <= 0) throw Error("image size must be positive");
+        if (c.calculate_mean_transmittance && (!c.out_touched_pixels || !c.out_transmittance))
+            throw Error("counter mode needs out_touched_pixels and out_transmittance");
+        return;
+    }
     if (!c.means3D || !c.opacities || !c.viewmatrix || !c.projmatrix || !c.cam_pos || !c.background || !c.out_color)
         throw Error("a required pointer is NULL");
     if (!c.colors_precomp && !c.shs) throw Error("provide SHs or precomputed colours");
@@ -640,6 +660,7 @@ FwdPlan make_fwd_plan(const FwdCall& c, uint32_t reserve)
     p.generic_depth_sort = (generic_env || c.P >= (1 << 24)) ? 1 : 0;   // the bucket histogram packs the count in 24 bits
     p.tight = tight_rects();
     p.raw_params = c.raw ? 1 : 0;
+    p.quant = c.quantised ? 1 : 0;
     return p;
 }
 
@@ -663,6 +684,7 @@ void fill_fwd_args(FwdPassArgs& a, const FwdPlan& p, const FwdCall& c, const Geo
     in.per_band_count = p.ragged ? c.perBand : nullptr;
     in.cumsum_count = p.ragged ? c.cumSum : nullptr;
     a.shs_rest = c.raw ? c.shs_rest : nullptr;
+    if (c.quantised) a.quant = c.quant;
     ViewParams& v = a.pre.view;
     v.view = c.viewmatrix;
     v.proj = c.projmatrix;
@@ -809,7 +831,8 @@ void fill_fwd_args(FwdPassArgs& a, const FwdPlan& p, const FwdCall& c, const Geo
 uint32_t fwd_flags(const FwdPlan& p, const FwdCall& c)
 {
     return (uint32_t)p.ragged | ((uint32_t)p.counters << 1) | ((uint32_t)(c.colors_precomp != nullptr) << 2) |
-           ((uint32_t)p.tight << 3) | ((uint32_t)p.raw_params << 4) | ((uint32_t)p.layout.wide << 5);   // wide: 0 / 1 / 2
+           ((uint32_t)p.tight << 3) | ((uint32_t)p.raw_params << 4) | ((uint32_t)p.layout.wide << 5) |   // wide: 0 / 1 / 2
+           ((uint32_t)p.quant << 7);
 }
 
 int current_device()
@@ -1521,6 +1544,88 @@ int r3dgs_activate_params(int P, const float* scaling_raw, const float* rotation
         r3::check_launch("activate_params", s, false);
         return 0;
     });
+}
+
+// ---- the quantised model (include/r3dgs_quantised.h) -------------------------------------------------------------------
+// The forward of r3dgs_inference_forward with the model read in place from codebook ids: the same plan, blobs, graph cache
+// and reservation advice; only the two per-Gaussian stages have instantiations of their own (preprocess.hip).
+#define R3_QUANT_CALL()                                                                                                 \
+    const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *opacities = nullptr, *scales = nullptr,  \
+                *rotations = nullptr, *cov3D_precomp = nullptr;                                                         \
+    check_ragged(nullptr, bandsNum, coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount);                            \
+    R3_FWD_CALL(coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount, 16);                                            \
+    c.quantised = 1;                                                                                                    \
+    c.quant.xyz = xyz;                                                                                                  \
+    c.quant.xyz_is_half = xyz_is_half ? 1 : 0;                                                                          \
+    c.quant.geom_ids = geom_ids;                                                                                        \
+    c.quant.sh_ids = sh_ids;                                                                                            \
+    c.quant.codebooks = codebooks
+
+int r3dgs_quantised_forward(r3dgs_alloc_fn geometryBuffer, void* geometry_user, r3dgs_alloc_fn binningBuffer, void* binning_user,
+                            r3dgs_alloc_fn imageBuffer, void* image_user, int P, const int* D, int bandsNum,
+                            const int* coeffsNum, const int* perBandPrimitiveCount, const int* cumSumPrimitiveCount,
+                            const float* background, int width, int height, const void* xyz, int xyz_is_half,
+                            const unsigned char* geom_ids, const unsigned char* sh_ids, const float* codebooks,
+                            float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                            float tan_fovx, float tan_fovy, int prefiltered, float* out_color, int* out_touched_pixels,
+                            float* out_transmittance, int* radii, int calculate_mean_transmittance, int debug, void* stream)
+{
+    (void)prefiltered;
+    return guarded([&]() {
+        R3_QUANT_CALL();
+        return forward_exact(geometryBuffer, geometry_user, binningBuffer, binning_user, imageBuffer, image_user, c);
+    });
+}
+
+long long r3dgs_quantised_forward_reserved(char* geom_buffer, char* binning_buffer, char* image_buffer, int reserve, int P,
+                                           const int* D, int bandsNum, const int* coeffsNum,
+                                           const int* perBandPrimitiveCount, const int* cumSumPrimitiveCount,
+                                           const float* background, int width, int height, const void* xyz, int xyz_is_half,
+                                           const unsigned char* geom_ids, const unsigned char* sh_ids, const float* codebooks,
+                                           float scale_modifier, const float* viewmatrix, const float* projmatrix,
+                                           const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                           float* out_color, int* out_touched_pixels, float* out_transmittance, int* radii,
+                                           int calculate_mean_transmittance, int debug, void* stream)
+{
+    (void)prefiltered;
+    return guarded([&]() {
+        R3_QUANT_CALL();
+        return forward_reserved(geom_buffer, binning_buffer, image_buffer, reserve, c);
+    });
+}
+
+int r3dgs_quantised_decode(int P, const int* coeffsNum, const int* perBandPrimitiveCount, const int* cumSumPrimitiveCount,
+                           const void* xyz, int xyz_is_half, const unsigned char* geom_ids, const unsigned char* sh_ids,
+                           const float* codebooks, float* xyz_out, float* features_dc, float* features_rest, float* opacity,
+                           float* scaling, float* rotation, int* degrees, void* stream)
+{
+    return guarded([&]() {
+        if (P <= 0) return 0;
+        if (!coeffsNum || !perBandPrimitiveCount || !cumSumPrimitiveCount || !xyz || !geom_ids || !sh_ids || !codebooks)
+            throw r3::Error("quantised_decode: a required pointer is NULL");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        r3::QuantInputs q = {xyz, geom_ids, sh_ids, codebooks, xyz_is_half ? 1 : 0};
+        r3::launch_quantised_decode(P, coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount, q, xyz_out, features_dc,
+                                    features_rest, opacity, scaling, rotation, degrees, s);
+        r3::check_launch("quantised_decode", s, false);
+        return 0;
+    });
+}
+
+size_t r3dgs_quantised_bytes(int P, const int* perBandPrimitiveCount_host, int xyz_is_half)
+{
+    return guarded(
+        [&]() {
+            if (P < 0 || !perBandPrimitiveCount_host) throw r3::Error("quantised_bytes: P >= 0 and four per-degree counts");
+            long long n = 0;
+            for (int d = 0; d < 4; d++) {
+                if (perBandPrimitiveCount_host[d] < 0) throw r3::Error("quantised_bytes: negative count");
+                n += perBandPrimitiveCount_host[d];
+            }
+            if (n != P) throw r3::Error("quantised_bytes: the per-degree counts do not add up to P");
+            return (size_t)r3::quant_model_bytes(P, perBandPrimitiveCount_host, xyz_is_half);
+        },
+        (size_t)0);
 }
 
 int r3dgs_colour_variance_accumulate(int P, const int* D, int M, int max_sh_deg, const float* means3D,

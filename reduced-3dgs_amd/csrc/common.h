@@ -528,6 +528,17 @@ struct FwdInputs {
 // so that no existing field moves (fields inside FwdInputs / BwdOutputs shifted every offset behind them, and the
 // register allocation of the existing instantiations with it: profiles/raw_params_kernel_resources.txt).
 
+// Quantised passes (r3dgs_quantised_forward, FwdPlan::quant; quant_math.h): the model arrives as codebook ids.  The pass
+// block carries them BEHIND everything the other passes use (FwdPassArgs::quant), like shs_rest; FwdInputs holds the band
+// tables of the ragged path and nothing else of the model.
+struct QuantInputs {
+    const void* xyz;                 // half [P,3] (bit pattern) or float [P,3]
+    const unsigned char* geom_ids;   // [P,8]
+    const unsigned char* sh_ids;     // ragged, 3 (d+1)^2 bytes per Gaussian
+    const float* codebooks;          // [20][256]
+    int xyz_is_half;
+};
+
 struct BwdOutputs {
     float* dL_dmean2D;   // [P,3]
     float* dL_dopacity;  // [P,1]
@@ -715,6 +726,7 @@ struct FwdPassArgs {
     RangesArgs ranges;
     BlendFwdArgs blend;
     const float* shs_rest;   // raw-parameter forward only: features_rest [P,M-1,3] (see FwdInputs)
+    QuantInputs quant;       // quantised forward only
 };
 struct BwdPassArgs {
     BlendBwdArgs blend;
@@ -737,6 +749,7 @@ struct FwdPlan {
     int generic_depth_sort;  // rocPRIM sort + scan instead of the bucketed sort (never inside a graph)
     int tight;             // opacity-aware tile rects (default) or the reference's 3-sigma squares
     int raw_params;        // the inputs are the model's raw parameters (see FwdInputs): the *_params instantiations
+    int quant;             // the inputs are codebook ids (QuantInputs): the *_quant instantiations; implies ragged
 };
 struct BwdPlan {
     int P, M, W, H, gx, gy;
@@ -762,6 +775,10 @@ void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, bool* present, hipStream_t s);
 void launch_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales, float* rotations,
                             hipStream_t s);   // preprocess.hip: param_math.h's scale_act / quat_act per Gaussian
+
+void launch_quantised_decode(int P, const int* coeffs, const int* perband, const int* cumsum, const QuantInputs& q, float* xyz,
+                             float* features_dc, float* features_rest, float* opacity, float* scaling, float* rotation,
+                             int* degrees, hipStream_t s);   // preprocess.hip: quant_math.h's quant_decode_one per Gaussian
 
 void issue_header_reduce(const HeaderArgs* a, hipStream_t s);
 void prepare_depth_bucket_sort(int nb);   // LDS opt-in of the depth-sort kernels, once per device (not a stream op)

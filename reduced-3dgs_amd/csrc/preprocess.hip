@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "depth_sort.h"
+#include "quant_math.h"
 
 namespace r3 {
 
@@ -169,10 +170,12 @@ __device__ __forceinline__ int ragged_offset(int idx, const int* coeffs, const i
 // the (launch-latency-bound) sort's kernels.
 // COLOR is 0, or 4 (r3dgs_forward_params): scales / rotations hold the model's RAW parameters and are activated after the
 // load (param_math.h).  The two keep these numbers because the committed profiles and bench.py cite the kernels by name.
+// COLOR 5 (r3dgs_quantised_forward): the raw parameters are looked up from the codebooks (quant_math.h; 8 id bytes and 6 or
+// 12 position bytes per Gaussian, the four geometry codebooks -- 4 KB -- through the cache), then activated as for 4.
 template <int COLOR>
 __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs* dst, FwdPassArgs v)
 {
-    static_assert(COLOR == 0 || COLOR == 4, "0: activated inputs, 4: raw parameters");
+    static_assert(COLOR == 0 || COLOR == 4 || COLOR == 5, "0: activated inputs, 4: raw parameters, 5: codebook ids");
     // first kernel of the forward: it gets the pass block by value, installs it for the kernels behind it ...
     if (blockIdx.x == 0) install_block_from_kernarg(dst, (int)threadIdx.x, kPreBlock);
     const PreArgs a = v.pre;   // ... and reads its own arguments from the kernarg segment (scalar loads)
@@ -187,7 +190,19 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
     o.tiles = 0;
     o.tiles_ref = 0;
     o.depth = 0.f;
-    if (valid) {
+    if (COLOR == 5) {
+        if (valid) {
+            float m[3], raw_op, sc[3], rq[4], q[4];
+            quant_xyz(v.quant.xyz, v.quant.xyz_is_half, i, m);
+            const uint2 gw = reinterpret_cast<const uint2*>(v.quant.geom_ids)[i];   // the eight ids in one load
+            const uint8_t gid[8] = {(uint8_t)gw.x, (uint8_t)(gw.x >> 8), (uint8_t)(gw.x >> 16), (uint8_t)(gw.x >> 24),
+                                    (uint8_t)gw.y, (uint8_t)(gw.y >> 8), (uint8_t)(gw.y >> 16), (uint8_t)(gw.y >> 24)};
+            quant_geom(v.quant.codebooks, gid, &raw_op, sc, rq);
+            for (int k = 0; k < 3; k++) sc[k] = scale_act(sc[k]);
+            quat_act(rq, q);
+            preprocess_one(cam, m[0], m[1], m[2], sc, q, nullptr, raw_op, &o, a.tight != 0);
+        }
+    } else if (valid) {
         const float mx = a.in.means3D[3 * i], my = a.in.means3D[3 * i + 1], mz = a.in.means3D[3 * i + 2];
         float sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c6[6];
         const float* c6p = nullptr;
@@ -208,6 +223,8 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
             }
         }
         preprocess_one(cam, mx, my, mz, sc, q, c6p, a.in.opacities[i], &o, a.tight != 0);
+    }
+    if (valid) {
         uint32_t dkey = 0xFFFFFFFFu;
         if (o.radius > 0) {
             GRec r;
@@ -386,6 +403,122 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
   }
 }
 
+// ---- colour role over the quantised model (r3dgs_quantised_forward) ---------------------------------------------------
+// The wave's 64 rows are one contiguous BYTE span of sh_ids (at most 64 x 48 B).  It starts at 3 * off_first bytes, which
+// is in general not aligned: the wave copies the 16-byte chunks that cover the span, aligned by ADDRESS, into LDS with
+// dwordx4 loads; a chunk that reaches in front of the array's first byte or behind its last (at most the first and the
+// last chunk of a span at an end of the array) is put together from byte loads of the bytes that exist.  The sixteen SH
+// codebooks (16 KB) are copied into LDS once per workgroup; a lane evaluates sh_to_rgb through an accessor that reads an id
+// byte of its row and gathers the centre -- the same values in the same order as the fp32 ragged path reads from its row.
+// LDS words of the id window are skewed one per 32 like the fp32 rows (lanes of a degree read 3 / 12 / 27 / 48 B apart).
+constexpr int kQuantSpanChunks = (64 * kRowFloats + 15 + 15) / 16 + 1;                 // 16-byte chunks of a misaligned span
+constexpr int kQuantSpanWords = 4 * kQuantSpanChunks + (4 * kQuantSpanChunks) / 32 + 1;   // + skew
+constexpr size_t kQuantBooksLds = sizeof(float) * kQuantShBooks * kQuantCentres;
+constexpr size_t kQuantColorLds = kQuantBooksLds + sizeof(uint32_t) * (kPreBlock / 64) * kQuantSpanWords;
+static_assert(kQuantSpanChunks <= 4 * 64, "four chunks per lane cover a span");
+
+struct ShRowQuantLds {
+    const uint8_t* ids;   // the wave's id window (skewed words)
+    int roff;             // first byte of the lane's row in the window
+    const float* books;   // [16][256] in LDS
+    __device__ __forceinline__ float at(int e) const
+    {
+        const int b = roff + e, w = b >> 2;
+        const uint32_t id = ids[((w + (w >> 5)) << 2) | (b & 3)];
+        return books[(quant_sh_book(e) << 8) + (int)id];
+    }
+};
+
+template <int BLOCK>
+__device__ __forceinline__ void color_role_quant(const PreArgs& a, const QuantInputs& qi, char* smem, int first, int last, int wg,
+                                                 int n_wg)
+{
+    float* s_books = reinterpret_cast<float*>(smem);
+    uint32_t(*s_ids)[kQuantSpanWords] = reinterpret_cast<uint32_t(*)[kQuantSpanWords]>(smem + kQuantBooksLds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.in.P;
+    if (first + wg < last) {   // (the first barrier of the loop below orders these stores in front of every read)
+        const float4* src = reinterpret_cast<const float4*>(qi.codebooks);
+        for (int k = tid; k < kQuantShBooks * kQuantCentres / 4; k += BLOCK) reinterpret_cast<float4*>(s_books)[k] = src[k];
+    }
+    const uintptr_t arr_begin = reinterpret_cast<uintptr_t>(qi.sh_ids);
+    const uintptr_t arr_end = arr_begin + (uintptr_t)quant_sh_bytes(a.in.coeffs_num, a.in.per_band_count);
+  for (int blk = first + wg; blk < last; blk += n_wg) {
+    const int i = blk * BLOCK + tid;
+    const bool valid = i < P;
+    const int wave_first = blk * BLOCK + wave * 64;
+    const bool vis = valid && a.tiles[i] > 0;
+
+    int deg = 0, roff = 0;
+    uintptr_t win = 0;   // address of the first chunk
+    int nchunks = 0;
+    if (wave_first < P) {
+        const int last_i = min(wave_first + 63, P - 1);
+        int d0, dl;
+        const int off_first = quant_ragged_offset(wave_first, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &d0);
+        const int off_last = quant_ragged_offset(last_i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &dl);
+        const uintptr_t span = arr_begin + 3ull * (uintptr_t)off_first;
+        const int span_len = 3 * (off_last + (dl + 1) * (dl + 1) - off_first);
+        const int head = (int)(span & 15u);
+        win = span - (uintptr_t)head;
+        nchunks = (head + span_len + 15) >> 4;
+        if (valid) {
+            const int off = quant_ragged_offset(i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &deg);
+            roff = head + 3 * (off - off_first);
+        }
+    }
+    if (__ballot(vis) != 0ull) {
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = k * 64 + lane;
+            v[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (c < nchunks) {
+                const uintptr_t p = win + 16ull * (uintptr_t)c;
+                if (p >= arr_begin && p + 16 <= arr_end) {
+                    v[k] = *reinterpret_cast<const uint4*>(p);
+                } else {   // an end of the array: only the bytes that exist
+                    uint32_t w[4] = {0u, 0u, 0u, 0u};
+                    for (int b = 0; b < 16; b++) {
+                        const uintptr_t q = p + (uintptr_t)b;
+                        if (q >= arr_begin && q < arr_end) w[b >> 2] |= (uint32_t)(*reinterpret_cast<const uint8_t*>(q)) << (8 * (b & 3));
+                    }
+                    v[k] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = k * 64 + lane;
+            if (c < nchunks) {
+                const int w = 4 * c;   // four words of one chunk never straddle a skew step: 4 c % 32 <= 28
+                uint32_t* d = s_ids[wave] + w + (w >> 5);
+                d[0] = v[k].x;
+                d[1] = v[k].y;
+                d[2] = v[k].z;
+                d[3] = v[k].w;
+            }
+        }
+    }
+    __syncthreads();
+
+    if (vis) {
+        float rgb[3], m[3];
+        uint32_t cbits = 0;
+        const float campos[3] = {a.view.campos[0], a.view.campos[1], a.view.campos[2]};
+        quant_xyz(qi.xyz, qi.xyz_is_half, i, m);
+        sh_to_rgb(deg, ShRowQuantLds{reinterpret_cast<const uint8_t*>(s_ids[wave]), roff, s_books}, m[0], m[1], m[2], campos, rgb,
+                  &cbits);
+        GRec* r = a.rec + i;
+        r->r = rgb[0];
+        r->g = rgb[1];
+        r->b = rgb[2];
+        if (cbits) r->width_clamp |= cbits << 16;  // same lane wrote the width in the geometry kernel
+    }
+    __syncthreads();   // the id window is reused by the next round
+  }
+}
+
 // standalone colour kernel (generic depth sort path only): small persistent grid
 template <bool RAGGED, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void preprocess_color_kernel(const PreArgs* __restrict__ ap)
@@ -401,6 +534,15 @@ __global__ __launch_bounds__(BLOCK) void preprocess_color_params_kernel(const Fw
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PreArgs a = pa->pre;
     color_role<false, BLOCK, true>(a, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x, pa->shs_rest);
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void preprocess_color_quant_kernel(const FwdPassArgs* __restrict__ pa)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const PreArgs a = pa->pre;
+    const QuantInputs qi = pa->quant;
+    color_role_quant<BLOCK>(a, qi, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- depth-sort kernels carrying a share of the colour stream in extra workgroups -------------------------------
@@ -447,6 +589,28 @@ __global__ __launch_bounds__(kPreBlock) void depth_sort_color_params_kernel(cons
     }
 }
 
+// the same with the colour role reading the quantised model
+template <int STEP>
+__global__ __launch_bounds__(kPreBlock) void depth_sort_color_quant_kernel(const FwdPassArgs* __restrict__ pa, int n_sort,
+                                                                           int c0, int c1)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int wg = (int)blockIdx.x;
+    if (wg < n_sort) {
+        const DepthArgs d = pa->depth;
+        if (STEP == 0)
+            depth_hist_role(d, pa->header, smem, wg);
+        else if (STEP == 1)
+            depth_scatter_role(d, smem, wg);
+        else
+            depth_bucket_group_role(d, smem, wg, n_sort);
+    } else {
+        const PreArgs a = pa->pre;
+        const QuantInputs qi = pa->quant;
+        color_role_quant<kPreBlock>(a, qi, smem, c0, c1, wg - n_sort, (int)gridDim.x - n_sort);
+    }
+}
+
 __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const DepthArgs* __restrict__ ap)
 {
     const DepthArgs d = *ap;
@@ -456,7 +620,9 @@ __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const Dep
 void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs& v, hipStream_t s)
 {
     const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
-    if (p.raw_params)
+    if (p.quant)
+        hipLaunchKernelGGL(preprocess_geom_kernel<5>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
+    else if (p.raw_params)
         hipLaunchKernelGGL(preprocess_geom_kernel<4>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
     else
         hipLaunchKernelGGL(preprocess_geom_kernel<0>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
@@ -466,7 +632,10 @@ void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s)
 {
     const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
     const int grid = p.color_grid > 0 && blocks > p.color_grid ? p.color_grid : blocks;
-    if (p.raw_params) {
+    if (p.quant) {
+        const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
+        hipLaunchKernelGGL((preprocess_color_quant_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), kQuantColorLds, s, pa);
+    } else if (p.raw_params) {
         const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
         hipLaunchKernelGGL((preprocess_color_params_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, pa);
     } else if (p.ragged) {
@@ -490,6 +659,13 @@ static void launch_sort_color_params(const FwdPassArgs* pa, int n_sort, int n_co
                        c0, c1);
 }
 
+template <int STEP>
+static void launch_sort_color_quant(const FwdPassArgs* pa, int n_sort, int n_color, int c0, int c1, size_t lds, hipStream_t s)
+{
+    hipLaunchKernelGGL((depth_sort_color_quant_kernel<STEP>), dim3(n_sort + n_color), dim3(kPreBlock), lds, s, pa, n_sort, c0,
+                       c1);
+}
+
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 template <int STEP, bool RAGGED>
@@ -505,6 +681,14 @@ static void opt_in_lds_params(size_t bytes)
 {
     if (bytes > 48 * 1024)
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_params_kernel<STEP>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+
+template <int STEP>
+static void opt_in_lds_quant(size_t bytes)
+{
+    if (bytes > 48 * 1024)
+        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_quant_kernel<STEP>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
@@ -530,6 +714,10 @@ void prepare_depth_bucket_sort(int nb)
     opt_in_lds_params<0>(h);
     opt_in_lds_params<1>(sc);
     opt_in_lds_params<2>(bs);
+    // the quantised colour role needs kQuantColorLds (29 KB): its launches take the sort role's size or that
+    opt_in_lds_quant<0>(max_sz(depth_hist_lds(nb), kQuantColorLds));
+    opt_in_lds_quant<1>(max_sz(depth_scatter_lds(nb), kQuantColorLds));
+    opt_in_lds_quant<2>(max_sz(kBucketSortLds, kQuantColorLds));
     if (kColorLds > 48 * 1024) {
         R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<false, kPreBlock>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
@@ -556,7 +744,15 @@ void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStre
     const size_t lds0 = n_color(0) ? max_sz(depth_hist_lds(nb), kColorLds) : depth_hist_lds(nb);
     const size_t lds1 = n_color(1) ? max_sz(depth_scatter_lds(nb), kColorLds) : depth_scatter_lds(nb);
     const size_t lds2 = n_color(2) ? max_sz(kBucketSortLds, kColorLds) : kBucketSortLds;
-    if (p.raw_params) {
+    if (p.quant) {
+        const size_t q0 = n_color(0) ? max_sz(depth_hist_lds(nb), kQuantColorLds) : depth_hist_lds(nb);
+        const size_t q1 = n_color(1) ? max_sz(depth_scatter_lds(nb), kQuantColorLds) : depth_scatter_lds(nb);
+        const size_t q2 = n_color(2) ? max_sz(kBucketSortLds, kQuantColorLds) : kBucketSortLds;
+        launch_sort_color_quant<0>(pa, rows, n_color(0), c[0], c[1], q0, s);
+        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
+        launch_sort_color_quant<1>(pa, rows, n_color(1), c[1], c[2], q1, s);
+        launch_sort_color_quant<2>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], q2, s);
+    } else if (p.raw_params) {
         launch_sort_color_params<0>(pa, rows, n_color(0), c[0], c[1], lds0, s);
         hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
         launch_sort_color_params<1>(pa, rows, n_color(1), c[1], c[2], lds1, s);
@@ -612,6 +808,26 @@ void launch_activate_params(int P, const float* scaling_raw, const float* rotati
 {
     hipLaunchKernelGGL(activate_params_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, scaling_raw, rotation_raw, scales,
                        rotations);
+}
+
+// r3dgs_quantised_decode: the dense tensors of the reference's load_ply, by the very functions the quantised kernels call
+__global__ __launch_bounds__(256) void quantised_decode_kernel(int P, const int* __restrict__ coeffs, const int* __restrict__ perband,
+                                                               const int* __restrict__ cumsum, QuantInputs q, float* xyz,
+                                                               float* features_dc, float* features_rest, float* opacity,
+                                                               float* scaling, float* rotation, int* degrees)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    quant_decode_one(i, coeffs, perband, cumsum, q.xyz, q.xyz_is_half, q.geom_ids, q.sh_ids, q.codebooks, xyz, features_dc,
+                     features_rest, opacity, scaling, rotation, degrees);
+}
+
+void launch_quantised_decode(int P, const int* coeffs, const int* perband, const int* cumsum, const QuantInputs& q, float* xyz,
+                             float* features_dc, float* features_rest, float* opacity, float* scaling, float* rotation,
+                             int* degrees, hipStream_t s)
+{
+    hipLaunchKernelGGL(quantised_decode_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, coeffs, perband, cumsum, q, xyz,
+                       features_dc, features_rest, opacity, scaling, rotation, degrees);
 }
 
 }  // namespace r3

@@ -101,6 +101,16 @@ if hasattr(_lib, "r3dgs_forward_params"):   # raster from the model's raw parame
     _lib.r3dgs_activate_params.restype = _i
     _lib.r3dgs_activate_params.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
 
+if hasattr(_lib, "r3dgs_quantised_forward"):   # include/r3dgs_quantised.h
+    _FWD_QUANT_TAIL = [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+    _lib.r3dgs_quantised_forward.restype = _i
+    _lib.r3dgs_quantised_forward.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL
+    _lib.r3dgs_quantised_forward_reserved.restype = C.c_longlong
+    _lib.r3dgs_quantised_forward_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL
+    _lib.r3dgs_quantised_decode.restype = _i
+    _lib.r3dgs_quantised_decode.argtypes = [_i, _vp, _vp, _vp, _vp, _i] + [_vp] * 11
+    _lib.r3dgs_quantised_bytes.restype = C.c_size_t
+    _lib.r3dgs_quantised_bytes.argtypes = [_i, C.POINTER(_i), _i]
 _lib.r3dgs_colour_variance_accumulate.restype = _i
 _lib.r3dgs_colour_variance_accumulate.argtypes = [_i, _vp, _i, _i] + [_vp] * 12
 _lib.r3dgs_min_pixel_size.restype = _i
@@ -891,6 +901,138 @@ def activate_params(scaling, rotation):
         with _on_device(dev):
             _check(_lib.r3dgs_activate_params(P, _ptr(scaling), _ptr(rotation), _ptr(s), _ptr(q), _stream()), "activate_params")
     return s, q
+
+
+# ---- the quantised (codebook-indexed) model: include/r3dgs_quantised.h ------------------------------------------------
+# Inference only.  The arrays are read in place; a tensor that would need a copy is refused.
+
+def _need_quantised():
+    if not hasattr(_lib, "r3dgs_quantised_forward"):
+        raise RuntimeError("the loaded libr3dgs_hip.so has no quantised entry points: rebuild it with build.py")
+
+
+def _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum):
+    """-> (P, xyz_is_half, device); the refusals of the quantised path."""
+    dev = xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise RuntimeError("xyz must have dimensions (num_points, 3)")
+    if xyz.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"xyz: the quantised path needs float16 or float32, got {xyz.dtype}")
+    P = int(xyz.size(0))
+    if geom_ids.dtype != torch.uint8 or tuple(geom_ids.shape) != (P, 8):
+        raise RuntimeError("geom_ids must be uint8 with dimensions (num_points, 8)")
+    if sh_ids.dtype != torch.uint8 or sh_ids.dim() != 1:
+        raise RuntimeError("sh_ids must be a flat uint8 tensor")
+    if codebooks.dtype != torch.float32 or tuple(codebooks.shape) != (20, 256):
+        raise RuntimeError("codebooks must be float32 with dimensions (20, 256)")
+    for t, name in ((perBandPrimitiveCount, "perBandPrimitiveCount"), (cumSumPrimitiveCount, "cumSumPrimitiveCount"),
+                    (coeffsNum, "coeffsNum")):
+        if t.dtype != torch.int32 or t.numel() != 4:
+            raise RuntimeError(f"{name} must be int32 with 4 entries (degrees 0..3)")
+    for t, name in ((xyz, "xyz"), (geom_ids, "geom_ids"), (sh_ids, "sh_ids"), (codebooks, "codebooks"),
+                    (perBandPrimitiveCount, "perBandPrimitiveCount"), (cumSumPrimitiveCount, "cumSumPrimitiveCount"),
+                    (coeffsNum, "coeffsNum")):
+        if t.device != dev:
+            raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name}: the quantised path needs a contiguous tensor")
+    return P, int(xyz.dtype == torch.float16), dev
+
+
+def rasterize_gaussians_quantised(background, xyz, geom_ids, sh_ids, codebooks, scale_modifier, viewmatrix, projmatrix,
+                                  tan_fovx, tan_fovy, image_height, image_width, perBandPrimitiveCount, cumSumPrimitiveCount,
+                                  coeffsNum, campos, prefiltered, debug, counters=None, exact=False, _reserve=None,
+                                  _strict_override=None):
+    """rasterize_gaussians_variableSH_bands over the quantised model (xyz half or float [P,3], geom_ids uint8 [P,8], sh_ids
+    uint8 ragged, codebooks float [20,256]; r3dgs_quantised.QuantisedModel holds them) -> (num_rendered, out_color[3,H,W],
+    radii[P], geomBuffer, binningBuffer, imgBuffer); same asynchronous / exact-size / strict-mode behaviour.  `counters`:
+    (out_touched_pixels int32 [P], out_transmittance float [P]) for counter mode.  sh_ids is not length-checked against the
+    band tables here (they live on the device); QuantisedModel builds them together."""
+    _need_quantised()
+    P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
+    H, W = int(image_height), int(image_width)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    if P == 0:
+        e = torch.empty(0, **u8)
+        return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+    _tls.next_forward_trains = None
+    strict = _strict if _strict_override is None else bool(_strict_override)
+    out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    touched = transm = None
+    if counters is not None:
+        touched, transm = counters
+    if vm is not None:
+        _track_view(vm)
+    _lib.r3dgs_forward_hint(0)   # no backward exists for this model
+    with _on_device(dev):
+        args = (P, None, 4, _ptr(coeffsNum), _ptr(perBandPrimitiveCount), _ptr(cumSumPrimitiveCount), _ptr(bg), W, H,
+                xyz.data_ptr(), half, geom_ids.data_ptr(), sh_ids.data_ptr() if sh_ids.numel() else None, codebooks.data_ptr(),
+                float(scale_modifier), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+                _ptr(out_color), _ptr(touched), _ptr(transm), _ptr(radii), int(counters is not None), int(bool(debug)),
+                _stream())
+        reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, _ptr(vm))
+        if _reserve is not None:
+            reserve = int(_reserve)
+        if reserve > 0:
+            geom = torch.empty(_blob_bytes("geom_lean", P), **u8)
+            binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
+            img = torch.empty(_blob_bytes("img", W, H), **u8)
+            ticket = _lib.r3dgs_quantised_forward_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *args)
+            if ticket < 0:
+                _check(-1, "rasterize_gaussians_quantised")
+            _stats["reserved_passes"] += 1
+            nr = NumRendered(ticket, reserve)
+            if not strict:
+                _watch_overflow()
+                return nr, out_color, radii, geom, binning, img
+            if not nr.truncated:
+                return nr, out_color, radii, geom, binning, img
+            _stats["redone_passes"] += 1
+            if counters is not None:   # counter mode accumulates into its outputs
+                touched.zero_()
+                transm.zero_()
+            del geom, binning, img
+        geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
+        rendered = _lib.r3dgs_quantised_forward(geom.cb, None, binning.cb, None, img.cb, None, *args)
+    for blob in (geom, binning, img):
+        if blob.error is not None:
+            raise blob.error
+    _check(rendered, "rasterize_gaussians_quantised")
+    _stats["exact_passes"] += 1
+    pairs = int(_lib.r3dgs_forward_pairs())
+    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom.tensor, binning.tensor, img.tensor
+
+
+def quantised_decode(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum):
+    """The dense fp32 tensors the reference's load_ply returns for the model, decoded on the device by the functions the
+    quantised kernels use (csrc/quant_math.h) -> (xyz [P,3], features_dc [P,1,3], features_rest [P,15,3], opacity [P,1],
+    scaling [P,3], rotation [P,4], degrees int32 [P,1])."""
+    _need_quantised()
+    P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # every element is written by the library
+    out = (f(P, 3), f(P, 1, 3), f(P, 15, 3), f(P, 1), f(P, 3), f(P, 4), torch.empty((P, 1), dtype=torch.int32, device=dev))
+    if P:
+        with _on_device(dev):
+            _check(_lib.r3dgs_quantised_decode(P, _ptr(coeffsNum), _ptr(perBandPrimitiveCount), _ptr(cumSumPrimitiveCount),
+                                               xyz.data_ptr(), half, geom_ids.data_ptr(),
+                                               sh_ids.data_ptr() if sh_ids.numel() else geom_ids.data_ptr(),
+                                               codebooks.data_ptr(), *(t.data_ptr() for t in out), _stream()), "quantised_decode")
+    return out
+
+
+def quantised_bytes(P, per_band_count, xyz_is_half):
+    """Resident bytes of a quantised model with `per_band_count` Gaussians of degree 0..3 (needs no GPU)."""
+    _need_quantised()
+    counts = (_i * 4)(*[int(c) for c in per_band_count])
+    n = int(_lib.r3dgs_quantised_bytes(int(P), counts, int(bool(xyz_is_half))))
+    if n == 0:
+        raise RuntimeError(f"quantised_bytes: {_lib.r3dgs_last_error().decode()}")
+    return n
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

@@ -12,7 +12,8 @@ The fused path is taken when the call asks for nothing it does not cover; otherw
 pipe.convert_SHs_python, override_color, variable_sh_bands -- the call does what the reference's does, through the existing
 package entry points.  `pc` is anything shaped like the reference's GaussianModel: _xyz, _features_dc, _features_rest,
 _opacity, _scaling, _rotation, _degrees, active_sh_degree, max_sh_degree (and get_* / get_covariance / per_band_count for
-the fallback routes).
+the fallback routes) -- or a r3dgs_quantised.QuantisedModel, which is rendered from its ids and codebooks in place
+(inference only: "viewspace_points" is None, and the three Python-side options and override_color are refused).
 """
 import math
 
@@ -20,6 +21,7 @@ import torch
 
 from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C,
                                          rasterize_gaussian_params)
+from r3dgs_quantised import QuantisedModel
 
 
 def _settings(camera, pc, pipe, bg_color, scaling_modifier):
@@ -39,10 +41,41 @@ def fused_path_applies(pc, pipe, override_color=None, variable_sh_bands=False):
     return all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
 
 
+def _render_quantised(camera, qm, pipe, bg_color, scaling_modifier, override_color, lambda_sh_sparsity, measure_fps):
+    """render() of a QuantisedModel: the rasterizer reads ids, positions and codebooks in place.  Inference only."""
+    if override_color is not None:
+        raise ValueError("render: override_color is not supported for a QuantisedModel (colours come from its codebooks); "
+                         "decode() it and render the dense tensors")
+    if pipe.compute_cov3D_python:
+        raise ValueError("render: pipe.compute_cov3D_python is not supported for a QuantisedModel (the kernels activate the "
+                         "looked-up scales and rotations); decode() it and render the dense tensors")
+    if pipe.convert_SHs_python:
+        raise ValueError("render: pipe.convert_SHs_python is not supported for a QuantisedModel (the kernels evaluate SH from "
+                         "the ids); decode() it and render the dense tensors")
+    if lambda_sh_sparsity:
+        raise ValueError("render: a QuantisedModel has no gradients (lambda_sh_sparsity must be 0)")
+    rs = _settings(camera, qm, pipe, bg_color, scaling_modifier)
+    fps = 0
+    if measure_fps:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+    _, image, radii, _, _, _ = _C.rasterize_gaussians_quantised(
+        rs.bg, qm.xyz, qm.geom_ids, qm.sh_ids, qm.codebooks, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
+        rs.tanfovy, rs.image_height, rs.image_width, qm.per_band, qm.cumsum, qm.coeffs, rs.campos, rs.prefiltered, rs.debug)
+    if measure_fps:
+        t1.record()
+        torch.cuda.synchronize()
+        fps = 1 / t0.elapsed_time(t1)
+    return {"render": image, "viewspace_points": None, "visibility_filter": radii > 0, "radii": radii, "FPS": fps}
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, lambda_sh_sparsity=0.,
            measure_fps=False, variable_sh_bands=False):
     """Render the scene seen by `viewpoint_camera`.  bg_color must be a device tensor.
     -> {"render", "viewspace_points", "visibility_filter", "radii", "FPS"}"""
+    if isinstance(pc, QuantisedModel):
+        return _render_quantised(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, lambda_sh_sparsity,
+                                 measure_fps)
     xyz = pc._xyz
     # a zero tensor whose gradient is the screen-space gradient of the means (densification statistics)
     screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0
