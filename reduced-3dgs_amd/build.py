@@ -41,12 +41,15 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's
     # kernels perform written out (adam_math.h)
     "optim.hip": EXACT,
+    # per-iteration training statistics: the roundings stats_math.h names and no others (bit-exact accumulator updates)
+    "train_stats.hip": EXACT,
     "capi.hip": [],
 }
-HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
+HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", "stats_math.h",
+           os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
            os.path.join("..", "..", "include", "r3dgs_quantised.h"),
            os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),
-           os.path.join("..", "..", "include", "r3dgs_optim.h")]
+           os.path.join("..", "..", "include", "r3dgs_optim.h"), os.path.join("..", "..", "include", "r3dgs_trainstats.h")]
 
 
 def _newest(paths):
@@ -100,7 +103,8 @@ def build_torch_binding(force=False, verbose=True):
     import sysconfig
 
     import torch
-    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h")]
+    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h",
+                                                               "r3dgs_trainstats.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
             [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT

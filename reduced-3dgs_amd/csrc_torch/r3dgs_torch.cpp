@@ -24,6 +24,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <limits>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -34,6 +35,7 @@
 #include "r3dgs_loss.h"
 #include "r3dgs_optim.h"
 #include "r3dgs_rasterizer.h"
+#include "r3dgs_trainstats.h"
 
 namespace {
 
@@ -66,6 +68,10 @@ struct Api {
     R3_FN(r3dgs_forward_params_reserved)
     R3_FN(r3dgs_backward_params)
     R3_FN(r3dgs_activate_params)
+    R3_FN(r3dgs_train_stats_workspace_bytes)
+    R3_FN(r3dgs_visible_means)
+    R3_FN(r3dgs_alpha_regul_backward)
+    R3_FN(r3dgs_densification_stats)
 #undef R3_FN
     bool bound = false;
 } api;
@@ -110,6 +116,11 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_OPT(r3dgs_forward_params_reserved)
     R3_OPT(r3dgs_backward_params)
     R3_OPT(r3dgs_activate_params)
+    // the training statistics (r3dgs_trainstats.h): likewise
+    R3_OPT(r3dgs_train_stats_workspace_bytes)
+    R3_OPT(r3dgs_visible_means)
+    R3_OPT(r3dgs_alpha_regul_backward)
+    R3_OPT(r3dgs_densification_stats)
 #undef R3_OPT
     api.bound = true;
 }
@@ -630,6 +641,67 @@ void adam_step_capturable(const std::vector<Tensor>& params, const std::vector<T
     if (api.r3dgs_adam_step_capturable((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step_capturable");
 }
 
+// ---- per-iteration training statistics (r3dgs_trainstats.h): the same calls as diff_gaussian_rasterization/_C.py's
+// visible_means / alpha_regul_backward / densification_stats; r3dgs_train_stats.py has checked the tensors (one device, dtypes,
+// shapes, contiguity).  Absent optional tensors are empty.
+
+void need_stats()
+{
+    need_bound();
+    if (!api.r3dgs_visible_means) throw std::runtime_error("the loaded libr3dgs_hip.so has no training statistics: rebuild it with build.py");
+}
+
+// -> (visibility bool[P], n_visible int32 0-d, alpha_mean fp32 0-d, sh_abs_mean fp32 0-d); a mean that was not asked for (want_alpha /
+// want_sh false) comes back as an empty tensor.  features_rest may be empty with want_sh set: M == 1, the mean of nothing.
+std::tuple<Tensor, Tensor, Tensor, Tensor> visible_means(const Tensor& radii, const Tensor& opacity, const Tensor& features_rest,
+                                                         bool want_alpha, bool want_sh, int64_t M)
+{
+    need_stats();
+    const c10::Device dev = radii.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    const int64_t P = radii.numel();
+    Tensor vis = at::empty({P}, f32.dtype(at::kBool));
+    if (P == 0) {
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        return {vis, at::zeros({}, f32.dtype(at::kInt)), want_alpha ? at::full({}, nan, f32) : at::empty({0}, f32),
+                want_sh ? at::full({}, nan, f32) : at::empty({0}, f32)};
+    }
+    Tensor n = at::empty({}, f32.dtype(at::kInt));
+    Tensor alpha = want_alpha ? at::empty({}, f32) : at::empty({0}, f32);
+    Tensor sh = want_sh ? at::empty({}, f32) : at::empty({0}, f32);
+    Tensor ws = at::empty({(int64_t)api.r3dgs_train_stats_workspace_bytes((int)P)}, f32.dtype(at::kByte));
+    if (api.r3dgs_visible_means((int)P, (int)M, radii.data_ptr<int>(), opt_ptr<float>(opacity), opt_ptr<float>(features_rest),
+                                reinterpret_cast<uint8_t*>(vis.data_ptr()), n.data_ptr<int>(), want_alpha ? alpha.data_ptr<float>() : nullptr,
+                                want_sh ? sh.data_ptr<float>() : nullptr, reinterpret_cast<char*>(ws.data_ptr()), cur_stream(dev)) < 0)
+        fail("visible_means");
+    return {vis, n, alpha, sh};
+}
+
+void alpha_regul_backward(const Tensor& radii, const Tensor& opacity, const Tensor& upstream, const Tensor& n_visible, Tensor& grad)
+{
+    need_stats();
+    if (radii.numel() == 0) return;
+    const c10::Device dev = radii.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    if (api.r3dgs_alpha_regul_backward((int)radii.numel(), radii.data_ptr<int>(), opacity.data_ptr<float>(), upstream.data_ptr<float>(),
+                                       n_visible.data_ptr<int>(), grad.data_ptr<float>(), cur_stream(dev)) < 0)
+        fail("alpha_regul_backward");
+}
+
+void densification_stats(const Tensor& viewspace_grad, const Tensor& radii, Tensor& xyz_gradient_accum, Tensor& denom,
+                         Tensor& max_radii2D)
+{
+    need_stats();
+    if (radii.numel() == 0) return;
+    const c10::Device dev = radii.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    if (api.r3dgs_densification_stats((int)radii.numel(), viewspace_grad.data_ptr<float>(), radii.data_ptr<int>(),
+                                      xyz_gradient_accum.data_ptr<float>(), denom.data_ptr<float>(), max_radii2D.data_ptr<float>(),
+                                      cur_stream(dev)) < 0)
+        fail("densification_stats");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -649,6 +721,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("l1_backward", &l1_backward);
     m.def("adam_step", &adam_step);
     m.def("adam_step_capturable", &adam_step_capturable);
+    m.def("visible_means", &visible_means);
+    m.def("alpha_regul_backward", &alpha_regul_backward);
+    m.def("densification_stats", &densification_stats);
     m.def("library_version", []() {
         need_bound();
         return std::string(api.r3dgs_version());

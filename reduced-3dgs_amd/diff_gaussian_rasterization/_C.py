@@ -163,6 +163,15 @@ if hasattr(_lib, "r3dgs_adam_step"):   # fused Adam step (include/r3dgs_optim.h;
     _lib.r3dgs_adam_step.argtypes = [_i, C.POINTER(_AdamSegment), _vp]
     _lib.r3dgs_adam_step_capturable.restype = _i
     _lib.r3dgs_adam_step_capturable.argtypes = [_i, C.POINTER(_AdamCapturableSegment), _vp]
+if hasattr(_lib, "r3dgs_visible_means"):   # per-iteration training statistics (include/r3dgs_trainstats.h; absent from older A/B builds)
+    _lib.r3dgs_train_stats_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_train_stats_workspace_bytes.argtypes = [_i]
+    _lib.r3dgs_visible_means.restype = _i
+    _lib.r3dgs_visible_means.argtypes = [_i, _i] + [_vp] * 9
+    _lib.r3dgs_alpha_regul_backward.restype = _i
+    _lib.r3dgs_alpha_regul_backward.argtypes = [_i] + [_vp] * 6
+    _lib.r3dgs_densification_stats.restype = _i
+    _lib.r3dgs_densification_stats.argtypes = [_i] + [_vp] * 6
 _lib.r3dgs_profile_enable.argtypes = [_i]
 _lib.r3dgs_profile_stage_name.restype = C.c_char_p
 _lib.r3dgs_profile_stage_name.argtypes = [_i]
@@ -181,6 +190,8 @@ _EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3
                    "r3dgs_adam_step", "r3dgs_adam_step_capturable")   # ... nor a fused Adam
 _EXT_PARAMS_FUNCS = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r3dgs_backward_params",
                      "r3dgs_activate_params")   # ... nor the raw-parameter entry points
+_EXT_STATS_FUNCS = ("r3dgs_train_stats_workspace_bytes", "r3dgs_visible_means", "r3dgs_alpha_regul_backward",
+                    "r3dgs_densification_stats")   # ... nor the training statistics
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -190,7 +201,8 @@ if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
         _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value
-                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS if hasattr(_lib, f))})
+                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS + _EXT_STATS_FUNCS
+                                                         if hasattr(_lib, f))})
         _ext = _ext_loaded
     except ImportError:
         if _binding_request == "torch":
@@ -1503,4 +1515,70 @@ def adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scala
                                          *scalars[4 * i:4 * i + 4])
     with _on_device(params[0].device):
         _check(_lib.r3dgs_adam_step_capturable(n, segs, _stream()), "adam_step_capturable")
+    return None
+
+
+# ---- per-iteration training statistics (include/r3dgs_trainstats.h, csrc/train_stats.hip); the surface is r3dgs_train_stats.py,
+# which checks the tensors (one device, dtypes, shapes, contiguity).  These calls only allocate and launch, on the current
+# stream, without a host synchronisation, so they can be captured in a graph.
+
+def _need_stats():
+    if not hasattr(_lib, "r3dgs_visible_means"):
+        raise RuntimeError(f"{_LIB_PATH} has no training statistics (r3dgs_visible_means): rebuild it with build.py")
+
+
+def visible_means(radii, opacity, features_rest):
+    """-> (visibility bool[P], n_visible int32 0-d, alpha_mean fp32 0-d or None, sh_abs_mean fp32 0-d or None) of
+    r3dgs_visible_means.  opacity: raw fp32 [P] / [P,1] or None; features_rest: fp32 [P,M-1,3] or None (M - 1 may be 0: the mean
+    of nothing, NaN).  P == 0 gives n_visible = 0 and NaN means without a launch."""
+    _need_stats()
+    dev = _need_gpu(radii, "visible_means")
+    P = int(radii.numel())
+    M = 1 if features_rest is None else int(features_rest.size(1)) + 1
+    if _ext is not None:
+        vis, n, alpha, sh = _ext.visible_means(radii, _t(opacity), _t(features_rest), opacity is not None, features_rest is not None, M)
+        return vis, n, (None if opacity is None else alpha), (None if features_rest is None else sh)
+    f32 = dict(dtype=torch.float32, device=dev)
+    vis = torch.empty((P,), dtype=torch.bool, device=dev)
+    if P == 0:
+        nan = torch.full((), float("nan"), **f32)
+        return (vis, torch.zeros((), dtype=torch.int32, device=dev), None if opacity is None else nan,
+                None if features_rest is None else nan.clone())
+    n = torch.empty((), dtype=torch.int32, device=dev)
+    alpha = None if opacity is None else torch.empty((), **f32)
+    sh = None if features_rest is None else torch.empty((), **f32)
+    with _on_device(dev):
+        ws = torch.empty((_lib.r3dgs_train_stats_workspace_bytes(P),), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_visible_means(P, M, radii.data_ptr(), _ptr(opacity), _ptr(features_rest), vis.data_ptr(), n.data_ptr(),
+                                        _ptr(alpha), _ptr(sh), ws.data_ptr(), _stream()), "visible_means")
+    return vis, n, alpha, sh
+
+
+def alpha_regul_backward(radii, opacity, upstream, n_visible, grad):
+    """grad[i] += upstream * (radii[i] > 0) * sigmoid'(opacity[i]) / n_visible, in place (r3dgs_alpha_regul_backward);
+    upstream, n_visible: 0-d device tensors."""
+    _need_stats()
+    dev = _need_gpu(radii, "alpha_regul_backward")
+    if _ext is not None:
+        return _ext.alpha_regul_backward(radii, opacity, upstream, n_visible, grad)
+    P = int(radii.numel())
+    if P:
+        with _on_device(dev):
+            _check(_lib.r3dgs_alpha_regul_backward(P, radii.data_ptr(), opacity.data_ptr(), upstream.data_ptr(),
+                                                   n_visible.data_ptr(), grad.data_ptr(), _stream()), "alpha_regul_backward")
+    return None
+
+
+def densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D):
+    """train.py:134 and gaussian_model.py:693-695 in one launch, in place on the three accumulators
+    (r3dgs_densification_stats)."""
+    _need_stats()
+    dev = _need_gpu(radii, "densification_stats")
+    if _ext is not None:
+        return _ext.densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D)
+    P = int(radii.numel())
+    if P:
+        with _on_device(dev):
+            _check(_lib.r3dgs_densification_stats(P, viewspace_grad.data_ptr(), radii.data_ptr(), xyz_gradient_accum.data_ptr(),
+                                                  denom.data_ptr(), max_radii2D.data_ptr(), _stream()), "densification_stats")
     return None
