@@ -61,6 +61,21 @@ typedef struct r3dgs_adam_capturable_segment {
 
 int r3dgs_adam_step_capturable(int n_segments, const r3dgs_adam_capturable_segment* segments, void* stream);
 
+/* The visibility-gated step (opt-in; the two calls above are unchanged by it).  Every segment is a [P, row_len[i]] array
+ * (n == P * row_len[i]; row_len: a host array of n_segments ints >= 1) and radii is the rasterizer's device int[P].
+ * Gaussian j is visible iff radii[j] > 0.  The elements of a visible Gaussian take exactly the step of the dense call with
+ * the same scalars; those of any other keep the bits of param, exp_avg and exp_avg_sq, and their gradient is not looked at
+ * (it may hold NaN or Inf).  The step count and so the bias corrections are the tensor's, not the row's, as in
+ * torch.optim.SparseAdam; with every Gaussian visible the result equals the dense call's bit for bit.  Unlike the dense
+ * step, a culled Gaussian's moments do not decay and its parameters do not move on their momentum.
+ * Refused before anything is launched: row_len[i] < 1, n != P * row_len[i], radii NULL with P > 0, and all the dense calls
+ * refuse.  P == 0 launches no step kernel (the capturable form still bumps the counts).  radii is read on the stream at
+ * run time, so a captured graph follows new contents of the same buffer. */
+int r3dgs_adam_step_visible(int n_segments, const r3dgs_adam_segment* segments, const int* row_len, const int* radii,
+                            long long P, void* stream);
+int r3dgs_adam_step_capturable_visible(int n_segments, const r3dgs_adam_capturable_segment* segments, const int* row_len,
+                                       const int* radii, long long P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

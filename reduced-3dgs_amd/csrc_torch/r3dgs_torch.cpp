@@ -64,6 +64,8 @@ struct Api {
     R3_FN(r3dgs_l1_backward)
     R3_FN(r3dgs_adam_step)
     R3_FN(r3dgs_adam_step_capturable)
+    R3_FN(r3dgs_adam_step_visible)
+    R3_FN(r3dgs_adam_step_capturable_visible)
     R3_FN(r3dgs_forward_params)
     R3_FN(r3dgs_forward_params_reserved)
     R3_FN(r3dgs_backward_params)
@@ -111,6 +113,8 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_OPT(r3dgs_l1_backward)
     R3_OPT(r3dgs_adam_step)
     R3_OPT(r3dgs_adam_step_capturable)
+    R3_OPT(r3dgs_adam_step_visible)
+    R3_OPT(r3dgs_adam_step_capturable_visible)
     // the raw-parameter entry points: absent from an older A/B build, whose calls then refuse
     R3_OPT(r3dgs_forward_params)
     R3_OPT(r3dgs_forward_params_reserved)
@@ -641,6 +645,74 @@ void adam_step_capturable(const std::vector<Tensor>& params, const std::vector<T
     if (api.r3dgs_adam_step_capturable((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step_capturable");
 }
 
+// ---- the visibility-gated step: radii is the rasterizer's device int32 [P], every tensor [P, ...]
+
+void need_optim_visible()
+{
+    need_bound();
+    if (!api.r3dgs_adam_step_visible)
+        throw std::runtime_error("the loaded libr3dgs_hip.so has no visibility-gated Adam: rebuild it with build.py");
+}
+
+// floats per Gaussian of each tensor (the C ABI checks n == P * row_len again)
+std::vector<int> row_lens(const std::vector<Tensor>& params, long long P, const char* what)
+{
+    std::vector<int> out;
+    for (const Tensor& t : params) {
+        if (t.dim() < 1 || t.size(0) != P)
+            throw std::runtime_error(std::string(what) + ": a tensor is not [P, ...] with P = " + std::to_string(P));
+        out.push_back(P ? (int)(t.numel() / P) : 1);
+    }
+    return out;
+}
+
+void adam_step_visible(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+                       const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars, const Tensor& radii)
+{
+    need_optim_visible();
+    const size_t n = params.size();
+    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 6);
+    if (n == 0) return;
+    const c10::Device dev = params[0].device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const long long P = radii.numel();
+    const std::vector<int> lens = row_lens(params, P, "adam_step_visible");
+    std::vector<r3dgs_adam_segment> segs(n);
+    for (size_t i = 0; i < n; i++) {
+        const double* s = &scalars[6 * i];
+        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
+                   exp_avg_sqs[i].data_ptr<float>(), (long long)params[i].numel(), (float)s[0], (float)s[1], (float)s[2],
+                   (float)s[3], (float)s[4], (float)s[5]};
+    }
+    if (api.r3dgs_adam_step_visible((int)n, segs.data(), lens.data(), opt_ptr<int>(radii), P, cur_stream(dev)) < 0)
+        fail("adam_step_visible");
+}
+
+void adam_step_capturable_visible(const std::vector<Tensor>& params, const std::vector<Tensor>& grads,
+                                  const std::vector<Tensor>& exp_avgs, const std::vector<Tensor>& exp_avg_sqs,
+                                  const std::vector<Tensor>& steps, const std::vector<Tensor>& lrs,
+                                  const std::vector<double>& scalars, const Tensor& radii)
+{
+    need_optim_visible();
+    const size_t n = params.size();
+    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 4);
+    if (steps.size() != n || lrs.size() != n) throw std::runtime_error("adam_step_capturable_visible: list lengths differ");
+    if (n == 0) return;
+    const c10::Device dev = params[0].device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const long long P = radii.numel();
+    const std::vector<int> lens = row_lens(params, P, "adam_step_capturable_visible");
+    std::vector<r3dgs_adam_capturable_segment> segs(n);
+    for (size_t i = 0; i < n; i++) {
+        const double* s = &scalars[4 * i];
+        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
+                   exp_avg_sqs[i].data_ptr<float>(), steps[i].data_ptr<float>(), opt_ptr<float>(lrs[i]),
+                   (long long)params[i].numel(), s[0], s[1], s[2], s[3]};
+    }
+    if (api.r3dgs_adam_step_capturable_visible((int)n, segs.data(), lens.data(), opt_ptr<int>(radii), P, cur_stream(dev)) < 0)
+        fail("adam_step_capturable_visible");
+}
+
 // ---- per-iteration training statistics (r3dgs_trainstats.h): the same calls as diff_gaussian_rasterization/_C.py's
 // visible_means / alpha_regul_backward / densification_stats; r3dgs_train_stats.py has checked the tensors (one device, dtypes,
 // shapes, contiguity).  Absent optional tensors are empty.
@@ -721,6 +793,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("l1_backward", &l1_backward);
     m.def("adam_step", &adam_step);
     m.def("adam_step_capturable", &adam_step_capturable);
+    m.def("adam_step_visible", &adam_step_visible);
+    m.def("adam_step_capturable_visible", &adam_step_capturable_visible);
     m.def("visible_means", &visible_means);
     m.def("alpha_regul_backward", &alpha_regul_backward);
     m.def("densification_stats", &densification_stats);

@@ -163,6 +163,12 @@ if hasattr(_lib, "r3dgs_adam_step"):   # fused Adam step (include/r3dgs_optim.h;
     _lib.r3dgs_adam_step.argtypes = [_i, C.POINTER(_AdamSegment), _vp]
     _lib.r3dgs_adam_step_capturable.restype = _i
     _lib.r3dgs_adam_step_capturable.argtypes = [_i, C.POINTER(_AdamCapturableSegment), _vp]
+if hasattr(_lib, "r3dgs_adam_step_visible"):   # the visibility-gated step (absent from older A/B builds)
+    _lib.r3dgs_adam_step_visible.restype = _i
+    _lib.r3dgs_adam_step_visible.argtypes = [_i, C.POINTER(_AdamSegment), C.POINTER(_i), _vp, C.c_longlong, _vp]
+    _lib.r3dgs_adam_step_capturable_visible.restype = _i
+    _lib.r3dgs_adam_step_capturable_visible.argtypes = [_i, C.POINTER(_AdamCapturableSegment), C.POINTER(_i), _vp,
+                                                        C.c_longlong, _vp]
 if hasattr(_lib, "r3dgs_visible_means"):   # per-iteration training statistics (include/r3dgs_trainstats.h; absent from older A/B builds)
     _lib.r3dgs_train_stats_workspace_bytes.restype = C.c_size_t
     _lib.r3dgs_train_stats_workspace_bytes.argtypes = [_i]
@@ -187,7 +193,8 @@ _EXT_FUNCS = ("r3dgs_last_error", "r3dgs_version", "r3dgs_geometry_bytes", "r3dg
               "r3dgs_pass_query", "r3dgs_backward", "r3dgs_mark_visible")
 _EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3dgs_l1_ssim_backward", "r3dgs_l1_workspace_bytes",
                    "r3dgs_l1_forward", "r3dgs_l1_backward",   # optional: an older A/B build has no loss
-                   "r3dgs_adam_step", "r3dgs_adam_step_capturable")   # ... nor a fused Adam
+                   "r3dgs_adam_step", "r3dgs_adam_step_capturable",   # ... nor a fused Adam
+                   "r3dgs_adam_step_visible", "r3dgs_adam_step_capturable_visible")   # ... nor its gated form
 _EXT_PARAMS_FUNCS = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r3dgs_backward_params",
                      "r3dgs_activate_params")   # ... nor the raw-parameter entry points
 _EXT_STATS_FUNCS = ("r3dgs_train_stats_workspace_bytes", "r3dgs_visible_means", "r3dgs_alpha_regul_backward",
@@ -1515,6 +1522,66 @@ def adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scala
                                          *scalars[4 * i:4 * i + 4])
     with _on_device(params[0].device):
         _check(_lib.r3dgs_adam_step_capturable(n, segs, _stream()), "adam_step_capturable")
+    return None
+
+
+def _need_optim_visible():
+    if not hasattr(_lib, "r3dgs_adam_step_visible"):
+        raise RuntimeError(f"{_LIB_PATH} has no visibility-gated Adam (r3dgs_adam_step_visible): rebuild it with build.py")
+
+
+def _row_lens(params, P, what):
+    """Floats per Gaussian of each [P, ...] tensor (the C ABI checks n == P * row_len again)."""
+    out = []
+    for t in params:
+        if t.dim() < 1 or t.shape[0] != P:
+            raise RuntimeError(f"{what}: a tensor of shape {tuple(t.shape)} is not [P, ...] with P = {P}")
+        out.append(t.numel() // P if P else 1)
+    return out
+
+
+def adam_step_visible(params, grads, exp_avgs, exp_avg_sqs, scalars, radii):
+    """adam_step for the Gaussians with radii > 0 only (radii: the rasterizer's device int32 [P]; every tensor [P, ...]).
+    The rows of the others keep their bits and their gradients are not looked at (r3dgs_adam_step_visible)."""
+    _need_optim_visible()
+    if _ext is not None:
+        return _ext.adam_step_visible(params, grads, exp_avgs, exp_avg_sqs, scalars, radii)
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n and len(scalars) == 6 * n):
+        raise RuntimeError("adam_step_visible: list lengths differ")
+    if n == 0:
+        return None
+    P = radii.numel()
+    lens = (_i * n)(*_row_lens(params, P, "adam_step_visible"))
+    segs = (_AdamSegment * n)()
+    for i in range(n):
+        segs[i] = _AdamSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(),
+                               params[i].numel(), *scalars[6 * i:6 * i + 6])
+    with _on_device(params[0].device):
+        _check(_lib.r3dgs_adam_step_visible(n, segs, lens, _ptr(radii), P, _stream()), "adam_step_visible")
+    return None
+
+
+def adam_step_capturable_visible(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars, radii):
+    """adam_step_capturable for the Gaussians with radii > 0 only; radii is read at replay, like steps and lrs."""
+    _need_optim_visible()
+    if _ext is not None:
+        return _ext.adam_step_capturable_visible(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars, radii)
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(lrs) == n and len(scalars) == 4 * n):
+        raise RuntimeError("adam_step_capturable_visible: list lengths differ")
+    if n == 0:
+        return None
+    P = radii.numel()
+    lens = (_i * n)(*_row_lens(params, P, "adam_step_capturable_visible"))
+    segs = (_AdamCapturableSegment * n)()
+    for i in range(n):
+        segs[i] = _AdamCapturableSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(),
+                                         exp_avg_sqs[i].data_ptr(), steps[i].data_ptr(), _ptr(lrs[i]), params[i].numel(),
+                                         *scalars[4 * i:4 * i + 4])
+    with _on_device(params[0].device):
+        _check(_lib.r3dgs_adam_step_capturable_visible(n, segs, lens, _ptr(radii), P, _stream()),
+               "adam_step_capturable_visible")
     return None
 
 

@@ -14,6 +14,23 @@ that are not float32, host, sparse, complex or non-contiguous tensors, a paramet
 a step() during stream capture unless capturable=True.  With capturable=True the step count lives on the device, the kernel
 bumps it and computes the bias corrections from it, and lr may be a 0-d float32 device tensor read at replay; that
 arithmetic is close to torch's capturable step but not bit-identical to it.
+
+The visibility-gated step (opt-in): `step(radii=radii)` with the rasterizer's radii of the view just rendered, an int32,
+contiguous, 1-d device tensor [P], updates only the Gaussians that view rendered.  Every parameter with a gradient must be
+[P, ...].  Row i is visible iff radii[i] > 0 (zero and negative are both invisible).
+
+  * a visible row takes exactly the dense step's arithmetic (the same csrc/adam_math.h function) with this step's scalars;
+  * an invisible row keeps the bits of its parameter, exp_avg and exp_avg_sq, and its gradient is not looked at: NaN or
+    Inf there reaches nothing;
+  * state['step'] is one count per tensor, bumped once per step() whatever was visible, and the bias corrections come
+    from it -- torch.optim.SparseAdam's row semantics; state keys, lazy initialisation and checkpoints are unchanged;
+  * with every row visible the result equals step() without radii bit for bit, plain and capturable; with capturable=True
+    radii is read at replay, so a captured graph follows new contents of the same buffer.
+
+This is NOT the dense step's arithmetic where a view culls: under torch.optim.Adam a culled row (g = 0) still decays exp_avg
+and exp_avg_sq and still moves the parameter on its momentum; here it does neither.  Training results therefore differ from
+the reference's default optimizer (official 3DGS offers the same trade as --optimizer_type sparse_adam).  No 30k-iteration
+PSNR comparison exists for either optimizer with this rasterizer.  step() without radii stays the default and is unchanged.
 """
 import torch
 
@@ -56,6 +73,32 @@ def _check_tensor(what, t, p):
         raise RuntimeError(f"r3dgs_optim.Adam: {what} is not contiguous; the fused step takes contiguous tensors only")
 
 
+def _check_radii(radii, param_groups):
+    """The gated step's own refusals, each naming its offender, before any state is made or any count bumped."""
+    if not isinstance(radii, torch.Tensor):
+        raise TypeError(f"r3dgs_optim.Adam: radii is a {type(radii).__name__}; the gated step takes the rasterizer's int32 "
+                        "tensor")
+    if radii.dtype != torch.int32:
+        raise RuntimeError(f"r3dgs_optim.Adam: radii is {radii.dtype}; the gated step takes the rasterizer's int32 radii")
+    if radii.dim() != 1:
+        raise RuntimeError(f"r3dgs_optim.Adam: radii has shape {tuple(radii.shape)}; the gated step takes a 1-d tensor [P]")
+    if not radii.is_contiguous():
+        raise RuntimeError("r3dgs_optim.Adam: radii is not contiguous; the gated step takes a contiguous tensor only")
+    for gi, group in enumerate(param_groups):
+        for pi, p in enumerate(group["params"]):
+            if p.grad is not None and (p.dim() < 1 or p.shape[0] != radii.numel()):
+                name = group.get("name")
+                what = f"parameter {pi} of group {gi}" + (f" ({name!r})" if name is not None else "")
+                raise RuntimeError(f"r3dgs_optim.Adam: {what} has shape {tuple(p.shape)}, but radii has {radii.numel()} "
+                                   "rows; the gated step needs every parameter as [P, ...] with P == radii.numel()")
+    if not radii.is_cuda:
+        raise RuntimeError("r3dgs_optim.Adam: radii is a host tensor; the gated step needs a device tensor (no CPU path)")
+    for group in param_groups:
+        for p in group["params"]:
+            if p.grad is not None and p.device != radii.device:
+                raise RuntimeError(f"r3dgs_optim.Adam: radii is on {radii.device}, a parameter on {p.device}")
+
+
 class Adam(torch.optim.Optimizer):
     """torch.optim.Adam's interface and default step, fused into one HIP launch per step (see the module docstring)."""
 
@@ -89,12 +132,16 @@ class Adam(torch.optim.Optimizer):
         _check_group(self.param_groups[-1])
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, radii=None):
+        """One step; with radii (the rasterizer's int32 [P] of the view just rendered) only the rows with radii > 0 are
+        updated and the others keep their bits (see the module docstring)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if radii is not None:
+            _check_radii(radii, self.param_groups)
         plain, capt = {}, {}   # device -> the launch's lists
         bumps = []             # (state['step'], its bumped value): stored once every tensor has passed its checks
         for group in self.param_groups:
@@ -156,9 +203,15 @@ class Adam(torch.optim.Optimizer):
         for step_t, bumped in bumps:
             step_t.copy_(bumped)
         for params, grads, ms, vs, scalars in plain.values():
-            _C.adam_step(params, grads, ms, vs, scalars)
+            if radii is None:
+                _C.adam_step(params, grads, ms, vs, scalars)
+            else:
+                _C.adam_step_visible(params, grads, ms, vs, scalars, radii)
         for params, grads, ms, vs, steps, lrs, scalars in capt.values():
-            _C.adam_step_capturable(params, grads, ms, vs, steps, lrs, scalars)
+            if radii is None:
+                _C.adam_step_capturable(params, grads, ms, vs, steps, lrs, scalars)
+            else:
+                _C.adam_step_capturable_visible(params, grads, ms, vs, steps, lrs, scalars, radii)
         return loss
 
 

@@ -5,6 +5,7 @@ synth_scene workload's Gaussian count.  Prints one JSON line per workload.
 
     python tools/adam_bench.py [--workload metric_500k_1600x1062 ...] [--iters 50] [--steps 20] [--only hip|foreach|fused]
                                [--no-train]
+    python tools/adam_bench.py --visible [--visible-out profiles/visible_adam_bench.jsonl] [--workload ...] [--iters 50]
 
 Measured per workload:
   * step_ms.{foreach,fused,hip}: one optimizer step (device events around --iters steps; the three forms alternated in
@@ -13,6 +14,11 @@ Measured per workload:
   * train_it_s.{foreach,fused,hip}: a training iteration -- render + backward of bench.py's train_step with the loss
     r3dgs_loss.l1_dssim against a seeded target, then the optimizer step over the rasterizer's five leaves -- alternated the
     same way.
+With --visible the legs of the visibility-gated step run instead (r3dgs_optim.Adam.step(radii=...)): per workload's Gaussian
+count, visible fractions 1.0, 0.5 and 0.25, each drawn independently per Gaussian and in runs of 64 consecutive Gaussians;
+the dense and the gated step of one optimizer alternate in blocks of --iters within the process, --rounds times.  One JSON
+line per leg, printed and appended to --visible-out: the medians, every block, the dense step's own spread over the
+alternations, and the byte estimate dense * (1 - 0.76 (1 - fraction)) of DESIGN.md 13.
 Kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/adam_bench.py --only hip --no-train` run.
 The GPU is required; there is no CPU fallback."""
 import argparse
@@ -73,6 +79,44 @@ def step_bench(P, names, args, dev):
     return n_params, ms
 
 
+VISIBLE_FRACTIONS = (1.0, 0.5, 0.25)
+VISIBLE_PATTERNS = {"independent": 1, "runs64": 64}   # Gaussians per run that share one draw
+REST_SHARE = 0.76   # f_rest's 45 of the 59 floats: rows long enough that a culled row's lines are skipped whole
+
+
+def visible_radii(P, fraction, run, gen, dev):
+    draws = torch.rand((P + run - 1) // run, device=dev, generator=gen) < fraction
+    return torch.where(draws.repeat_interleave(run)[:P], 7, 0).to(torch.int32).contiguous()
+
+
+def visible_bench(P, args, dev):
+    """The gated step against the dense one on the six reference groups at P Gaussians: yields one leg per fraction and
+    pattern.  Both forms step the same optimizer (fixed random gradients), alternating in blocks of --iters."""
+    gen = torch.Generator(device=dev).manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn((P,) + shape, device=dev, generator=gen)) for _, shape, _ in adam_ref.GROUPS]
+    for p in params:
+        p.grad = torch.randn(p.shape, device=dev, generator=gen) * 1e-3
+    opt = FORMS["hip"]([{"params": [p], "lr": lr, "name": n} for p, (n, _, lr) in zip(params, adam_ref.GROUPS)])
+    n_params = sum(p.numel() for p in params)
+    for fraction in VISIBLE_FRACTIONS:
+        for pattern, run in VISIBLE_PATTERNS.items():
+            radii = visible_radii(P, fraction, run, gen, dev)
+            forms = {"dense": opt.step, "gated": lambda: opt.step(radii=radii)}
+            for body in forms.values():
+                for _ in range(5):
+                    body()
+            ms = {k: [] for k in forms}
+            for _ in range(args.rounds):
+                for name, body in forms.items():
+                    ms[name].append(timed(body, args.iters))
+            dense, gated = (float(np.median(ms[k])) for k in ("dense", "gated"))
+            yield {"metric": "adam_step_visible", "gaussians": P, "params": n_params, "fraction": fraction,
+                   "pattern": pattern, "visible": int((radii > 0).sum()) / P, "step_ms": {"dense": dense, "gated": gated},
+                   "step_ms_all": ms, "dense_spread_ms": float(max(ms["dense"]) - min(ms["dense"])),
+                   "gated_over_dense": gated / dense, "byte_estimate_ms": dense * (1 - REST_SHARE * (1 - fraction)),
+                   "iters": args.iters, "rounds": args.rounds}
+
+
 def train_bench(w, cam, g, names, args, dev):
     import diff_gaussian_rasterization as dgr
 
@@ -118,6 +162,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="alternations of the forms")
     ap.add_argument("--only", choices=list(FORMS), default=None, help="one form only (for a profiler run)")
     ap.add_argument("--no-train", action="store_true", help="optimizer steps only")
+    ap.add_argument("--visible", action="store_true", help="the legs of the visibility-gated step instead")
+    ap.add_argument("--visible-out", default=os.path.join(ROOT, "profiles", "visible_adam_bench.jsonl"),
+                    help="with --visible: the file each leg's JSON line is appended to")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("adam_bench.py needs a GPU")
@@ -125,6 +172,16 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     names = [args.only] if args.only else list(FORMS)
+    if args.visible:
+        with open(args.visible_out, "a") as f:
+            for wl in args.workload:
+                for leg in visible_bench(ss.WORKLOADS[wl]["P"], args, dev):
+                    line = json.dumps({"workload": wl, **leg})
+                    print(line, flush=True)
+                    f.write(line + "\n")
+                    f.flush()
+                torch.cuda.empty_cache()
+        return
     for wl in args.workload:
         w, cam, g = ss.make_workload(wl, seed=0)
         P = w["P"]
