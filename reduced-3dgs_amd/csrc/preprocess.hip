@@ -291,10 +291,19 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
 // SH -> RGB (forward.cu:105-159, ragged variant :19-100) or copy of the precomputed colours into the
 // records of the visible Gaussians.  Streams the SH tensor (192 B per Gaussian at degree 3): the wave's 64 rows
 // are one contiguous span, staged through LDS with dwordx4 loads, evaluated per lane from LDS.
-// Launched as a SMALL persistent grid (launch_preprocess_color): the kernel is bandwidth-bound filler next to the
+// Launched as a SMALL persistent grid (issue_preprocess_color): the kernel is bandwidth-bound filler next to the
 // latency-bound depth-sort kernels of the main stream, and a full grid's LDS footprint (3 x 49 KB per CU) left their
 // workgroups no room -- the depth scatter kernel took 46 us instead of 14 us beside it.
 constexpr size_t kColorLds = sizeof(float) * (kPreBlock / 64) * kWaveShFloats;
+
+// the colour roles' epilogue: rgb and the clamp bits into the record of a visible Gaussian
+__device__ __forceinline__ void store_color(GRec* r, const float* rgb, uint32_t cbits)
+{
+    r->r = rgb[0];
+    r->g = rgb[1];
+    r->b = rgb[2];
+    if (cbits) r->width_clamp |= cbits << 16;  // same lane wrote the width in the geometry kernel
+}
 
 // chunks [first + wg, last) in steps of n_wg, BLOCK Gaussians each (BLOCK = workgroup size, always kPreBlock); smem: BLOCK / 64
 // wave windows.
@@ -393,11 +402,7 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
             rgb[1] = a.in.colors_precomp[3 * i + 1];
             rgb[2] = a.in.colors_precomp[3 * i + 2];
         }
-        GRec* r = a.rec + i;
-        r->r = rgb[0];
-        r->g = rgb[1];
-        r->b = rgb[2];
-        if (cbits) r->width_clamp |= cbits << 16;  // same lane wrote the width in the geometry kernel
+        store_color(a.rec + i, rgb, cbits);
     }
     __syncthreads();   // the staging buffer is reused by the next round
   }
@@ -509,11 +514,7 @@ __device__ __forceinline__ void color_role_quant(const PreArgs& a, const QuantIn
         quant_xyz(qi.xyz, qi.xyz_is_half, i, m);
         sh_to_rgb(deg, ShRowQuantLds{reinterpret_cast<const uint8_t*>(s_ids[wave]), roff, s_books}, m[0], m[1], m[2], campos, rgb,
                   &cbits);
-        GRec* r = a.rec + i;
-        r->r = rgb[0];
-        r->g = rgb[1];
-        r->b = rgb[2];
-        if (cbits) r->width_clamp |= cbits << 16;  // same lane wrote the width in the geometry kernel
+        store_color(a.rec + i, rgb, cbits);
     }
     __syncthreads();   // the id window is reused by the next round
   }
@@ -628,68 +629,50 @@ void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs
         hipLaunchKernelGGL(preprocess_geom_kernel<0>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
 }
 
+// ---- the colour sources -----------------------------------------------------------------------------------------------
+// Everything that depends on where the colours come from, as data: the three depth-sort launches that carry the source's
+// colour role, its stand-alone colour kernel (one argument: the pass block's address -- PreArgs is the block's first
+// member, so the kernels that take a PreArgs* get the same value) and the dynamic LDS that role needs.
+struct ColorSource {
+    void (*sort_step[3])(const FwdPassArgs*, int, int, int);
+    const void* color;
+    size_t color_lds;
+};
+
+static const ColorSource kColorSources[4] = {
+    // activated tensors, dense SH [P,M,3]
+    {{depth_sort_color_kernel<0, false>, depth_sort_color_kernel<1, false>, depth_sort_color_kernel<2, false>},
+     reinterpret_cast<const void*>(preprocess_color_kernel<false, kPreBlock>), kColorLds},
+    // activated tensors, ragged degree-sorted SH buffer
+    {{depth_sort_color_kernel<0, true>, depth_sort_color_kernel<1, true>, depth_sort_color_kernel<2, true>},
+     reinterpret_cast<const void*>(preprocess_color_kernel<true, kPreBlock>), kColorLds},
+    // raw parameters: the two SH tensors
+    {{depth_sort_color_params_kernel<0>, depth_sort_color_params_kernel<1>, depth_sort_color_params_kernel<2>},
+     reinterpret_cast<const void*>(preprocess_color_params_kernel<kPreBlock>), kColorLds},
+    // quantised model (kQuantColorLds: 29 KB)
+    {{depth_sort_color_quant_kernel<0>, depth_sort_color_quant_kernel<1>, depth_sort_color_quant_kernel<2>},
+     reinterpret_cast<const void*>(preprocess_color_quant_kernel<kPreBlock>), kQuantColorLds},
+};
+
+static const ColorSource& color_source(const FwdPlan& p)
+{
+    return kColorSources[p.quant ? 3 : p.raw_params ? 2 : p.ragged ? 1 : 0];
+}
+
 void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s)
 {
     const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
     const int grid = p.color_grid > 0 && blocks > p.color_grid ? p.color_grid : blocks;
-    if (p.quant) {
-        const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
-        hipLaunchKernelGGL((preprocess_color_quant_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), kQuantColorLds, s, pa);
-    } else if (p.raw_params) {
-        const FwdPassArgs* pa = reinterpret_cast<const FwdPassArgs*>(a);   // `a` is the block's first member
-        hipLaunchKernelGGL((preprocess_color_params_kernel<kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, pa);
-    } else if (p.ragged) {
-        hipLaunchKernelGGL((preprocess_color_kernel<true, kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, a);
-    } else {
-        hipLaunchKernelGGL((preprocess_color_kernel<false, kPreBlock>), dim3(grid), dim3(kPreBlock), kColorLds, s, a);
-    }
-}
-
-template <int STEP, bool RAGGED>
-static void launch_sort_color(const FwdPassArgs* pa, int n_sort, int n_color, int c0, int c1, size_t lds, hipStream_t s)
-{
-    hipLaunchKernelGGL((depth_sort_color_kernel<STEP, RAGGED>), dim3(n_sort + n_color), dim3(kPreBlock), lds, s, pa,
-                       n_sort, c0, c1);
-}
-
-template <int STEP>
-static void launch_sort_color_params(const FwdPassArgs* pa, int n_sort, int n_color, int c0, int c1, size_t lds, hipStream_t s)
-{
-    hipLaunchKernelGGL((depth_sort_color_params_kernel<STEP>), dim3(n_sort + n_color), dim3(kPreBlock), lds, s, pa, n_sort,
-                       c0, c1);
-}
-
-template <int STEP>
-static void launch_sort_color_quant(const FwdPassArgs* pa, int n_sort, int n_color, int c0, int c1, size_t lds, hipStream_t s)
-{
-    hipLaunchKernelGGL((depth_sort_color_quant_kernel<STEP>), dim3(n_sort + n_color), dim3(kPreBlock), lds, s, pa, n_sort, c0,
-                       c1);
+    const ColorSource& src = color_source(p);
+    void* args[] = {&a};
+    (void)hipLaunchKernel(src.color, dim3(grid), dim3(kPreBlock), args, src.color_lds, s);
 }
 
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
-template <int STEP, bool RAGGED>
-static void opt_in_lds(size_t bytes)
+static void opt_in_lds(const void* kernel, size_t bytes)
 {
-    if (bytes > 48 * 1024)
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_kernel<STEP, RAGGED>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
-template <int STEP>
-static void opt_in_lds_params(size_t bytes)
-{
-    if (bytes > 48 * 1024)
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_params_kernel<STEP>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
-template <int STEP>
-static void opt_in_lds_quant(size_t bytes)
-{
-    if (bytes > 48 * 1024)
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(depth_sort_color_quant_kernel<STEP>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (bytes > 48 * 1024) R3_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
 // Not a stream operation: called before a chain is captured / issued.  hipFuncSetAttribute applies to the CURRENT
@@ -703,28 +686,12 @@ void prepare_depth_bucket_sort(int nb)
     R3_HIP(hipGetDevice(&dev));
     int& prepared_nb = prepared[dev];
     if (nb <= prepared_nb) return;
-    const size_t h = max_sz(depth_hist_lds(nb), kColorLds), sc = max_sz(depth_scatter_lds(nb), kColorLds),
-                 bs = max_sz(kBucketSortLds, kColorLds);
-    opt_in_lds<0, false>(h);
-    opt_in_lds<0, true>(h);
-    opt_in_lds<1, false>(sc);
-    opt_in_lds<1, true>(sc);
-    opt_in_lds<2, false>(bs);
-    opt_in_lds<2, true>(bs);
-    opt_in_lds_params<0>(h);
-    opt_in_lds_params<1>(sc);
-    opt_in_lds_params<2>(bs);
-    // the quantised colour role needs kQuantColorLds (29 KB): its launches take the sort role's size or that
-    opt_in_lds_quant<0>(max_sz(depth_hist_lds(nb), kQuantColorLds));
-    opt_in_lds_quant<1>(max_sz(depth_scatter_lds(nb), kQuantColorLds));
-    opt_in_lds_quant<2>(max_sz(kBucketSortLds, kQuantColorLds));
-    if (kColorLds > 48 * 1024) {
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<false, kPreBlock>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_kernel<true, kPreBlock>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
-        R3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_color_params_kernel<kPreBlock>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColorLds));
+    // a launch takes its sort role's size or the colour role's, whichever is larger
+    const size_t sort_lds[3] = {depth_hist_lds(nb), depth_scatter_lds(nb), kBucketSortLds};
+    for (const ColorSource& src : kColorSources) {
+        for (int k = 0; k < 3; k++)
+            opt_in_lds(reinterpret_cast<const void*>(src.sort_step[k]), max_sz(sort_lds[k], src.color_lds));
+        opt_in_lds(src.color, src.color_lds);
     }
     prepared_nb = nb;
 }
@@ -740,34 +707,18 @@ void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStre
     c[1] = (int)((long long)chunks * p.color_split[0] / 100);
     c[2] = c[1] + (int)((long long)chunks * p.color_split[1] / 100);
     const int cw = p.color_grid > 0 ? p.color_grid : 512;
-    auto n_color = [&](int k) { const int n = c[k + 1] - c[k]; return n < cw ? n : cw; };
-    const size_t lds0 = n_color(0) ? max_sz(depth_hist_lds(nb), kColorLds) : depth_hist_lds(nb);
-    const size_t lds1 = n_color(1) ? max_sz(depth_scatter_lds(nb), kColorLds) : depth_scatter_lds(nb);
-    const size_t lds2 = n_color(2) ? max_sz(kBucketSortLds, kColorLds) : kBucketSortLds;
-    if (p.quant) {
-        const size_t q0 = n_color(0) ? max_sz(depth_hist_lds(nb), kQuantColorLds) : depth_hist_lds(nb);
-        const size_t q1 = n_color(1) ? max_sz(depth_scatter_lds(nb), kQuantColorLds) : depth_scatter_lds(nb);
-        const size_t q2 = n_color(2) ? max_sz(kBucketSortLds, kQuantColorLds) : kBucketSortLds;
-        launch_sort_color_quant<0>(pa, rows, n_color(0), c[0], c[1], q0, s);
-        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
-        launch_sort_color_quant<1>(pa, rows, n_color(1), c[1], c[2], q1, s);
-        launch_sort_color_quant<2>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], q2, s);
-    } else if (p.raw_params) {
-        launch_sort_color_params<0>(pa, rows, n_color(0), c[0], c[1], lds0, s);
-        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
-        launch_sort_color_params<1>(pa, rows, n_color(1), c[1], c[2], lds1, s);
-        launch_sort_color_params<2>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], lds2, s);
-    } else if (p.ragged) {
-        launch_sort_color<0, true>(pa, rows, n_color(0), c[0], c[1], lds0, s);
-        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
-        launch_sort_color<1, true>(pa, rows, n_color(1), c[1], c[2], lds1, s);
-        launch_sort_color<2, true>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], lds2, s);
-    } else {
-        launch_sort_color<0, false>(pa, rows, n_color(0), c[0], c[1], lds0, s);
-        hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
-        launch_sort_color<1, false>(pa, rows, n_color(1), c[1], c[2], lds1, s);
-        launch_sort_color<2, false>(pa, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup, n_color(2), c[2], c[3], lds2, s);
-    }
+    const ColorSource& src = color_source(p);
+    const int n_sort[3] = {rows, rows, (nb + kBucketsPerGroup - 1) / kBucketsPerGroup};
+    const size_t sort_lds[3] = {depth_hist_lds(nb), depth_scatter_lds(nb), kBucketSortLds};
+    auto step = [&](int k) {
+        const int n_color = c[k + 1] - c[k] < cw ? c[k + 1] - c[k] : cw;
+        const size_t lds = n_color ? max_sz(sort_lds[k], src.color_lds) : sort_lds[k];
+        hipLaunchKernelGGL(src.sort_step[k], dim3(n_sort[k] + n_color), dim3(kPreBlock), lds, s, pa, n_sort[k], c[k], c[k + 1]);
+    };
+    step(0);
+    hipLaunchKernelGGL(depth_colscan_kernel, dim3((nb + 1 + 63) / 64), dim3(64 * kColWaves), 0, s, &pa->depth);
+    step(1);
+    step(2);
 }
 
 // rasterizer_impl.cu:62-74 checkFrustum: present[i] = (view * p).z > 0.2

@@ -163,7 +163,7 @@ Tensor dev_i32(const Tensor& t, const c10::Device& dev)
     return t.contiguous();
 }
 
-void* cur_stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+void* cur_stream(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
 
 std::mutex g_mu;
 std::map<std::tuple<int, int, int, int, int>, size_t> g_sizes;   // (kind, a, b, c, d) -> bytes
@@ -187,11 +187,47 @@ size_t blob_bytes(int kind, int a, int b = 0, int c = 0, int d = 0)
     return v;
 }
 
-// RasterizeGaussiansCUDA (rasterize_points.cu:136-222) on the asynchronous path.
-// -> (ticket, reserve, num_rendered, flags, out_color, radii, geom, binning, img).  ticket == 0: nothing is known about
-// this view size yet -- the caller takes the exact-size path.  num_rendered / flags are filled (>= 0) when `strict`: the
-// call then waited for the pass's HEADER (not for the pass), with the GIL released.
-std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_reserved(
+using ReservedPass = std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// What the reserved forwards share behind their argument checks (the caller holds the device guard): the hint, the pair
+// reservation (`reserve_override` > 0: a chosen one), out_color / radii and the three blobs, the entry point --
+// call(geom, binning, img, reserve, out_color, radii, stream) -> ticket -- and, when `strict`, the wait for the pass's HEADER
+// (not for the pass) with the GIL released.  `what` names the caller in errors.
+// -> (ticket, reserve, num_rendered, flags, out_color, radii, geom, binning, img).  ticket == 0: nothing is known about this
+// view size yet -- the caller takes the exact-size path.  num_rendered / flags are filled (>= 0) when `strict`.
+template <class Call>
+ReservedPass reserved_pass(const char* what, const c10::Device& dev, int P, int W, int H, const Tensor& vm, bool trains, bool lean,
+                           bool strict, int64_t reserve_override, Call&& call)
+{
+    api.r3dgs_forward_hint(trains ? 1 : 0);
+    const int reserve = reserve_override > 0 ? (int)reserve_override : api.r3dgs_reserve_hint_view(P, W, H, opt_ptr<float>(vm));
+    if (reserve < 0) fail(what);
+    Tensor none;
+    if (reserve == 0 || P == 0) return {0LL, 0, -1, 0, none, none, none, none, none};
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev), i32 = f32.dtype(at::kInt), u8 = f32.dtype(at::kByte);
+    Tensor out_color = at::empty({3, H, W}, f32), radii = at::empty({P}, i32);
+    Tensor geom = at::empty({(int64_t)blob_bytes(lean ? 1 : 0, P)}, u8);
+    Tensor binning = at::empty({(int64_t)blob_bytes(2, P, W, H, reserve)}, u8);
+    Tensor img = at::empty({(int64_t)blob_bytes(3, W, H)}, u8);
+    const long long ticket = call(reinterpret_cast<char*>(geom.data_ptr()), reinterpret_cast<char*>(binning.data_ptr()),
+                                  reinterpret_cast<char*>(img.data_ptr()), reserve, out_color.data_ptr<float>(),
+                                  radii.data_ptr<int>(), cur_stream(dev));
+    if (ticket < 0) fail(what);
+    int rendered = -1, flags = 0;
+    if (strict && ticket > 0) {
+        int visible = 0, cap = 0, st;
+        {
+            pybind11::gil_scoped_release nogil;   // a poll of host memory with short sleeps inside the library
+            st = api.r3dgs_pass_query(ticket, 1, &rendered, &visible, &cap, &flags);
+        }
+        if (st < 0) fail("num_rendered");
+        if (st != 1) rendered = -1;
+    }
+    return {ticket, reserve, rendered, flags, out_color, radii, geom, binning, img};
+}
+
+// RasterizeGaussiansCUDA (rasterize_points.cu:136-222) on the asynchronous path -> as reserved_pass
+ReservedPass forward_reserved(
     const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
     const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrix,
     const Tensor& projmatrix, double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& sh,
@@ -208,37 +244,16 @@ std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor> for
     const Tensor cov = dev_f32(cov3D_precomp, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
     const Tensor cp = dev_f32(campos, dev), shc = dev_f32(sh, dev), deg = dev_i32(degrees, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    api.r3dgs_forward_hint(trains ? 1 : 0);
-    const int reserve = api.r3dgs_reserve_hint_view(P, W, H, opt_ptr<float>(vm));
-    if (reserve < 0) fail("rasterize_gaussians");
-    Tensor none;
-    if (reserve == 0) return {0LL, 0, -1, 0, none, none, none, none, none};
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev), i32 = f32.dtype(at::kInt), u8 = f32.dtype(at::kByte);
-    Tensor out_color = at::empty({3, H, W}, f32), radii = at::empty({P}, i32);
     const bool lean = !trains || !shc.defined() || col.defined();   // no SH direction derivatives will be left
-    Tensor geom = at::empty({(int64_t)blob_bytes(lean ? 1 : 0, P)}, u8);
-    Tensor binning = at::empty({(int64_t)blob_bytes(2, P, W, H, reserve)}, u8);
-    Tensor img = at::empty({(int64_t)blob_bytes(3, W, H)}, u8);
-    void* stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
     const int M = shc.defined() ? (int)shc.size(1) : 0;
-    const long long ticket = api.r3dgs_forward_reserved(
-        reinterpret_cast<char*>(geom.data_ptr()), reinterpret_cast<char*>(binning.data_ptr()),
-        reinterpret_cast<char*>(img.data_ptr()), reserve, P, opt_ptr<int>(deg), M, opt_ptr<float>(bg), W, H, opt_ptr<float>(m3),
-        opt_ptr<float>(shc), opt_ptr<float>(col), opt_ptr<float>(op), opt_ptr<float>(sc), (float)scale_modifier,
-        opt_ptr<float>(rot), opt_ptr<float>(cov), opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx,
-        (float)tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), nullptr, nullptr, radii.data_ptr<int>(), 0, 0, stream);
-    if (ticket < 0) fail("rasterize_gaussians");
-    int rendered = -1, flags = 0;
-    if (strict && ticket > 0) {
-        int visible = 0, cap = 0, st;
-        {
-            pybind11::gil_scoped_release nogil;   // a poll of host memory with short sleeps inside the library
-            st = api.r3dgs_pass_query(ticket, 1, &rendered, &visible, &cap, &flags);
-        }
-        if (st < 0) fail("num_rendered");
-        if (st != 1) rendered = -1;
-    }
-    return {ticket, reserve, rendered, flags, out_color, radii, geom, binning, img};
+    return reserved_pass("rasterize_gaussians", dev, P, W, H, vm, trains, lean, strict, 0,
+                         [&](char* geom, char* binning, char* img, int reserve, float* out_color, int* radii, void* stream) {
+        return api.r3dgs_forward_reserved(
+            geom, binning, img, reserve, P, opt_ptr<int>(deg), M, opt_ptr<float>(bg), W, H, opt_ptr<float>(m3), opt_ptr<float>(shc),
+            opt_ptr<float>(col), opt_ptr<float>(op), opt_ptr<float>(sc), (float)scale_modifier, opt_ptr<float>(rot),
+            opt_ptr<float>(cov), opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy,
+            prefiltered ? 1 : 0, out_color, nullptr, nullptr, radii, 0, 0, stream);
+    });
 }
 
 // RasterizeGaussiansBackwardCUDA (rasterize_points.cu:224-305).  `capacity`: the pair capacity the forward carved the
@@ -341,8 +356,8 @@ ParamPtrs check_params(const Tensor& xyz, const Tensor& features_dc, const Tenso
     return p;
 }
 
-// -> as forward_reserved: (ticket, reserve, num_rendered, flags, out_color, radii, geom, binning, img)
-std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_params_reserved(
+// -> as reserved_pass
+ReservedPass forward_params_reserved(
     const Tensor& background, const Tensor& xyz, const Tensor& features_dc, const Tensor& features_rest, const Tensor& degrees,
     const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, double scale_modifier, const Tensor& viewmatrix,
     const Tensor& projmatrix, double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& campos,
@@ -355,34 +370,13 @@ std::tuple<long long, int, int, int, Tensor, Tensor, Tensor, Tensor, Tensor> for
     const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
     const Tensor cp = dev_f32(campos, dev), deg = dev_i32(degrees, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    api.r3dgs_forward_hint(trains ? 1 : 0);
-    const int reserve = reserve_override > 0 ? (int)reserve_override : api.r3dgs_reserve_hint_view(P, W, H, opt_ptr<float>(vm));
-    if (reserve < 0) fail("rasterize_gaussian_params");
-    Tensor none;
-    if (reserve == 0 || P == 0) return {0LL, 0, -1, 0, none, none, none, none, none};
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev), i32 = f32.dtype(at::kInt), u8 = f32.dtype(at::kByte);
-    Tensor out_color = at::empty({3, H, W}, f32), radii = at::empty({P}, i32);
-    Tensor geom = at::empty({(int64_t)blob_bytes(trains ? 0 : 1, P)}, u8);
-    Tensor binning = at::empty({(int64_t)blob_bytes(2, P, W, H, reserve)}, u8);
-    Tensor img = at::empty({(int64_t)blob_bytes(3, W, H)}, u8);
-    const long long ticket = api.r3dgs_forward_params_reserved(
-        reinterpret_cast<char*>(geom.data_ptr()), reinterpret_cast<char*>(binning.data_ptr()),
-        reinterpret_cast<char*>(img.data_ptr()), reserve, P, opt_ptr<int>(deg), p.M, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest,
-        p.opacity, p.scaling, (float)scale_modifier, p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp),
-        (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), nullptr, nullptr,
-        radii.data_ptr<int>(), 0, 0, cur_stream_of(dev));
-    if (ticket < 0) fail("rasterize_gaussian_params");
-    int rendered = -1, flags = 0;
-    if (strict && ticket > 0) {
-        int visible = 0, cap = 0, st;
-        {
-            pybind11::gil_scoped_release nogil;
-            st = api.r3dgs_pass_query(ticket, 1, &rendered, &visible, &cap, &flags);
-        }
-        if (st < 0) fail("num_rendered");
-        if (st != 1) rendered = -1;
-    }
-    return {ticket, reserve, rendered, flags, out_color, radii, geom, binning, img};
+    return reserved_pass("rasterize_gaussian_params", dev, P, W, H, vm, trains, !trains, strict, reserve_override,
+                         [&](char* geom, char* binning, char* img, int reserve, float* out_color, int* radii, void* stream) {
+        return api.r3dgs_forward_params_reserved(
+            geom, binning, img, reserve, P, opt_ptr<int>(deg), p.M, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest, p.opacity,
+            p.scaling, (float)scale_modifier, p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp),
+            (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0, out_color, nullptr, nullptr, radii, 0, 0, stream);
+    });
 }
 
 // the exact-size path (r3dgs_forward_params): the three blobs are byte tensors allocated from the library's callbacks
@@ -426,7 +420,7 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_params(
         blob_alloc, &geom, blob_alloc, &binning, blob_alloc, &img, P, opt_ptr<int>(deg), p.M, opt_ptr<float>(bg), W, H, p.xyz, p.dc,
         p.rest, p.opacity, p.scaling, (float)scale_modifier, p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm),
         opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), nullptr, nullptr,
-        radii.data_ptr<int>(), 0, debug ? 1 : 0, cur_stream_of(dev));
+        radii.data_ptr<int>(), 0, debug ? 1 : 0, cur_stream(dev));
     if (geom.failed || binning.failed || img.failed) throw std::runtime_error("rasterize_gaussian_params: a state buffer could not be allocated");
     if (rendered < 0) fail("rasterize_gaussian_params");
     const auto u8 = f32.dtype(at::kByte);
@@ -469,7 +463,7 @@ std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz,
         dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), scratch.data_ptr<float>(),
         dL_dmeans3D.data_ptr<float>(), scratch.data_ptr<float>() + 3 * (size_t)P, dL_ddc.data_ptr<float>(),
         M > 1 ? dL_drest.data_ptr<float>() : nullptr, dL_dscaling.data_ptr<float>(), dL_drotation.data_ptr<float>(),
-        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream_of(dev));
+        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev));
     if (st < 0) fail("rasterize_gaussian_params_backward");
     return {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation};
 }
@@ -488,7 +482,7 @@ std::tuple<Tensor, Tensor> activate_params(const Tensor& scaling, const Tensor& 
     const float* rp = param_ptr(rotation, dev, "rotation");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     Tensor s = at::empty_like(scaling), q = at::empty_like(rotation);
-    if (P && api.r3dgs_activate_params(P, sp, rp, s.data_ptr<float>(), q.data_ptr<float>(), cur_stream_of(dev)) < 0)
+    if (P && api.r3dgs_activate_params(P, sp, rp, s.data_ptr<float>(), q.data_ptr<float>(), cur_stream(dev)) < 0)
         fail("activate_params");
     return {s, q};
 }
@@ -519,8 +513,6 @@ void need_loss()
     need_bound();
     if (!api.r3dgs_l1_ssim_forward) throw std::runtime_error("the loaded libr3dgs_hip.so has no fused loss: rebuild it with build.py");
 }
-
-void* cur_stream(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> l1_ssim_forward(
     const Tensor& img1, const Tensor& img2, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials,

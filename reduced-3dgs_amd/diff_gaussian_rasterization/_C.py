@@ -533,6 +533,77 @@ def _forget_view(ptr, ident):
         pass
 
 
+def _empty_forward(dev, H, W):
+    """The forward's result for P == 0: a black image, nothing rendered, empty state."""
+    e = torch.empty(0, dtype=torch.uint8, device=dev)
+    return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+            torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+
+
+def _pair_capacity(R, P, W, H, binningBuffer):
+    """The pair capacity the forward carved the binning blob with: R says (a NumRendered), or -- R a plain int from an older
+    caller -- what the blob's size implies."""
+    if isinstance(R, NumRendered):
+        return R.capacity
+    return _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+
+
+def _reserved_result(strict, ticket, reserve, rendered, flags, out_color, radii, geom, binning, img):
+    """A pass issued on a reservation (either binding; rendered < 0: not fetched yet) -> the forward's six-tuple, or None:
+    strict mode found the pass truncated and the caller redoes it on the exact-size path."""
+    nr = NumRendered(ticket, reserve, rendered if rendered >= 0 else None)
+    nr._flags = flags
+    _stats["reserved_passes"] += 1
+    if not strict:
+        _watch_overflow()
+        return nr, out_color, radii, geom, binning, img
+    if not nr.truncated:   # waits for the pass's header (not for the pass)
+        return nr, out_color, radii, geom, binning, img
+    _stats["redone_passes"] += 1
+    return None
+
+
+def _exact_result(rendered, out_color, radii, geom, binning, img):
+    """An exact-size pass -> the forward's six-tuple."""
+    _stats["exact_passes"] += 1
+    pairs = int(_lib.r3dgs_forward_pairs())   # pairs actually binned (<= num_rendered, what the blob was carved for)
+    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom, binning, img
+
+
+def _drive_forward(fn_exact, fn_reserved, args, what, dev, P, W, H, vm_ptr, lean, counters, out_color, radii, exact, debug,
+                   _reserve, strict):
+    """The ctypes forward of every source, called with `dev` current: `args` is what the source's two entry points take
+    behind the blobs (the pointers of out_color, radii and the counters among them), `what` names the caller in errors.
+    Asynchronous path: blobs sized up front from a pair reservation, one graph launch, no wait for the pass.  The
+    exact-size path (allocator callbacks, one wait in the middle) runs when nothing is known about this view size yet, in
+    debug mode, when asked for -- and to redo a pass that overflowed its reservation (strict mode)."""
+    reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, vm_ptr)
+    if _reserve is not None:   # tests: a chosen reservation
+        reserve = int(_reserve)
+    if reserve > 0:
+        u8 = dict(dtype=torch.uint8, device=dev)
+        geom = torch.empty(_blob_bytes("geom_lean" if lean else "geom", P), **u8)
+        binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
+        img = torch.empty(_blob_bytes("img", W, H), **u8)
+        ticket = fn_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *args)
+        if ticket < 0:
+            _check(-1, what)
+        out = _reserved_result(strict, ticket, reserve, -1, 0, out_color, radii, geom, binning, img)
+        if out is not None:
+            return out
+        if counters is not None:   # the redo below: counter mode accumulates into its outputs
+            counters[0].zero_()
+            counters[1].zero_()
+        del geom, binning, img
+    geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
+    rendered = fn_exact(geom.cb, None, binning.cb, None, img.cb, None, *args)
+    for blob in (geom, binning, img):
+        if blob.error is not None:   # e.g. torch OOM inside the allocator callback: surface the original exception
+            raise blob.error
+    _check(rendered, what)
+    return _exact_result(rendered, out_color, radii, geom.tensor, binning.tensor, img.tensor)
+
+
 def _forward_common(ragged, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                     viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degrees, campos,
                     prefiltered, debug, counters=None, exact=False, _reserve=None, _strict_override=None):
@@ -542,36 +613,26 @@ def _forward_common(ragged, background, means3D, colors, opacity, scales, rotati
     if dev.type != "cuda":
         raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    u8 = dict(dtype=torch.uint8, device=dev)
     if P == 0:
-        out_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.zeros((0,), dtype=torch.int32, device=dev)
-        e = torch.empty(0, **u8)
-        return NumRendered(0, 0, 0, 0), out_color, radii, e, e.clone(), e.clone()
+        return _empty_forward(dev, H, W)
     hint = getattr(_tls, "next_forward_trains", None)   # per thread, like the library's own r3dgs_forward_hint state
     trains = torch.is_grad_enabled() if hint is None else hint
     _tls.next_forward_trains = None
+    strict = _strict if _strict_override is None else bool(_strict_override)
     if _ext is not None and ragged is None and counters is None and not exact and not debug and _reserve is None:
         # the hot call: compiled marshalling (csrc_torch/r3dgs_torch.cpp), same library entry points as below
-        strict = _strict if _strict_override is None else bool(_strict_override)
         if viewmatrix is not None and viewmatrix.is_contiguous() and viewmatrix.dtype == torch.float32:
             _track_view(viewmatrix)
-        ticket, reserve, rendered, flags, out_color, radii, geom, binning, img = _ext.forward_reserved(
+        res = _ext.forward_reserved(
             _t(background), means3D, _t(colors), _t(opacity), _t(scales), _t(rotations), float(scale_modifier),
             _t(cov3D_precomp), _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy), H, W, _t(sh), _t(degrees),
             _t(campos), bool(prefiltered), bool(trains), strict)
-        if ticket:
-            _stats["reserved_passes"] += 1
-            nr = NumRendered(ticket, reserve, rendered if rendered >= 0 else None)
-            nr._flags = flags
-            if not strict:
-                _watch_overflow()
-                return nr, out_color, radii, geom, binning, img
-            if not nr.truncated:
-                return nr, out_color, radii, geom, binning, img
-            _stats["redone_passes"] += 1   # the reservation did not hold: redo on the exact-size path below
-            del geom, binning, img
-        exact = True   # (ticket == 0: nothing known about this view size yet)
+        if res[0]:
+            out = _reserved_result(strict, *res)
+            if out is not None:
+                return out
+        del res        # the reservation did not hold, or ticket == 0 (nothing known about this view size yet):
+        exact = True   # the exact-size path below
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     bg = _dev_f32(background, dev)
@@ -596,46 +657,12 @@ def _forward_common(ragged, background, means3D, colors, opacity, scales, rotati
             head = (P, _ptr(deg), int(perband.numel()) if perband is not None else 0, _ptr(coeffs), _ptr(perband),
                     _ptr(cumsum))
             fn_exact, fn_reserved = _lib.r3dgs_inference_forward, _lib.r3dgs_inference_forward_reserved
-        # Asynchronous path: blobs sized up front from a pair reservation, one graph launch, no wait for the pass.  The
-        # exact-size path (allocator callbacks, one wait in the middle) runs when nothing is known about this view size
-        # yet, in debug mode, when asked for -- and to redo a pass that overflowed its reservation (strict mode).
         if vm is not None:
             _track_view(vm)
-        reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, _ptr(vm))
-        if _reserve is not None:   # tests: a chosen reservation
-            reserve = int(_reserve)
-        strict = _strict if _strict_override is None else bool(_strict_override)
-        if reserve > 0:
-            # no SH direction derivatives will be left (render-only / ragged SH / precomputed colours): the lean blob
-            lean = not trains or ragged is not None or shc is None or col is not None
-            geom = torch.empty(_blob_bytes("geom_lean" if lean else "geom", P), **u8)
-            binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
-            img = torch.empty(_blob_bytes("img", W, H), **u8)
-            ticket = fn_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *head, *tail)
-            if ticket < 0:
-                _check(-1, "rasterize_gaussians")
-            _stats["reserved_passes"] += 1
-            nr = NumRendered(ticket, reserve)
-            if not strict:
-                _watch_overflow()
-                return nr, out_color, radii, geom, binning, img
-            if not nr.truncated:   # waits for the pass's header (not for the pass)
-                return nr, out_color, radii, geom, binning, img
-            # The reservation did not hold: redo on the exact-size path.  Counter mode accumulates into its outputs.
-            _stats["redone_passes"] += 1
-            if counters is not None:
-                touched.zero_()
-                transm.zero_()
-            del geom, binning, img
-        geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
-        rendered = fn_exact(geom.cb, None, binning.cb, None, img.cb, None, *head, *tail)
-    for blob in (geom, binning, img):
-        if blob.error is not None:   # e.g. torch OOM inside the allocator callback: surface the original exception
-            raise blob.error
-    _check(rendered, "rasterize_gaussians")
-    _stats["exact_passes"] += 1
-    pairs = int(_lib.r3dgs_forward_pairs())   # pairs actually binned (<= num_rendered, what the blob was carved for)
-    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom.tensor, binning.tensor, img.tensor
+        # no SH direction derivatives will be left (render-only / ragged SH / precomputed colours): the lean blob
+        lean = not trains or ragged is not None or shc is None or col is not None
+        return _drive_forward(fn_exact, fn_reserved, head + tail, "rasterize_gaussians", dev, P, W, H, _ptr(vm), lean,
+                              counters, out_color, radii, exact, debug, _reserve, strict)
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -687,10 +714,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         z = lambda *s: torch.zeros(s, **opts)
         return z(0, 3), z(0, 3), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)
     if _ext is not None and _grad_arena is None:
-        if isinstance(R, NumRendered):
-            cap = R.capacity
-        else:
-            cap = _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+        cap = _pair_capacity(R, P, W, H, binningBuffer)
         return tuple(_ext.backward(_t(background), means3D, _t(radii), _t(colors), _t(scales), _t(rotations),
                                    float(scale_modifier), _t(cov3D_precomp), _t(viewmatrix), _t(projmatrix), float(tan_fovx),
                                    float(tan_fovy), dL_dout_color, _t(sh), _t(degrees), _t(campos), geomBuffer, int(cap),
@@ -712,10 +736,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     col, sc, rot, cov = (_dev_f32(t, dev) for t in (colors, scales, rotations, cov3D_precomp))
     vm, pm, cp = _dev_f32(viewmatrix, dev), _dev_f32(projmatrix, dev), _dev_f32(campos, dev)
     g, shc, deg, rad = _dev_f32(dL_dout_color, dev), _dev_f32(sh, dev), _dev_i32(degrees, dev), _dev_i32(radii, dev)
-    if isinstance(R, NumRendered):
-        cap = R.capacity
-    else:   # a plain int from an older caller: the capacity is what the binning buffer was sized with
-        cap = _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+    cap = _pair_capacity(R, P, W, H, binningBuffer)
     with _on_device(dev):
         st = _lib.r3dgs_backward(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sc),
                                  float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp),
@@ -787,11 +808,8 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
     _need_params()
     P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
     H, W = int(image_height), int(image_width)
-    u8 = dict(dtype=torch.uint8, device=dev)
     if P == 0:
-        e = torch.empty(0, **u8)
-        return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
-                torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+        return _empty_forward(dev, H, W)
     hint = getattr(_tls, "next_forward_trains", None)
     trains = torch.is_grad_enabled() if hint is None else hint
     _tls.next_forward_trains = None
@@ -803,23 +821,13 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
         common = (_t(background), xyz, features_dc, rest, degrees, opacity, scaling, rotation, float(scale_modifier),
                   _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy), H, W, _t(campos), bool(prefiltered), bool(trains))
         if not exact and not debug:
-            ticket, reserve, rendered, flags, out_color, radii, geom, binning, img = _ext.forward_params_reserved(
-                *common, strict, int(_reserve or 0))
-            if ticket:
-                _stats["reserved_passes"] += 1
-                nr = NumRendered(ticket, reserve, rendered if rendered >= 0 else None)
-                nr._flags = flags
-                if not strict:
-                    _watch_overflow()
-                    return nr, out_color, radii, geom, binning, img
-                if not nr.truncated:
-                    return nr, out_color, radii, geom, binning, img
-                _stats["redone_passes"] += 1
-                del geom, binning, img
-        rendered, out_color, radii, geom, binning, img = _ext.forward_params(*common, bool(debug))
-        _stats["exact_passes"] += 1
-        pairs = int(_lib.r3dgs_forward_pairs())
-        return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom, binning, img
+            res = _ext.forward_params_reserved(*common, strict, int(_reserve or 0))
+            if res[0]:
+                out = _reserved_result(strict, *res)
+                if out is not None:
+                    return out
+            del res
+        return _exact_result(*_ext.forward_params(*common, bool(debug)))
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
@@ -829,34 +837,8 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
         args = (P, _ptr(deg), M, _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest), _ptr(opacity), _ptr(scaling),
                 float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx), float(tan_fovy),
                 int(bool(prefiltered)), _ptr(out_color), None, None, _ptr(radii), 0, int(bool(debug)), _stream())
-        reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, _ptr(vm))
-        if _reserve is not None:
-            reserve = int(_reserve)
-        if reserve > 0:
-            geom = torch.empty(_blob_bytes("geom" if trains else "geom_lean", P), **u8)
-            binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
-            img = torch.empty(_blob_bytes("img", W, H), **u8)
-            ticket = _lib.r3dgs_forward_params_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *args)
-            if ticket < 0:
-                _check(-1, "rasterize_gaussian_params")
-            _stats["reserved_passes"] += 1
-            nr = NumRendered(ticket, reserve)
-            if not strict:
-                _watch_overflow()
-                return nr, out_color, radii, geom, binning, img
-            if not nr.truncated:
-                return nr, out_color, radii, geom, binning, img
-            _stats["redone_passes"] += 1
-            del geom, binning, img
-        geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
-        rendered = _lib.r3dgs_forward_params(geom.cb, None, binning.cb, None, img.cb, None, *args)
-    for blob in (geom, binning, img):
-        if blob.error is not None:
-            raise blob.error
-    _check(rendered, "rasterize_gaussian_params")
-    _stats["exact_passes"] += 1
-    pairs = int(_lib.r3dgs_forward_pairs())
-    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom.tensor, binning.tensor, img.tensor
+        return _drive_forward(_lib.r3dgs_forward_params, _lib.r3dgs_forward_params_reserved, args, "rasterize_gaussian_params",
+                              dev, P, W, H, _ptr(vm), not trains, None, out_color, radii, exact, debug, _reserve, strict)
 
 
 def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation,
@@ -872,10 +854,7 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
         z = lambda *s: torch.zeros(s, **opts)
         return z(0, 3), z(0, 1), z(0, 3), z(0, 1, 3), z(0, M - 1, 3), z(0, 3), z(0, 4)
     rest = _NO_TENSOR if M == 1 else features_rest
-    if isinstance(R, NumRendered):
-        cap = R.capacity
-    else:
-        cap = _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+    cap = _pair_capacity(R, P, W, H, binningBuffer)
     if _ext is not None:
         return tuple(_ext.backward_params(_t(background), xyz, _t(radii), features_dc, rest, degrees, opacity, scaling, rotation,
                                           float(scale_modifier), _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy),
@@ -972,11 +951,8 @@ def rasterize_gaussians_quantised(background, xyz, geom_ids, sh_ids, codebooks, 
     _need_quantised()
     P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
     H, W = int(image_height), int(image_width)
-    u8 = dict(dtype=torch.uint8, device=dev)
     if P == 0:
-        e = torch.empty(0, **u8)
-        return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
-                torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+        return _empty_forward(dev, H, W)
     _tls.next_forward_trains = None
     strict = _strict if _strict_override is None else bool(_strict_override)
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
@@ -994,37 +970,9 @@ def rasterize_gaussians_quantised(background, xyz, geom_ids, sh_ids, codebooks, 
                 float(scale_modifier), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
                 _ptr(out_color), _ptr(touched), _ptr(transm), _ptr(radii), int(counters is not None), int(bool(debug)),
                 _stream())
-        reserve = 0 if (exact or debug) else _lib.r3dgs_reserve_hint_view(P, W, H, _ptr(vm))
-        if _reserve is not None:
-            reserve = int(_reserve)
-        if reserve > 0:
-            geom = torch.empty(_blob_bytes("geom_lean", P), **u8)
-            binning = torch.empty(_blob_bytes("bin", P, W, H, reserve), **u8)
-            img = torch.empty(_blob_bytes("img", W, H), **u8)
-            ticket = _lib.r3dgs_quantised_forward_reserved(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), reserve, *args)
-            if ticket < 0:
-                _check(-1, "rasterize_gaussians_quantised")
-            _stats["reserved_passes"] += 1
-            nr = NumRendered(ticket, reserve)
-            if not strict:
-                _watch_overflow()
-                return nr, out_color, radii, geom, binning, img
-            if not nr.truncated:
-                return nr, out_color, radii, geom, binning, img
-            _stats["redone_passes"] += 1
-            if counters is not None:   # counter mode accumulates into its outputs
-                touched.zero_()
-                transm.zero_()
-            del geom, binning, img
-        geom, binning, img = _Blob(dev), _Blob(dev), _Blob(dev)
-        rendered = _lib.r3dgs_quantised_forward(geom.cb, None, binning.cb, None, img.cb, None, *args)
-    for blob in (geom, binning, img):
-        if blob.error is not None:
-            raise blob.error
-    _check(rendered, "rasterize_gaussians_quantised")
-    _stats["exact_passes"] += 1
-    pairs = int(_lib.r3dgs_forward_pairs())
-    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom.tensor, binning.tensor, img.tensor
+        return _drive_forward(_lib.r3dgs_quantised_forward, _lib.r3dgs_quantised_forward_reserved, args,
+                              "rasterize_gaussians_quantised", dev, P, W, H, _ptr(vm), True, counters, out_color, radii, exact,
+                              debug, _reserve, strict)
 
 
 def quantised_decode(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum):
@@ -1073,10 +1021,9 @@ def export_binning(P, R, H, W, geomBuffer, binningBuffer, imageBuffer):
     ranges, n_contrib, final T and tiles_touched of a finished forward -- for bit-exact integer parity tests."""
     dev = geomBuffer.device
     gx, gy = (W + 15) // 16, (H + 15) // 16
+    cap = _pair_capacity(R, P, W, H, binningBuffer)
     if isinstance(R, NumRendered):
-        cap, R = R.capacity, R.pairs
-    else:
-        cap = _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
+        R = R.pairs
     R = min(int(R), cap)
     keys = torch.empty((R,), dtype=torch.int64, device=dev)
     plist = torch.empty((R,), dtype=torch.int32, device=dev)

@@ -175,6 +175,35 @@ def test_fused_equals_existing_path(scene_name, lam, path, chain, binding):
         _C.set_f64_chain(was_chain)
 
 
+@pytest.mark.parametrize("binding", ["torch", "ctypes"])
+def test_strict_redo_and_lossy_opt_out(binding):
+    """tests/test_train_loop_gpu.py's test of that name for the raw-parameter forward, at its shape: the same overflowing
+    reservation through strict mode (default: result == exact path, one redo counted) and with strict mode off (farthest
+    pairs dropped, pass flagged)."""
+    from diff_gaussian_rasterization import _C
+    W, H, P = 320, 240, 8000
+    cam = ss.make_camera(W, H, 250.0, 6)
+    g = ss.make_gaussians(P, cam, seed=41, degree_mode="all3", scale_mu=0.03)
+    args = (_dev(np.array([0.3, 0.2, 0.1], np.float32)), _dev(g["means3D"]), _dev(g["sh"][:, :1]), _dev(g["sh"][:, 1:]),
+            _dev(g["degrees"]), _dev(g["opacity"]), _dev(np.log(g["scales"]).astype(np.float32)), _dev(g["rotations"]), 1.0,
+            _dev(cam.world_view_transform), _dev(cam.full_proj_transform), cam.tanfovx, cam.tanfovy, H, W,
+            _dev(cam.camera_center), False, False)
+    was = _C.set_binding(binding)
+    try:
+        exact = _C.rasterize_gaussian_params(*args, exact=True)
+        R = exact[0].pairs
+        s0 = _C.pass_stats()
+        out = _C.rasterize_gaussian_params(*args, _reserve=R // 2)            # strict (default)
+        s1 = _C.pass_stats()
+        assert s1["redone_passes"] == s0["redone_passes"] + 1
+        assert not out[0].truncated and out[0].pairs == R and int(out[0]) == int(exact[0])
+        assert torch.equal(out[1], exact[1]) and torch.equal(out[2], exact[2])
+        lossy = _C.rasterize_gaussian_params(*args, _reserve=R // 2, _strict_override=False)
+        assert lossy[0].truncated and not torch.equal(lossy[1], exact[1])
+    finally:
+        _C.set_binding(was)
+
+
 def test_odd_coefficient_counts_and_dc_only():
     """M = 1 (no features_rest), M = 4 and M = 9: the scalar / general staging paths."""
     from diff_gaussian_rasterization import _C

@@ -267,6 +267,40 @@ def test_fixture_files_decode_and_render(half, golden_dir):
                          ragged_forward(_C, qm, inputs, c, exact=False, reserve=reserve), (half, image, "reserved"))
 
 
+def test_strict_redo_and_lossy_opt_out(golden_dir):
+    """tests/test_train_loop_gpu.py's test of that name for the quantised forward, on quantised_P200.ply at 80x48, the
+    smallest case of test_fixture_files_decode_and_render (more than 100 of its Gaussians show there, so R // 2 > 0): the
+    same overflowing reservation through strict mode (default: result == exact path, one redo counted; counter mode not
+    counted twice) and with strict mode off (farthest pairs dropped, pass flagged)."""
+    import os
+
+    from diff_gaussian_rasterization import _C
+    from r3dgs_quantised import QuantisedModel
+    qm = QuantisedModel.from_ply(os.path.join(golden_dir, "quantised_P200.ply"), False)
+    c = camera("80x48", T=(0.1, -0.05, 4.0))
+    P = qm.P
+    exact = quantised_forward(_C, qm, c)
+    R = exact[0].pairs
+    assert R >= 2
+    s0 = _C.pass_stats()
+    out = quantised_forward(_C, qm, c, exact=False, reserve=R // 2)            # strict (default)
+    s1 = _C.pass_stats()
+    assert s1["redone_passes"] == s0["redone_passes"] + 1
+    assert not out[0].truncated and out[0].pairs == R and int(out[0]) == int(exact[0])
+    assert torch.equal(out[1], exact[1]) and torch.equal(out[2], exact[2])
+    # counter mode accumulates into its outputs: the redo must not count the truncated pass as well
+    touched, transm = torch.zeros(P, dtype=torch.int32, device="cuda"), torch.zeros(P, device="cuda")
+    touched_x, transm_x = torch.zeros_like(touched), torch.zeros_like(transm)
+    quantised_forward(_C, qm, c, counters=(touched_x, transm_x))
+    quantised_forward(_C, qm, c, exact=False, reserve=R // 2, counters=(touched, transm))
+    assert touched_x.sum() > 0 and torch.equal(touched, touched_x)
+    assert torch.allclose(transm, transm_x, rtol=1e-5, atol=1e-4)   # float atomics: order-dependent low bits
+    lossy = _C.rasterize_gaussians_quantised(c.bg, qm.xyz, qm.geom_ids, qm.sh_ids, qm.codebooks, 1.0, c.vm, c.pm, c.tanfovx,
+                                             c.tanfovy, c.H, c.W, qm.per_band, qm.cumsum, qm.coeffs, c.cp, False, False,
+                                             _reserve=R // 2, _strict_override=False)
+    assert lossy[0].truncated and not torch.equal(lossy[1], exact[1])
+
+
 class DecodedModel:
     """decode()'s tensors shaped like the reference's GaussianModel with variable_sh_bands: get_features is the list of
     per-degree tensors.  Its activations are this repository's (_C.activate_params)."""

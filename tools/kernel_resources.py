@@ -39,7 +39,7 @@ for r, d in zip(rows, demangle([r["name"] for r in rows])):
     d = d.replace("void ", "").replace("(anonymous namespace)::", "").replace("r3::", "")
     r["name"] = re.sub(r"\(.*", "", d)
 print("kernel resources on gfx950 (compiler metadata of this tree's build; waves/SIMD = what registers and STATIC LDS allow, 8 at most;")
-print("the depth_sort_color / depth_colscan kernels also take dynamic LDS -- up to 64 KB per workgroup, capi.hip prepare_depth_bucket_sort --")
+print("the depth_sort_color / depth_colscan kernels also take dynamic LDS -- up to 64 KB per workgroup, preprocess.hip prepare_depth_bucket_sort --")
 print("which this table does not see; scratch = spilled registers, all outside the kernels' inner loops)")
 print(f"{'kernel':62s} {'unit':20s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'LDS B':>7s} {'scratch B':>9s} {'wg':>5s} {'waves/SIMD':>10s}")
 rows = [r for r in rows if "rocprim" not in r["name"] and "hipcub" not in r["name"]]   # the library's own kernels
