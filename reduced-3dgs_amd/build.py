@@ -43,9 +43,12 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "optim.hip": EXACT,
     # per-iteration training statistics: the roundings stats_math.h names and no others (bit-exact accumulator updates)
     "train_stats.hip": EXACT,
+    # evaluation metrics: save_image's 8-bit rounding and to_tensor's divide, rounding for rounding (metrics_math.h)
+    "metrics.hip": EXACT,
     "capi.hip": [],
 }
 HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", "stats_math.h",
+           "metrics_math.h", os.path.join("..", "..", "include", "r3dgs_metrics.h"),
            os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
            os.path.join("..", "..", "include", "r3dgs_quantised.h"),
            os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),

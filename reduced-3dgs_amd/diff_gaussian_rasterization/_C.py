@@ -178,6 +178,17 @@ if hasattr(_lib, "r3dgs_visible_means"):   # per-iteration training statistics (
     _lib.r3dgs_alpha_regul_backward.argtypes = [_i] + [_vp] * 6
     _lib.r3dgs_densification_stats.restype = _i
     _lib.r3dgs_densification_stats.argtypes = [_i] + [_vp] * 6
+if hasattr(_lib, "r3dgs_image_metrics"):   # evaluation metrics (include/r3dgs_metrics.h; absent from older A/B builds)
+    _lib.r3dgs_image_metrics_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_image_metrics_workspace_bytes.argtypes = [_i, _i, _i]
+    _lib.r3dgs_image_metrics.restype = _i
+    _lib.r3dgs_image_metrics.argtypes = [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]
+    _lib.r3dgs_row_mse_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_row_mse_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong]
+    _lib.r3dgs_row_mse.restype = _i
+    _lib.r3dgs_row_mse.argtypes = [C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp, _vp]
+    _lib.r3dgs_image_to_uint8.restype = _i
+    _lib.r3dgs_image_to_uint8.argtypes = [_i, _i, _i, _vp, _vp, _vp]
 _lib.r3dgs_profile_enable.argtypes = [_i]
 _lib.r3dgs_profile_stage_name.restype = C.c_char_p
 _lib.r3dgs_profile_stage_name.argtypes = [_i]
@@ -1596,3 +1607,59 @@ def densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_ra
             _check(_lib.r3dgs_densification_stats(P, viewspace_grad.data_ptr(), radii.data_ptr(), xyz_gradient_accum.data_ptr(),
                                                   denom.data_ptr(), max_radii2D.data_ptr(), _stream()), "densification_stats")
     return None
+
+
+# ---- evaluation metrics (include/r3dgs_metrics.h, csrc/metrics.hip); the surface is r3dgs_metrics.py, which checks the
+# tensors (device, dtypes, shapes, contiguity).  These calls only launch, on the current stream, into tensors the caller
+# owns, without a host synchronisation, so they can be captured in a graph.  ctypes only: two launches per view.
+
+GT_F32_CHW, GT_U8_CHW, GT_U8_HWC = 0, 1, 2      # R3DGS_GT_*
+METRICS_CLAMP, METRICS_QUANTISE8 = 1, 2         # R3DGS_METRICS_*
+METRICS_ROW = 9                                 # R3DGS_METRICS_ROW
+
+
+def _need_metrics():
+    if not hasattr(_lib, "r3dgs_image_metrics"):
+        raise RuntimeError(f"{_LIB_PATH} has no evaluation metrics (r3dgs_image_metrics): rebuild it with build.py")
+
+
+def image_metrics_workspace_bytes(Cc, H, W):
+    """Bytes of device scratch r3dgs_image_metrics needs for a [C,H,W] image (0: a shape it refuses)."""
+    _need_metrics()
+    return int(_lib.r3dgs_image_metrics_workspace_bytes(Cc, H, W))
+
+
+def image_metrics(image, gt, gt_layout, flags, row, workspace):
+    """Writes the float64 row [METRICS_ROW] of image [C,H,W] against gt (r3dgs_image_metrics); workspace: uint8 tensor of
+    image_metrics_workspace_bytes(C, H, W) bytes."""
+    _need_metrics()
+    Cc, H, W = image.shape
+    with _on_device(image.device):
+        _check(_lib.r3dgs_image_metrics(Cc, H, W, image.data_ptr(), gt.data_ptr(), int(gt_layout), int(flags), row.data_ptr(),
+                                        workspace.data_ptr(), _stream()), "image_metrics")
+    return row
+
+
+def row_mse(a, b, rows):
+    """-> float64 [rows]: the mean squared error of each of the `rows` equal contiguous slices of a and b (r3dgs_row_mse)."""
+    _need_metrics()
+    dev = a.device
+    n = a.numel() // rows
+    out = torch.empty((rows,), dtype=torch.float64, device=dev)
+    with _on_device(dev):
+        ws_bytes = _lib.r3dgs_row_mse_workspace_bytes(rows, n)
+        if ws_bytes == 0:
+            raise RuntimeError(f"row_mse: invalid shape, {rows} rows of {n}")
+        ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=dev)
+        _check(_lib.r3dgs_row_mse(rows, n, a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), _stream()), "row_mse")
+    return out
+
+
+def image_to_uint8(image):
+    """-> uint8 [H,W,C] of image [C,H,W]: save_image's 8-bit rounding (r3dgs_image_to_uint8)."""
+    _need_metrics()
+    Cc, H, W = image.shape
+    out = torch.empty((H, W, Cc), dtype=torch.uint8, device=image.device)
+    with _on_device(image.device):
+        _check(_lib.r3dgs_image_to_uint8(Cc, H, W, image.data_ptr(), out.data_ptr(), _stream()), "image_to_uint8")
+    return out
