@@ -2,7 +2,8 @@
  * representation in place, its decoder, and its size (reduced-3dgs_amd/csrc/quant_math.h, preprocess.hip, capi.hip).
  * The Python surface is r3dgs_quantised.QuantisedModel.
  * Same conventions as r3dgs_rasterizer.h: device pointers; `void* stream` is a hipStream_t; return >= 0 on success, < 0
- * with the message in r3dgs_last_error().  Inference only: there is no backward.
+ * with the message in r3dgs_last_error().  The forwards are inference only; what training needs beside them is the adjoint of
+ * the lookup, r3dgs_quantised_codebook_grad below, which turns the gradients of the decoded tensors into the codebooks'.
  *
  * The model (what the reference's save_ply(quantised=True) stores, scene/gaussian_model.py:239-311), Gaussians sorted by
  * SH degree as in the file's vertex_0..vertex_3 groups; all arrays plain and contiguous:
@@ -63,6 +64,25 @@ int r3dgs_quantised_decode(int P, const int* coeffsNum, const int* perBandPrimit
                            const void* xyz, int xyz_is_half, const unsigned char* geom_ids, const unsigned char* sh_ids,
                            const float* codebooks, float* xyz_out, float* features_dc, float* features_rest, float* opacity,
                            float* scaling, float* rotation, int* degrees, void* stream);
+
+/* The adjoint of r3dgs_quantised_decode in the codebooks: dL_dcodebooks float [20][256], rows in the order of `codebooks`;
+ * centre c of book b receives the sum of the gradient elements whose id byte names it.  The five gradients are shaped exactly
+ * as the decoder writes its outputs -- dL_dfeatures_dc [P,1,3], dL_dfeatures_rest [P,15,3], dL_dopacity [P,1], dL_dscaling
+ * [P,3], dL_drotation [P,4] -- with the Gaussians in the model's own order (sorted by degree); any of them may be NULL and
+ * then counts as zeros.  A Gaussian of degree d contributes its 8 geometry slots (opacity -> book 16, the three scales -> 17,
+ * rotation re -> 18, the three rotation im -> 19) and the 3 (d+1)^2 SH slots it owns in sh_ids (coefficient 0 of all channels
+ * -> book 0, coefficient k >= 1 -> book k).  Rows of dL_dfeatures_rest ABOVE the Gaussian's degree are NOT READ: the decoder
+ * pads them with centre 0 of their book, and the rasterizer's gradient there is zero whenever lambda_sh_sparsity is 0.
+ * All 5120 entries are overwritten by every call; a centre without a member gets +0.0.  Every sum is accumulated in double
+ * in an order fixed by (P, the ids) and rounded to float once, without atomics: the same inputs give the same bits.  The
+ * call only enqueues work on `stream` (graph-capturable, no host wait); its grid depends on P alone.
+ * workspace: r3dgs_quantised_codebook_grad_workspace_bytes(P) bytes of device memory, 8-byte aligned, contents irrelevant
+ * (0 bytes, and then possibly NULL, for P == 0). */
+size_t r3dgs_quantised_codebook_grad_workspace_bytes(int P);
+int r3dgs_quantised_codebook_grad(int P, const int* coeffsNum, const int* perBandPrimitiveCount, const int* cumSumPrimitiveCount,
+                                  const unsigned char* geom_ids, const unsigned char* sh_ids, const float* dL_dfeatures_dc,
+                                  const float* dL_dfeatures_rest, const float* dL_dopacity, const float* dL_dscaling,
+                                  const float* dL_drotation, float* dL_dcodebooks, void* workspace, void* stream);
 
 /* Resident bytes of a model: P (8 + 6 or 12) + sum_d 3 (d+1)^2 P_d + 20 * 256 * 4 + the three band tables (48).
  * perBandPrimitiveCount_host: HOST int[4], adding up to P.  0 with a message on bad arguments. */

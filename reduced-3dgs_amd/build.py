@@ -45,6 +45,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "train_stats.hip": EXACT,
     # evaluation metrics: save_image's 8-bit rounding and to_tensor's divide, rounding for rounding (metrics_math.h)
     "metrics.hip": EXACT,
+    # the adjoint of the codebook lookup: double sums in a fixed order, no contraction to hide a rounding
+    "quant_grad.hip": EXACT,
     "capi.hip": [],
 }
 HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", "stats_math.h",
@@ -107,7 +109,7 @@ def build_torch_binding(force=False, verbose=True):
 
     import torch
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h",
-                                                               "r3dgs_trainstats.h")]
+                                                               "r3dgs_trainstats.h", "r3dgs_quantised.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
             [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT

@@ -1612,6 +1612,27 @@ int r3dgs_quantised_decode(int P, const int* coeffsNum, const int* perBandPrimit
     });
 }
 
+size_t r3dgs_quantised_codebook_grad_workspace_bytes(int P) { return r3::quantised_codebook_grad_workspace_bytes(P); }
+
+int r3dgs_quantised_codebook_grad(int P, const int* coeffsNum, const int* perBandPrimitiveCount, const int* cumSumPrimitiveCount,
+                                  const unsigned char* geom_ids, const unsigned char* sh_ids, const float* dL_dfeatures_dc,
+                                  const float* dL_dfeatures_rest, const float* dL_dopacity, const float* dL_dscaling,
+                                  const float* dL_drotation, float* dL_dcodebooks, void* workspace, void* stream)
+{
+    return guarded([&]() {
+        if (P < 0) throw r3::Error("quantised_codebook_grad: P < 0");
+        if (!dL_dcodebooks) throw r3::Error("quantised_codebook_grad: dL_dcodebooks is NULL");
+        if (P > 0 && (!coeffsNum || !perBandPrimitiveCount || !cumSumPrimitiveCount || !geom_ids || !sh_ids || !workspace))
+            throw r3::Error("quantised_codebook_grad: a required pointer is NULL");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        r3::launch_quantised_codebook_grad(P, coeffsNum, perBandPrimitiveCount, cumSumPrimitiveCount, geom_ids, sh_ids,
+                                           dL_dfeatures_dc, dL_dfeatures_rest, dL_dopacity, dL_dscaling, dL_drotation,
+                                           dL_dcodebooks, workspace, s);
+        r3::check_launch("quantised_codebook_grad", s, false);
+        return 0;
+    });
+}
+
 size_t r3dgs_quantised_bytes(int P, const int* perBandPrimitiveCount_host, int xyz_is_half)
 {
     return guarded(

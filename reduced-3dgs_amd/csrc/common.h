@@ -780,6 +780,13 @@ void launch_quantised_decode(int P, const int* coeffs, const int* perband, const
                              float* features_dc, float* features_rest, float* opacity, float* scaling, float* rotation,
                              int* degrees, hipStream_t s);   // preprocess.hip: quant_math.h's quant_decode_one per Gaussian
 
+// quant_grad.hip: the adjoint of the lookup (quant_math.h quant_grad_slot), per-group double partials + a finishing sum
+size_t quantised_codebook_grad_workspace_bytes(int P);
+void launch_quantised_codebook_grad(int P, const int* coeffs, const int* perband, const int* cumsum, const unsigned char* geom_ids,
+                                    const unsigned char* sh_ids, const float* dL_dfeatures_dc, const float* dL_dfeatures_rest,
+                                    const float* dL_dopacity, const float* dL_dscaling, const float* dL_drotation,
+                                    float* dL_dcodebooks, void* workspace, hipStream_t s);
+
 void issue_header_reduce(const HeaderArgs* a, hipStream_t s);
 void prepare_depth_bucket_sort(int nb);   // LDS opt-in of the depth-sort kernels, once per device (not a stream op)
 void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* a, hipStream_t s);   // preprocess.hip

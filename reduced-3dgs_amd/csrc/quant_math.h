@@ -147,6 +147,67 @@ __host__ __device__ inline void quant_decode_one(int i, const int* coeffs, const
     }
 }
 
+// ---- the adjoint of the lookup (r3dgs_quantised_codebook_grad, quant_grad.hip) ------------------------------------------
+// A Gaussian has kQuantSlots id slots: its 8 geometry ids, then the 48 elements of a full SH row, of which a Gaussian of
+// degree d owns the first 3 (d+1)^2.  Slot s of Gaussian i adds one element of one of the five gradient tensors -- shaped as
+// quant_decode_one writes its outputs -- to centre *id of codebook `book`.  This is the ONE statement of that mapping: the
+// kernel and tests/hostcheck_quant_grad both call it.
+constexpr int kQuantGeomSlots = 8;
+constexpr int kQuantSlots = kQuantGeomSlots + 48;
+enum QuantGradTensor { kGradDc = 0, kGradRest, kGradOpacity, kGradScaling, kGradRotation, kQuantGradTensors };
+
+struct QuantGradSlot {
+    int book;            // QuantBook row of dL_dcodebooks
+    int tensor;          // QuantGradTensor
+    long long elem;      // element of that tensor (flat index)
+    const uint8_t* id;   // the byte that names the centre
+};
+
+// sh_off: the byte of sh_ids at which Gaussian i's row starts, 3 * quant_ragged_offset(i); deg its degree.  False for an SH
+// slot above the degree: the decoder pads those with centre 0, nobody owns them, and their gradient is not read.
+__host__ __device__ inline bool quant_grad_slot(int s, long long i, int deg, long long sh_off, const uint8_t* geom_ids,
+                                                const uint8_t* sh_ids, QuantGradSlot* o)
+{
+    if (s < kQuantGeomSlots) {
+        o->id = geom_ids + 8 * i + s;
+        if (s == 0) {
+            o->book = kBookOpacity, o->tensor = kGradOpacity, o->elem = i;
+        } else if (s < 4) {
+            o->book = kBookScaling, o->tensor = kGradScaling, o->elem = 3 * i + (s - 1);
+        } else {
+            o->book = s == 4 ? kBookRotRe : kBookRotIm, o->tensor = kGradRotation, o->elem = 4 * i + (s - 4);
+        }
+        return true;
+    }
+    const int e = s - kQuantGeomSlots;   // element of the SH row: 3 * coefficient + channel
+    if (e >= 3 * (deg + 1) * (deg + 1)) return false;
+    o->id = sh_ids + sh_off + e;
+    o->book = quant_sh_book(e);
+    if (e < 3) {
+        o->tensor = kGradDc, o->elem = 3 * i + e;
+    } else {
+        o->tensor = kGradRest, o->elem = 45 * i + (e - 3);
+    }
+    return true;
+}
+
+// The reduction's shape, a function of P alone (never of the device): a chunk is kQuantGradChunk consecutive Gaussians; a
+// group is a run of consecutive chunks that one wave sums into one partial table; at most kQuantGradMaxGroups groups.
+constexpr int kQuantGradChunk = 1024;
+constexpr int kQuantGradMaxGroups = 2048;
+
+__host__ __device__ inline int quant_grad_chunks(int P) { return (int)(((long long)P + kQuantGradChunk - 1) / kQuantGradChunk); }
+__host__ __device__ inline int quant_grad_chunks_per_group(int P)
+{
+    const int c = quant_grad_chunks(P);
+    return c <= kQuantGradMaxGroups ? 1 : (c + kQuantGradMaxGroups - 1) / kQuantGradMaxGroups;
+}
+__host__ __device__ inline int quant_grad_groups(int P)
+{
+    const int c = quant_grad_chunks(P), per = quant_grad_chunks_per_group(P);
+    return (c + per - 1) / per;
+}
+
 // resident bytes of a model (the band tables: three int[4])
 __host__ __device__ inline long long quant_model_bytes(long long P, const int* perband, int xyz_is_half)
 {

@@ -34,6 +34,7 @@
 
 #include "r3dgs_loss.h"
 #include "r3dgs_optim.h"
+#include "r3dgs_quantised.h"
 #include "r3dgs_rasterizer.h"
 #include "r3dgs_trainstats.h"
 
@@ -74,6 +75,8 @@ struct Api {
     R3_FN(r3dgs_visible_means)
     R3_FN(r3dgs_alpha_regul_backward)
     R3_FN(r3dgs_densification_stats)
+    R3_FN(r3dgs_quantised_codebook_grad_workspace_bytes)
+    R3_FN(r3dgs_quantised_codebook_grad)
 #undef R3_FN
     bool bound = false;
 } api;
@@ -125,6 +128,9 @@ void bind(const std::map<std::string, uintptr_t>& addr)
     R3_OPT(r3dgs_visible_means)
     R3_OPT(r3dgs_alpha_regul_backward)
     R3_OPT(r3dgs_densification_stats)
+    // the adjoint of the codebook lookup (r3dgs_quantised.h): likewise
+    R3_OPT(r3dgs_quantised_codebook_grad_workspace_bytes)
+    R3_OPT(r3dgs_quantised_codebook_grad)
 #undef R3_OPT
     api.bound = true;
 }
@@ -487,6 +493,59 @@ std::tuple<Tensor, Tensor> activate_params(const Tensor& scaling, const Tensor& 
     return {s, q};
 }
 
+// dL_dcodebooks [20,256] from the gradients of the decoded tensors (empty tensor = zeros); the refusals of
+// diff_gaussian_rasterization/_C.py _check_quantised_grads
+Tensor quantised_codebook_grad(const Tensor& geom_ids, const Tensor& sh_ids, const Tensor& perBandPrimitiveCount,
+                               const Tensor& cumSumPrimitiveCount, const Tensor& coeffsNum, const Tensor& dL_dfeatures_dc,
+                               const Tensor& dL_dfeatures_rest, const Tensor& dL_dopacity, const Tensor& dL_dscaling,
+                               const Tensor& dL_drotation)
+{
+    need_bound();
+    if (!api.r3dgs_quantised_codebook_grad || !api.r3dgs_quantised_codebook_grad_workspace_bytes)
+        throw std::runtime_error("the loaded libr3dgs_hip.so has no r3dgs_quantised_codebook_grad: rebuild it with build.py");
+    const c10::Device dev = geom_ids.device();
+    if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
+    if (geom_ids.scalar_type() != at::kByte || geom_ids.dim() != 2 || geom_ids.size(1) != 8)
+        throw std::runtime_error("geom_ids must be uint8 with dimensions (num_points, 8)");
+    const int64_t P = geom_ids.size(0);
+    if (sh_ids.scalar_type() != at::kByte || sh_ids.dim() != 1) throw std::runtime_error("sh_ids must be a flat uint8 tensor");
+    auto plain = [&](const Tensor& t, const char* name) {
+        if (t.device() != dev) throw std::runtime_error(std::string(name) + ": expected a tensor on " + dev.str() + ", got " + t.device().str());
+        if (!t.is_contiguous()) throw std::runtime_error(std::string(name) + ": quantised_codebook_grad needs a contiguous tensor");
+    };
+    plain(geom_ids, "geom_ids");
+    plain(sh_ids, "sh_ids");
+    const Tensor* tables[3] = {&perBandPrimitiveCount, &cumSumPrimitiveCount, &coeffsNum};
+    const char* table_names[3] = {"perBandPrimitiveCount", "cumSumPrimitiveCount", "coeffsNum"};
+    for (int k = 0; k < 3; k++) {
+        if (tables[k]->scalar_type() != at::kInt || tables[k]->numel() != 4)
+            throw std::runtime_error(std::string(table_names[k]) + " must be int32 with 4 entries (degrees 0..3)");
+        plain(*tables[k], table_names[k]);
+    }
+    const Tensor* grads[5] = {&dL_dfeatures_dc, &dL_dfeatures_rest, &dL_dopacity, &dL_dscaling, &dL_drotation};
+    const char* grad_names[5] = {"dL_dfeatures_dc", "dL_dfeatures_rest", "dL_dopacity", "dL_dscaling", "dL_drotation"};
+    const std::vector<int64_t> shapes[5] = {{P, 1, 3}, {P, 15, 3}, {P, 1}, {P, 3}, {P, 4}};
+    const float* gp[5];
+    for (int k = 0; k < 5; k++) {
+        const Tensor& t = *grads[k];
+        gp[k] = nullptr;
+        if (!t.defined() || (t.numel() == 0 && t.dim() == 1)) continue;   // absent: zeros
+        if (t.scalar_type() != at::kFloat || t.sizes().vec() != shapes[k])
+            throw std::runtime_error(std::string(grad_names[k]) + " must be float32 with the decoder's dimensions (or None)");
+        plain(t, grad_names[k]);
+        gp[k] = t.numel() ? t.data_ptr<float>() : nullptr;
+    }
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = at::empty({20, 256}, geom_ids.options().dtype(at::kFloat));
+    Tensor work = at::empty({(int64_t)api.r3dgs_quantised_codebook_grad_workspace_bytes((int)P)}, geom_ids.options());
+    if (api.r3dgs_quantised_codebook_grad((int)P, coeffsNum.data_ptr<int>(), perBandPrimitiveCount.data_ptr<int>(),
+                                          cumSumPrimitiveCount.data_ptr<int>(), P ? geom_ids.data_ptr<uint8_t>() : nullptr,
+                                          sh_ids.numel() ? sh_ids.data_ptr<uint8_t>() : nullptr, gp[0], gp[1], gp[2], gp[3], gp[4],
+                                          out.data_ptr<float>(), work.numel() ? work.data_ptr() : nullptr, cur_stream(dev)) < 0)
+        fail("quantised_codebook_grad");
+    return out;
+}
+
 // markVisible (rasterize_points.cu:307-326)
 Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tensor& projmatrix)
 {
@@ -779,6 +838,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("forward_params_reserved", &forward_params_reserved);
     m.def("backward_params", &backward_params);
     m.def("activate_params", &activate_params);
+    m.def("quantised_codebook_grad", &quantised_codebook_grad);
     m.def("l1_ssim_forward", &l1_ssim_forward);
     m.def("l1_ssim_backward", &l1_ssim_backward);
     m.def("l1_forward", &l1_forward);

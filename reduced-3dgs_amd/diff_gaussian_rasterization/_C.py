@@ -111,6 +111,11 @@ if hasattr(_lib, "r3dgs_quantised_forward"):   # include/r3dgs_quantised.h
     _lib.r3dgs_quantised_decode.argtypes = [_i, _vp, _vp, _vp, _vp, _i] + [_vp] * 11
     _lib.r3dgs_quantised_bytes.restype = C.c_size_t
     _lib.r3dgs_quantised_bytes.argtypes = [_i, C.POINTER(_i), _i]
+if hasattr(_lib, "r3dgs_quantised_codebook_grad"):   # the lookup's adjoint (absent from older A/B builds)
+    _lib.r3dgs_quantised_codebook_grad_workspace_bytes.restype = C.c_size_t
+    _lib.r3dgs_quantised_codebook_grad_workspace_bytes.argtypes = [_i]
+    _lib.r3dgs_quantised_codebook_grad.restype = _i
+    _lib.r3dgs_quantised_codebook_grad.argtypes = [_i] + [_vp] * 13
 _lib.r3dgs_colour_variance_accumulate.restype = _i
 _lib.r3dgs_colour_variance_accumulate.argtypes = [_i, _vp, _i, _i] + [_vp] * 12
 _lib.r3dgs_min_pixel_size.restype = _i
@@ -210,6 +215,7 @@ _EXT_PARAMS_FUNCS = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r
                      "r3dgs_activate_params")   # ... nor the raw-parameter entry points
 _EXT_STATS_FUNCS = ("r3dgs_train_stats_workspace_bytes", "r3dgs_visible_means", "r3dgs_alpha_regul_backward",
                     "r3dgs_densification_stats")   # ... nor the training statistics
+_EXT_QUANT_FUNCS = ("r3dgs_quantised_codebook_grad_workspace_bytes", "r3dgs_quantised_codebook_grad")   # ... nor the lookup's adjoint
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -219,7 +225,7 @@ if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
         _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value
-                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS + _EXT_STATS_FUNCS
+                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS + _EXT_STATS_FUNCS + _EXT_QUANT_FUNCS
                                                          if hasattr(_lib, f))})
         _ext = _ext_loaded
     except ImportError:
@@ -986,20 +992,77 @@ def rasterize_gaussians_quantised(background, xyz, geom_ids, sh_ids, codebooks, 
                               debug, _reserve, strict)
 
 
-def quantised_decode(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum):
+def quantised_decode(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum, want_xyz=True):
     """The dense fp32 tensors the reference's load_ply returns for the model, decoded on the device by the functions the
     quantised kernels use (csrc/quant_math.h) -> (xyz [P,3], features_dc [P,1,3], features_rest [P,15,3], opacity [P,1],
-    scaling [P,3], rotation [P,4], degrees int32 [P,1])."""
+    scaling [P,3], rotation [P,4], degrees int32 [P,1]).  want_xyz=False: the positions are not decoded (xyz_out NULL) and
+    the first entry is None -- for a caller that holds them in float already."""
     _need_quantised()
     P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
     f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # every element is written by the library
-    out = (f(P, 3), f(P, 1, 3), f(P, 15, 3), f(P, 1), f(P, 3), f(P, 4), torch.empty((P, 1), dtype=torch.int32, device=dev))
+    out = (f(P, 3) if want_xyz else None, f(P, 1, 3), f(P, 15, 3), f(P, 1), f(P, 3), f(P, 4),
+           torch.empty((P, 1), dtype=torch.int32, device=dev))
     if P:
         with _on_device(dev):
             _check(_lib.r3dgs_quantised_decode(P, _ptr(coeffsNum), _ptr(perBandPrimitiveCount), _ptr(cumSumPrimitiveCount),
                                                xyz.data_ptr(), half, geom_ids.data_ptr(),
                                                sh_ids.data_ptr() if sh_ids.numel() else geom_ids.data_ptr(),
-                                               codebooks.data_ptr(), *(t.data_ptr() for t in out), _stream()), "quantised_decode")
+                                               codebooks.data_ptr(), *(_ptr(t) for t in out), _stream()), "quantised_decode")
+    return out
+
+
+QUANTISED_GRAD_CHUNK = 1024   # csrc/quant_math.h kQuantGradChunk: consecutive Gaussians one wave sums before the next chunk
+QUANTISED_GRAD_MAX_GROUPS = 2048   # kQuantGradMaxGroups: above that many chunks a wave takes a run of them
+
+
+def _check_quantised_grads(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum, grads):
+    """-> (P, device); the refusals of quantised_codebook_grad."""
+    dev = geom_ids.device
+    if dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if geom_ids.dtype != torch.uint8 or geom_ids.dim() != 2 or geom_ids.size(1) != 8:
+        raise RuntimeError("geom_ids must be uint8 with dimensions (num_points, 8)")
+    P = int(geom_ids.size(0))
+    if sh_ids.dtype != torch.uint8 or sh_ids.dim() != 1:
+        raise RuntimeError("sh_ids must be a flat uint8 tensor")
+    tables = ((perBandPrimitiveCount, "perBandPrimitiveCount"), (cumSumPrimitiveCount, "cumSumPrimitiveCount"),
+              (coeffsNum, "coeffsNum"))
+    for t, name in tables:
+        if t.dtype != torch.int32 or t.numel() != 4:
+            raise RuntimeError(f"{name} must be int32 with 4 entries (degrees 0..3)")
+    shapes = (("dL_dfeatures_dc", (P, 1, 3)), ("dL_dfeatures_rest", (P, 15, 3)), ("dL_dopacity", (P, 1)),
+              ("dL_dscaling", (P, 3)), ("dL_drotation", (P, 4)))
+    for t, (name, shape) in zip(grads, shapes):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise RuntimeError(f"{name} must be float32 with dimensions {shape} (or None)")
+    for t, name in ((geom_ids, "geom_ids"), (sh_ids, "sh_ids")) + tables + tuple(
+            (t, n) for t, (n, _) in zip(grads, shapes) if t is not None):
+        if t.device != dev:
+            raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name}: quantised_codebook_grad needs a contiguous tensor")
+    return P, dev
+
+
+def quantised_codebook_grad(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum, dL_dfeatures_dc,
+                            dL_dfeatures_rest, dL_dopacity, dL_dscaling, dL_drotation):
+    """The adjoint of quantised_decode in the codebooks (include/r3dgs_quantised.h r3dgs_quantised_codebook_grad): the
+    gradients of the decoded tensors, shaped as quantised_decode returns them (None = zeros), summed into the centres the ids
+    name -> dL_dcodebooks float32 [20,256].  Double accumulation in a fixed order, one rounding, no atomics: the same inputs
+    give the same bits.  Rows of dL_dfeatures_rest above a Gaussian's degree are not read."""
+    if not hasattr(_lib, "r3dgs_quantised_codebook_grad"):
+        raise RuntimeError("the loaded libr3dgs_hip.so has no r3dgs_quantised_codebook_grad: rebuild it with build.py")
+    grads = (dL_dfeatures_dc, dL_dfeatures_rest, dL_dopacity, dL_dscaling, dL_drotation)
+    if _ext is not None:
+        return _ext.quantised_codebook_grad(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum,
+                                            *(_t(t) for t in grads))
+    P, dev = _check_quantised_grads(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum, grads)
+    out = torch.empty((20, 256), dtype=torch.float32, device=dev)   # every entry is written by the library
+    work = torch.empty(int(_lib.r3dgs_quantised_codebook_grad_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        _check(_lib.r3dgs_quantised_codebook_grad(P, _ptr(coeffsNum), _ptr(perBandPrimitiveCount), _ptr(cumSumPrimitiveCount),
+                                                  _ptr(geom_ids), _ptr(sh_ids), *(_ptr(t) for t in grads), out.data_ptr(),
+                                                  _ptr(work), _stream()), "quantised_codebook_grad")
     return out
 
 

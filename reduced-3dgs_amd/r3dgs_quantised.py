@@ -11,8 +11,22 @@ place (`diff_gaussian_rasterization._C.rasterize_gaussians_quantised`, include/r
     qm = QuantisedModel.from_ply("point_cloud_quantised_half.ply", half_float=True)
     image = render(view, qm, pipe, background)["render"]
 
-Inference only: there are no gradients.  To train on from a quantised file, `decode()` and use the dense paths.
+Fine-tuning in codebook space: the ids stay fixed, the 20 x 256 centres and the positions are the parameters.
+
+    qm.requires_grad_(codebooks=True, xyz=True)      # qm.codebooks becomes a leaf; qm.xyz_master [P,3] float32 is created
+    opt = r3dgs_optim.Adam(qm.parameters(), lr=1e-3)  # (or torch.optim.Adam)
+    out = render(view, qm, pipe, background)          # differentiable in qm.codebooks and qm.xyz_master
+    loss(out["render"], target).backward(); opt.step()
+    qm.commit(); qm.to_ply("point_cloud_quantised_half.ply")
+
+With grad enabled, render() of a trainable model decodes the ids into dense tensors that live for that step
+(`_C.quantised_decode`), runs the raw-parameter training route of r3dgs_render on them, and its backward sums the decoded
+tensors' gradients into the centres (`_C.quantised_codebook_grad`: double accumulation in a fixed order, no atomics -- the
+same inputs give the same bits) and hands the position gradient through.  The resident model stays as small as it was.
+A model nobody asked gradients of, or any model under no_grad, renders through the in-place inference route as before.
+The SH-sparsity term (lambda_sh_sparsity) is not available for a quantised model.
 """
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -49,6 +63,7 @@ class QuantisedModel:
         self.cumsum = torch.cumsum(self.per_band, dim=0).to(torch.int32)
         self.coeffs = torch.tensor([1, 4, 9, 16], **i32)
         self.max_sh_degree = self.active_sh_degree = 3
+        self.xyz_master = None   # float32 [P,3] leaf while the positions are trained (requires_grad_)
 
     # ---- construction ------------------------------------------------------------------------------------------------
     @classmethod
@@ -145,3 +160,111 @@ class QuantisedModel:
         if self.device.type != "cuda":
             raise RuntimeError("QuantisedModel.decode: the model is on the host; the decoder runs on the device (no CPU path)")
         return OrderedDict(zip(DECODED, _C.quantised_decode(*self.arrays())))
+
+    # ---- fine-tuning: the centres and the positions as parameters, the ids fixed -----------------------------------------
+    @property
+    def trainable(self):
+        return bool(self.codebooks.requires_grad) or self.xyz_master is not None
+
+    def requires_grad_(self, codebooks=True, xyz=True):
+        """Asks for gradients of the centres and / or the positions.  `codebooks` (float32 [20,256]) becomes a leaf.  For the
+        positions a float32 leaf `xyz_master` [P,3] is created from the exact widening of `xyz`; the stored `xyz` is not
+        touched while training (a half array trained in place would round every step away) -- commit() rounds it back."""
+        self.codebooks = self.codebooks.detach().requires_grad_(bool(codebooks))
+        if xyz:
+            if self.xyz_master is None:
+                self.xyz_master = self.xyz.detach().to(torch.float32).clone().requires_grad_(True)
+        else:
+            self.xyz_master = None
+        return self
+
+    def parameters(self):
+        """The optimizer's parameter groups (r3dgs_optim.Adam, torch.optim.Adam): only what requires_grad_ asked for."""
+        groups = []
+        if self.codebooks.requires_grad:
+            groups.append({"params": [self.codebooks], "name": "codebooks"})
+        if self.xyz_master is not None:
+            groups.append({"params": [self.xyz_master], "name": "xyz"})
+        return groups
+
+    def decode_for_training(self):
+        """(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees) for one training step: decode()'s tensors,
+        differentiable in `codebooks`; xyz is `xyz_master` itself when the positions are trained (they are then not decoded)."""
+        if self.device.type != "cuda":
+            raise RuntimeError("QuantisedModel: the model is on the host; the decoder runs on the device (no CPU path)")
+        out = _DecodeQuantised.apply(self.codebooks, self, self.xyz_master is None)
+        xyz = self.xyz_master if self.xyz_master is not None else out[6]
+        return (xyz,) + tuple(out[:6])
+
+    def commit(self, half_float=None):
+        """Ends a fine-tune: rounds xyz_master into xyz's dtype (as .half() does), rounds the centres to half-representable
+        floats when `half_float` (default: when the positions are half, as in a half_float file), and drops the leaves.
+        Afterwards the inference forward renders exactly the committed values."""
+        half = self.xyz_is_half if half_float is None else bool(half_float)
+        with torch.no_grad():
+            if self.xyz_master is not None:
+                self.xyz = self.xyz_master.detach().to(self.xyz.dtype).contiguous()
+            books = self.codebooks.detach()
+            self.codebooks = (books.half().float() if half else books.clone()).contiguous()
+        self.xyz_master = None
+        return self
+
+    def to_ply(self, path, half_float=None):
+        """Writes the reference's quantised file (the layout of its save_ply(quantised=True), read back by from_ply):
+        vertex_0..vertex_3 with x y z, the id bytes f_dc_*, f_rest_* (rrr.. ggg.. bbb..), opacity, scale_*, rot_*, then
+        codebook_centers.  half_float (default: whether the positions are half): positions and centres as half bit patterns
+        in int16 columns.  With the model's own format, from_ply gives every array back bit for bit."""
+        from plyfile import PlyData, PlyElement
+        if self.trainable:
+            raise RuntimeError("QuantisedModel.to_ply: the model is being trained; commit() first")
+        half = self.xyz_is_half if half_float is None else bool(half_float)
+        ftype = "i2" if half else "f4"
+
+        def floats(t):   # float tensor -> the file's column: half bit patterns as int16, or float32
+            t = t.detach().cpu()
+            return t.half().view(torch.int16).numpy() if half else t.float().numpy()
+        xyz, geom, sh = floats(self.xyz), self.geom_ids.cpu().numpy(), self.sh_ids.cpu().numpy()
+        elements, first, byte = [], 0, 0
+        for d, n in enumerate(self.per_band_count):
+            K = (d + 1) ** 2
+            ids = sh[byte:byte + 3 * K * n].reshape(n, K, 3)
+            rest = ids[:, 1:, :].transpose(0, 2, 1).reshape(n, 3 * (K - 1))   # [coefficient][channel] -> [channel][coefficient]
+            columns = ([(k, ftype, xyz[first:first + n, j]) for j, k in enumerate("xyz")] +
+                       [(f"f_dc_{c}", "u1", ids[:, 0, c]) for c in range(3)] +
+                       [(f"f_rest_{j}", "u1", rest[:, j]) for j in range(3 * (K - 1))] +
+                       [(k, "u1", geom[first:first + n, j]) for j, k in enumerate(GEOM_COLUMNS)])
+            el = np.empty(n, dtype=[(k, t) for k, t, _ in columns])
+            for k, _, col in columns:
+                el[k] = col
+            elements.append(PlyElement.describe(el, f"vertex_{d}"))
+            first, byte = first + n, byte + 3 * K * n
+        books = floats(self.codebooks)
+        centres = np.empty(256, dtype=[(n, ftype) for n in BOOK_NAMES])
+        for k, n in enumerate(BOOK_NAMES):
+            centres[n] = books[k]
+        elements.append(PlyElement.describe(centres, "codebook_centers"))
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        PlyData(elements).write(path)
+
+
+class _DecodeQuantised(torch.autograd.Function):
+    """codebooks -> (features_dc, features_rest, opacity, scaling, rotation, degrees[, xyz]) of a QuantisedModel by
+    _C.quantised_decode; the backward is its adjoint, _C.quantised_codebook_grad."""
+
+    @staticmethod
+    def forward(ctx, codebooks, qm, want_xyz):
+        xyz, dc, rest, opacity, scaling, rotation, degrees = _C.quantised_decode(
+            qm.xyz, qm.geom_ids, qm.sh_ids, codebooks, qm.per_band, qm.cumsum, qm.coeffs, want_xyz=want_xyz)
+        ctx.ids = (qm.geom_ids, qm.sh_ids, qm.per_band, qm.cumsum, qm.coeffs)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(degrees)
+        if not want_xyz:
+            return dc, rest, opacity, scaling, rotation, degrees
+        ctx.mark_non_differentiable(xyz)
+        return dc, rest, opacity, scaling, rotation, degrees, xyz
+
+    @staticmethod
+    def backward(ctx, g_dc, g_rest, g_opacity, g_scaling, g_rotation, *_):
+        grads = [None if g is None else g.contiguous() for g in (g_dc, g_rest, g_opacity, g_scaling, g_rotation)]
+        return _C.quantised_codebook_grad(*ctx.ids, *grads), None, None

@@ -13,7 +13,9 @@ pipe.convert_SHs_python, override_color, variable_sh_bands -- the call does what
 package entry points.  `pc` is anything shaped like the reference's GaussianModel: _xyz, _features_dc, _features_rest,
 _opacity, _scaling, _rotation, _degrees, active_sh_degree, max_sh_degree (and get_* / get_covariance / per_band_count for
 the fallback routes) -- or a r3dgs_quantised.QuantisedModel, which is rendered from its ids and codebooks in place
-(inference only: "viewspace_points" is None, and the three Python-side options and override_color are refused).
+(the three Python-side options, override_color and lambda_sh_sparsity are refused).  A QuantisedModel on which gradients
+were asked for (`requires_grad_`) trains, with grad enabled, through the same raw-parameter route on tensors decoded for the
+step, and the result then carries "viewspace_points" like any model's; otherwise "viewspace_points" is None.
 """
 import math
 
@@ -42,7 +44,8 @@ def fused_path_applies(pc, pipe, override_color=None, variable_sh_bands=False):
 
 
 def _render_quantised(camera, qm, pipe, bg_color, scaling_modifier, override_color, lambda_sh_sparsity, measure_fps):
-    """render() of a QuantisedModel: the rasterizer reads ids, positions and codebooks in place.  Inference only."""
+    """render() of a QuantisedModel.  Inference (no_grad, or nobody asked for gradients): the rasterizer reads ids, positions
+    and codebooks in place.  Training: decode for this step, the raw-parameter route, the lookup's adjoint in the backward."""
     if override_color is not None:
         raise ValueError("render: override_color is not supported for a QuantisedModel (colours come from its codebooks); "
                          "decode() it and render the dense tensors")
@@ -53,12 +56,23 @@ def _render_quantised(camera, qm, pipe, bg_color, scaling_modifier, override_col
         raise ValueError("render: pipe.convert_SHs_python is not supported for a QuantisedModel (the kernels evaluate SH from "
                          "the ids); decode() it and render the dense tensors")
     if lambda_sh_sparsity:
-        raise ValueError("render: a QuantisedModel has no gradients (lambda_sh_sparsity must be 0)")
+        raise ValueError("render: the SH-sparsity term is not available for a QuantisedModel (lambda_sh_sparsity must be 0)")
     rs = _settings(camera, qm, pipe, bg_color, scaling_modifier)
     fps = 0
     if measure_fps:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
+    if qm.trainable and torch.is_grad_enabled():
+        xyz, dc, rest, opacity, scaling, rotation, degrees = qm.decode_for_training()
+        screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0
+        screenspace_points.retain_grad()
+        image, radii = rasterize_gaussian_params(xyz, screenspace_points, dc, rest, degrees, opacity, scaling, rotation, rs, 0.)
+        if measure_fps:
+            t1.record()
+            torch.cuda.synchronize()
+            fps = 1 / t0.elapsed_time(t1)
+        return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                "FPS": fps}
     _, image, radii, _, _, _ = _C.rasterize_gaussians_quantised(
         rs.bg, qm.xyz, qm.geom_ids, qm.sh_ids, qm.codebooks, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
         rs.tanfovy, rs.image_height, rs.image_width, qm.per_band, qm.cumsum, qm.coeffs, rs.campos, rs.prefiltered, rs.debug)
