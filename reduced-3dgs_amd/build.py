@@ -47,6 +47,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "metrics.hip": EXACT,
     # the adjoint of the codebook lookup: double sums in a fixed order, no contraction to hide a rounding
     "quant_grad.hip": EXACT,
+    # densification: the decisions and the children's rows with the roundings densify_math.h names and no others
+    "densify.hip": EXACT,
     "capi.hip": [],
 }
 HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", "stats_math.h",
@@ -54,7 +56,8 @@ HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_mat
            os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
            os.path.join("..", "..", "include", "r3dgs_quantised.h"),
            os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),
-           os.path.join("..", "..", "include", "r3dgs_optim.h"), os.path.join("..", "..", "include", "r3dgs_trainstats.h")]
+           os.path.join("..", "..", "include", "r3dgs_optim.h"), os.path.join("..", "..", "include", "r3dgs_trainstats.h"),
+           "densify_math.h", os.path.join("..", "..", "include", "r3dgs_densify.h")]
 
 
 def _newest(paths):

@@ -1,0 +1,285 @@
+"""`r3dgs_densify` -- densification on the MI355X in HIP (csrc/densify.hip, include/r3dgs_densify.h): clone, split and prune
+of the Gaussians, of both Adam moments of every parameter, of `_degrees` and of the accumulators as ONE read and one write of
+the state, with one host wait.
+
+    from r3dgs_densify import densify_and_prune, prune, prune_points
+
+    densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size, stats_dict)   # train.py:139
+    prune(gaussians, min_opacity, extent, max_screen_size, stats_dict)                         # train.py:144, :165
+    prune_points(gaussians, mask)                                                              # gaussian_model.py:548
+
+`pc` is anything shaped like the reference's GaussianModel: `_xyz`, `_features_dc`, `_features_rest`, `_opacity`, `_scaling`,
+`_rotation`, `_degrees`, `xyz_gradient_accum`, `denom`, `max_radii2D`, `percent_dense` and `optimizer`, whose groups are
+named "xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation" with one parameter each.  The reference runs these calls as
+some 80 torch launches that copy every tensor up to four times (cat, cat, mask-index, mask-index) and wait on the host about
+a dozen times (scene/gaussian_model.py:502-691).
+
+Semantics: the reference's, restated line by line in tests/densify_ref.py, quirks included:
+  * the result is four stable segments in source order: surviving originals, surviving clones, surviving first children,
+    surviving second children; exp_avg / exp_avg_sq rows follow their parameter row in the first and are zero in the others,
+    state['step'] is untouched, and the optimizer's state is re-keyed as _prune_optimizer / cat_tensors_to_optimizer do it
+    (the old key deleted, the SAME state dict under the new parameter, group["params"][0] replaced);
+  * inside densify_and_prune the screen-size term of the prune mask never acts: densification_postfix has zeroed max_radii2D
+    before prune() looks at it.  It acts when prune() is called on its own;
+  * the children's world-size term looks at exp(log(scale / 1.6)), the activation of the stored child scale;
+  * max_grad <= 0 is refused: the reference takes the split decision after the clones were appended with a zero gradient,
+    so it would split the clones;
+  * a group without optimizer state (before the first step) gets its parameter moved and nothing else; with store_grads
+    the `.grad` rows move like the moments, but only for a group that has state (as gaussian_model.py:511-515);
+  * after a densify, xyz_gradient_accum, denom, max_radii2D and density_gradient_accum are zeros of the new size; after
+    prune() and prune_points() the first three are compacted and density_gradient_accum is left alone, as in the reference.
+
+Noise: `noise` is standard-normal float32 [2, P, 3] indexed by (child, SOURCE Gaussian); only the rows of split parents are
+read.  With noise=None it is drawn as torch.randn((2, P, 3), generator=generator) on the device.  This is the reference's
+distribution (torch.normal(mean=0, std=s) is randn * s), not its random stream: the reference draws [2 n_split, 3].
+
+The calls read eight integers back once (the new sizes: they have to size the new tensors), so they are NOT capturable in a
+graph; nothing else waits.  No empty_cache().  P == 0 before or after is valid.  Host tensors are refused (no CPU path), as
+are non-contiguous tensors, wrong dtypes and tensors whose first dimension is not P.  n_points_cloned, n_points_split and
+n_points_pruned are stored as Python ints.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch import nn
+
+from diff_gaussian_rasterization import _C
+
+__all__ = ["densify_and_prune", "prune", "prune_points"]
+
+_lib = _C._lib
+if not hasattr(_lib, "r3dgs_densify_plan"):
+    raise ImportError(f"{_C._LIB_PATH} has no densification (r3dgs_densify_plan): rebuild it with build.py")
+
+COPY, ZERO_NEW, XYZ, SCALING = 0, 1, 2, 3     # R3DGS_DENSIFY_*
+MAX_TENSORS, TOTALS = 32, 8
+
+
+class _Tensor(C.Structure):   # r3dgs_densify_tensor
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int), ("kind", C.c_int)]
+
+
+_vp, _i, _f = C.c_void_p, C.c_int, C.c_float
+_lib.r3dgs_densify_workspace_bytes.restype = C.c_size_t
+_lib.r3dgs_densify_workspace_bytes.argtypes = [_i]
+_lib.r3dgs_densify_plan.restype = _i
+_lib.r3dgs_densify_plan.argtypes = [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp]
+_lib.r3dgs_prune_plan.restype = _i
+_lib.r3dgs_prune_plan.argtypes = [_i, _vp, _vp, _vp, _vp]
+_lib.r3dgs_densify_move.restype = _i
+_lib.r3dgs_densify_move.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_Tensor), _vp, _vp, _vp, _vp, _vp, _vp]
+
+_GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
+           ("scaling", "_scaling"), ("rotation", "_rotation"))
+_NAMES = {name for name, _ in _GROUPS}
+_CHILD_KIND = {"xyz": XYZ, "scaling": SCALING}
+_ACCUMULATORS = ("xyz_gradient_accum", "denom", "max_radii2D")
+
+
+def _check(what, name, t, dtype, P):
+    """dtype and shape first, so that a wrong tensor is named for what is wrong with it wherever it lives"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: {name} is {t.dtype}, expected {dtype}")
+    if t.dim() < 1 or t.shape[0] != P:
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected [P, ...] with P = {P}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} is not contiguous; densification takes contiguous tensors only")
+
+
+def _check_extra(what, name, t, dtype, shape, shape_text):
+    """noise and mask: looked at before the model's tensors, except for where they live"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError(f"{what}: {name} must be a {dtype} tensor")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape_text}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} is not contiguous; densification takes contiguous tensors only")
+
+
+def _model_size(what, pc):
+    xyz = pc._xyz
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2:
+        raise TypeError(f"{what}: pc._xyz must be a [P,3] tensor")
+    return xyz.shape[0]
+
+
+def _collect(what, pc, store_grads, accumulators):
+    """-> (P, device, entries): entries are (kind, source tensor, setter of the new tensor), in table order.  Every refusal
+    comes from here, before anything is launched or changed: dtypes, shapes and layouts of all tensors first, then where
+    they live."""
+    P = _model_size(what, pc)
+    xyz = pc._xyz
+    widths = {"xyz": (3,), "opacity": (1,), "scaling": (3,), "rotation": (4,)}
+    groups = {}
+    for group in pc.optimizer.param_groups:
+        name = group.get("name")
+        if name not in _NAMES or len(group["params"]) != 1:
+            raise ValueError(f"{what}: the optimizer must have one single-parameter group per name in {sorted(_NAMES)}; "
+                             f"found {name!r} with {len(group['params'])} parameters")
+        groups[name] = group
+    entries = []
+    for name, attr in _GROUPS:
+        if name not in groups:
+            raise ValueError(f"{what}: the optimizer has no group named {name!r}")
+        group = groups[name]
+        p = group["params"][0]
+        if getattr(pc, attr) is not p:
+            raise ValueError(f"{what}: pc.{attr} is not the parameter of the optimizer's group {name!r}")
+        _check(what, f"pc.{attr}", p, torch.float32, P)
+        if name in widths and tuple(p.shape[1:]) != widths[name]:
+            raise ValueError(f"{what}: pc.{attr} has shape {tuple(p.shape)}, expected {(P,) + widths[name]}")
+        state = pc.optimizer.state.get(p, None)
+        entries.append((_CHILD_KIND.get(name, COPY), p.detach(), ("param", group, attr, state)))
+        if state is not None:
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key not in state:
+                    raise ValueError(f"{what}: the optimizer state of group {name!r} has no {key}")
+                _check(what, f"{key} of group {name!r}", state[key], torch.float32, P)
+                if state[key].shape != p.shape:
+                    raise ValueError(f"{what}: {key} of group {name!r} has shape {tuple(state[key].shape)}, its parameter "
+                                     f"{tuple(p.shape)}")
+                entries.append((ZERO_NEW, state[key], ("state", state, key)))
+            if store_grads:
+                if p.grad is None:
+                    raise ValueError(f"{what}: store_grads=True but pc.{attr} has no .grad")
+                _check(what, f"pc.{attr}.grad", p.grad, torch.float32, P)
+                if p.grad.shape != p.shape:
+                    raise ValueError(f"{what}: pc.{attr}.grad has shape {tuple(p.grad.shape)}, its parameter {tuple(p.shape)}")
+                entries.append((ZERO_NEW, p.grad, ("grad", group)))
+    _check(what, "pc._degrees", pc._degrees, torch.int32, P)
+    entries.append((COPY, pc._degrees, ("attr", "_degrees")))
+    for name in _ACCUMULATORS:
+        t = getattr(pc, name)
+        _check(what, f"pc.{name}", t, torch.float32, P)
+        if t.numel() != P:
+            raise ValueError(f"{what}: pc.{name} has shape {tuple(t.shape)}, expected {P} elements")
+        if accumulators:
+            entries.append((COPY, t, ("attr", name)))
+    dev = xyz.device
+    for t in [e[1] for e in entries] + [getattr(pc, name) for name in _ACCUMULATORS]:
+        if not t.is_cuda:
+            raise RuntimeError(f"{what}: the model has host tensors; densification needs device tensors (no CPU path)")
+        if t.device != dev:
+            raise ValueError(f"{what}: a tensor is on {t.device}, pc._xyz on {dev}")
+    if len(entries) > MAX_TENSORS:
+        raise RuntimeError(f"{what}: more than {MAX_TENSORS} tensors")
+    return P, dev, entries
+
+
+def _f32(x):
+    """a Python double rounded to float32 once, as torch rounds the scalar it compares a float32 tensor with"""
+    return float(np.float32(x))
+
+
+def _run(what, pc, entries, P, dev, plan, noise, zero_accumulators):
+    """plan (enqueue) -> the one read-back -> new tensors -> move (enqueue) -> hand the new tensors to the model and the
+    optimizer.  -> the eight totals."""
+    with torch.no_grad(), _C._on_device(dev):
+        stream = _C._stream()
+        if P > 0:
+            ws = torch.empty((int(_lib.r3dgs_densify_workspace_bytes(P)),), dtype=torch.uint8, device=dev)
+            totals_dev = torch.empty((TOTALS,), dtype=torch.int32, device=dev)
+            _C._check(plan(ws.data_ptr(), totals_dev.data_ptr(), stream), what)
+            totals = totals_dev.tolist()          # the only host wait of the call: the new sizes
+        else:
+            ws, totals = None, [0] * TOTALS
+        nA, nB, nC, _, _, _, _, rows = totals
+        new = [torch.empty((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for _, t, _ in entries]
+        if rows > 0:
+            table = (_Tensor * len(entries))()
+            for slot, (kind, t, _), out in zip(table, entries, new):
+                words = t.numel() // P
+                slot.src, slot.dst, slot.row_words, slot.kind = (t.data_ptr() if words else None), \
+                    (out.data_ptr() if words else None), words, kind
+            _C._check(_lib.r3dgs_densify_move(P, nA, nB, nC, len(entries), table, pc._xyz.data_ptr(), pc._scaling.data_ptr(),
+                                              pc._rotation.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                              ws.data_ptr(), stream), what)
+        # hand-over, as _prune_optimizer / cat_tensors_to_optimizer: the same state dict under the new parameter
+        params = {}
+        for (_, _, dest), out in zip(entries, new):
+            if dest[0] == "param":
+                _, group, attr, state = dest
+                old = group["params"][0]
+                if state is not None:
+                    del pc.optimizer.state[old]
+                p = nn.Parameter(out.requires_grad_(True))
+                group["params"][0] = p
+                if state is not None:
+                    pc.optimizer.state[p] = state
+                setattr(pc, attr, p)
+                params[id(group)] = p
+            elif dest[0] == "state":
+                dest[1][dest[2]] = out
+            elif dest[0] == "grad":
+                params[id(dest[1])].grad = out
+            else:
+                setattr(pc, dest[1], out)
+        if zero_accumulators:   # densification_postfix, gaussian_model.py:617-620
+            pc.xyz_gradient_accum = torch.zeros((rows, 1), device=dev)
+            pc.density_gradient_accum = torch.zeros((rows, 1), device=dev)
+            pc.denom = torch.zeros((rows, 1), device=dev)
+            pc.max_radii2D = torch.zeros((rows,), device=dev)
+    return totals
+
+
+def densify_and_prune(pc, max_grad, min_opacity, extent, max_screen_size, densification_statistics_dict, store_grads=False,
+                      noise=None, generator=None):
+    """GaussianModel.densify_and_prune (scene/gaussian_model.py:670-682) in three launches and one host wait; see the module
+    docstring for the semantics, the kept quirks and the noise convention.  Not capturable in a graph: the sizes change."""
+    what = "densify_and_prune"
+    if not max_grad > 0:
+        raise ValueError(f"{what}: max_grad = {max_grad!r} must be > 0 (the reference takes the split decision after the clones "
+                         "were appended with a zero gradient: max_grad <= 0 would split the clones)")
+    if noise is not None:
+        P = _model_size(what, pc)
+        _check_extra(what, "noise", noise, torch.float32, (2, P, 3), f"(2, P, 3) with P = {P}")
+    P, dev, entries = _collect(what, pc, store_grads, accumulators=False)
+    if noise is None:
+        noise = torch.randn((2, P, 3), generator=generator, device=dev, dtype=torch.float32)
+    elif noise.device != dev:
+        raise RuntimeError(f"{what}: noise is on {noise.device}, pc._xyz on {dev}; densification needs device tensors "
+                           "(no CPU path)")
+    thresholds = (_f32(max_grad), _f32(pc.percent_dense * extent), _f32(min_opacity), 1 if max_screen_size else 0,
+                  _f32(max_screen_size) if max_screen_size else 0.0, _f32(0.1 * extent))
+
+    def plan(ws, totals, stream):
+        return _lib.r3dgs_densify_plan(P, 1, pc.xyz_gradient_accum.data_ptr(), pc.denom.data_ptr(), pc._scaling.data_ptr(),
+                                       pc._opacity.data_ptr(), pc.max_radii2D.data_ptr(), *thresholds, ws, totals, stream)
+    totals = _run(what, pc, entries, P, dev, plan, noise, zero_accumulators=True)
+    densification_statistics_dict["n_points_pruned"] = totals[6]
+    densification_statistics_dict["n_points_cloned"] = totals[4]
+    densification_statistics_dict["n_points_split"] = totals[5]
+
+
+def prune(pc, min_opacity, extent, max_screen_size, densification_statistics_dict, store_grads=False):
+    """GaussianModel.prune (scene/gaussian_model.py:684-691) called on its own: the screen-size term sees max_radii2D as it
+    is, and the three accumulators are compacted with the parameters."""
+    what = "prune"
+    P, dev, entries = _collect(what, pc, store_grads, accumulators=True)
+    thresholds = (1.0, 0.0, _f32(min_opacity), 1 if max_screen_size else 0, _f32(max_screen_size) if max_screen_size else 0.0,
+                  _f32(0.1 * extent))
+
+    def plan(ws, totals, stream):
+        return _lib.r3dgs_densify_plan(P, 0, None, None, pc._scaling.data_ptr(), pc._opacity.data_ptr(),
+                                       pc.max_radii2D.data_ptr(), *thresholds, ws, totals, stream)
+    totals = _run(what, pc, entries, P, dev, plan, None, zero_accumulators=False)
+    densification_statistics_dict["n_points_pruned"] = totals[6]
+
+
+def prune_points(pc, mask, store_grads=False):
+    """GaussianModel.prune_points (scene/gaussian_model.py:553-568): removes the Gaussians with mask True.  mask: bool [P] on
+    the device (what mercy_points builds in torch)."""
+    what = "prune_points"
+    P = _model_size(what, pc)
+    _check_extra(what, "mask", mask, torch.bool, (P,), f"(P,) with P = {P}")
+    P, dev, entries = _collect(what, pc, store_grads, accumulators=True)
+    if mask.device != dev:
+        raise RuntimeError(f"{what}: mask is on {mask.device}, pc._xyz on {dev}; densification needs device tensors "
+                           "(no CPU path)")
+
+    def plan(ws, totals, stream):
+        return _lib.r3dgs_prune_plan(P, mask.data_ptr(), ws, totals, stream)
+    _run(what, pc, entries, P, dev, plan, None, zero_accumulators=False)
