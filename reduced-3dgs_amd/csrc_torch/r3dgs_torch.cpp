@@ -30,6 +30,8 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "r3dgs_loss.h"
@@ -42,102 +44,82 @@ namespace {
 
 using at::Tensor;
 
-// entry points of the loaded libr3dgs_hip.so (types taken from the C header)
-struct Api {
-#define R3_FN(name) decltype(&::name) name = nullptr;
-    R3_FN(r3dgs_last_error)
-    R3_FN(r3dgs_version)
-    R3_FN(r3dgs_geometry_bytes)
-    R3_FN(r3dgs_geometry_bytes_lean)
-    R3_FN(r3dgs_binning_bytes)
-    R3_FN(r3dgs_image_bytes)
-    R3_FN(r3dgs_forward_hint)
-    R3_FN(r3dgs_reserve_hint_view)
-    R3_FN(r3dgs_forward_reserved)
-    R3_FN(r3dgs_pass_query)
-    R3_FN(r3dgs_backward)
-    R3_FN(r3dgs_mark_visible)
-    R3_FN(r3dgs_l1_ssim_workspace_bytes)
-    R3_FN(r3dgs_l1_ssim_forward)
-    R3_FN(r3dgs_l1_ssim_backward)
-    R3_FN(r3dgs_l1_workspace_bytes)
-    R3_FN(r3dgs_l1_forward)
-    R3_FN(r3dgs_l1_backward)
-    R3_FN(r3dgs_adam_step)
-    R3_FN(r3dgs_adam_step_capturable)
-    R3_FN(r3dgs_adam_step_visible)
-    R3_FN(r3dgs_adam_step_capturable_visible)
-    R3_FN(r3dgs_forward_params)
-    R3_FN(r3dgs_forward_params_reserved)
-    R3_FN(r3dgs_backward_params)
-    R3_FN(r3dgs_activate_params)
-    R3_FN(r3dgs_train_stats_workspace_bytes)
-    R3_FN(r3dgs_visible_means)
-    R3_FN(r3dgs_alpha_regul_backward)
-    R3_FN(r3dgs_densification_stats)
-    R3_FN(r3dgs_quantised_codebook_grad_workspace_bytes)
-    R3_FN(r3dgs_quantised_codebook_grad)
-#undef R3_FN
+// The entry points of the loaded libr3dgs_hip.so this module calls, once: X(name, required).  An optional one belongs to a
+// family an older A/B build of the library lacks; its calls then refuse (need()).
+#define R3_ENTRY_POINTS(X)                                    \
+    X(r3dgs_last_error, true)                                 \
+    X(r3dgs_version, true)                                    \
+    X(r3dgs_geometry_bytes, true)                             \
+    X(r3dgs_geometry_bytes_lean, true)                        \
+    X(r3dgs_binning_bytes, true)                              \
+    X(r3dgs_image_bytes, true)                                \
+    X(r3dgs_forward_hint, true)                               \
+    X(r3dgs_reserve_hint_view, true)                          \
+    X(r3dgs_forward_reserved, true)                           \
+    X(r3dgs_pass_query, true)                                 \
+    X(r3dgs_backward, true)                                   \
+    X(r3dgs_mark_visible, true)                               \
+    X(r3dgs_l1_ssim_workspace_bytes, false)                   \
+    X(r3dgs_l1_ssim_forward, false)                           \
+    X(r3dgs_l1_ssim_backward, false)                          \
+    X(r3dgs_l1_workspace_bytes, false)                        \
+    X(r3dgs_l1_forward, false)                                \
+    X(r3dgs_l1_backward, false)                               \
+    X(r3dgs_adam_step, false)                                 \
+    X(r3dgs_adam_step_capturable, false)                      \
+    X(r3dgs_adam_step_visible, false)                         \
+    X(r3dgs_adam_step_capturable_visible, false)              \
+    X(r3dgs_forward_params, false)                            \
+    X(r3dgs_forward_params_reserved, false)                   \
+    X(r3dgs_backward_params, false)                           \
+    X(r3dgs_activate_params, false)                           \
+    X(r3dgs_train_stats_workspace_bytes, false)               \
+    X(r3dgs_visible_means, false)                             \
+    X(r3dgs_alpha_regul_backward, false)                      \
+    X(r3dgs_densification_stats, false)                       \
+    X(r3dgs_quantised_codebook_grad_workspace_bytes, false)   \
+    X(r3dgs_quantised_codebook_grad, false)
+
+struct Api {   // (types taken from the C headers)
+#define R3_MEMBER(name, required) decltype(&::name) name = nullptr;
+    R3_ENTRY_POINTS(R3_MEMBER)
+#undef R3_MEMBER
     bool bound = false;
 } api;
 
+// what _C.py builds bind()'s address dict from: [(name, required)]
+std::vector<std::pair<std::string, bool>> entry_points()
+{
+#define R3_LIST(name, required) {#name, required},
+    return {R3_ENTRY_POINTS(R3_LIST)};
+#undef R3_LIST
+}
+
 void bind(const std::map<std::string, uintptr_t>& addr)
 {
-#define R3_FN(name)                                                                         \
-    {                                                                                       \
-        auto it = addr.find(#name);                                                         \
-        if (it == addr.end() || !it->second) throw std::runtime_error("bind: no " #name);   \
-        api.name = reinterpret_cast<decltype(api.name)>(it->second);                        \
+#define R3_BIND(name, required)                                                                    \
+    {                                                                                              \
+        auto it = addr.find(#name);                                                                \
+        const uintptr_t at = it == addr.end() ? 0 : it->second;                                    \
+        if (required && !at) throw std::runtime_error("bind: no " #name);                          \
+        api.name = reinterpret_cast<decltype(api.name)>(at);                                       \
     }
-    R3_FN(r3dgs_last_error)
-    R3_FN(r3dgs_version)
-    R3_FN(r3dgs_geometry_bytes)
-    R3_FN(r3dgs_geometry_bytes_lean)
-    R3_FN(r3dgs_binning_bytes)
-    R3_FN(r3dgs_image_bytes)
-    R3_FN(r3dgs_forward_hint)
-    R3_FN(r3dgs_reserve_hint_view)
-    R3_FN(r3dgs_forward_reserved)
-    R3_FN(r3dgs_pass_query)
-    R3_FN(r3dgs_backward)
-    R3_FN(r3dgs_mark_visible)
-#undef R3_FN
-    // the fused loss (r3dgs_loss.h) is optional: an older A/B build of the library has none, and its calls then refuse
-#define R3_OPT(name)                                                                        \
-    {                                                                                       \
-        auto it = addr.find(#name);                                                         \
-        api.name = it == addr.end() ? nullptr : reinterpret_cast<decltype(api.name)>(it->second); \
-    }
-    R3_OPT(r3dgs_l1_ssim_workspace_bytes)
-    R3_OPT(r3dgs_l1_ssim_forward)
-    R3_OPT(r3dgs_l1_ssim_backward)
-    R3_OPT(r3dgs_l1_workspace_bytes)
-    R3_OPT(r3dgs_l1_forward)
-    R3_OPT(r3dgs_l1_backward)
-    R3_OPT(r3dgs_adam_step)
-    R3_OPT(r3dgs_adam_step_capturable)
-    R3_OPT(r3dgs_adam_step_visible)
-    R3_OPT(r3dgs_adam_step_capturable_visible)
-    // the raw-parameter entry points: absent from an older A/B build, whose calls then refuse
-    R3_OPT(r3dgs_forward_params)
-    R3_OPT(r3dgs_forward_params_reserved)
-    R3_OPT(r3dgs_backward_params)
-    R3_OPT(r3dgs_activate_params)
-    // the training statistics (r3dgs_trainstats.h): likewise
-    R3_OPT(r3dgs_train_stats_workspace_bytes)
-    R3_OPT(r3dgs_visible_means)
-    R3_OPT(r3dgs_alpha_regul_backward)
-    R3_OPT(r3dgs_densification_stats)
-    // the adjoint of the codebook lookup (r3dgs_quantised.h): likewise
-    R3_OPT(r3dgs_quantised_codebook_grad_workspace_bytes)
-    R3_OPT(r3dgs_quantised_codebook_grad)
-#undef R3_OPT
+    R3_ENTRY_POINTS(R3_BIND)
+#undef R3_BIND
     api.bound = true;
 }
 
 void need_bound()
 {
     if (!api.bound) throw std::runtime_error("r3dgs torch binding: not bound to libr3dgs_hip.so (import diff_gaussian_rasterization._C)");
+}
+
+// an entry point of an optional family: `what` names the family the loaded library lacks
+template <class Fn>
+void need(Fn* entry, const char* what)
+{
+    need_bound();
+    if (!entry) throw std::runtime_error(std::string("the loaded libr3dgs_hip.so has no ") + what + ": rebuild it with build.py");
 }
 
 [[noreturn]] void fail(const char* what)
@@ -153,20 +135,26 @@ const T* opt_ptr(const Tensor& t)
     return t.defined() && t.numel() != 0 ? t.data_ptr<T>() : nullptr;
 }
 
-Tensor dev_f32(const Tensor& t, const c10::Device& dev)
+// a state blob (or any byte buffer) as the C ABI takes it
+char* blob_ptr(const Tensor& t) { return t.defined() && t.numel() != 0 ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; }
+
+// an input as the library reads it: on `dev`, of `type`, contiguous (copied if it is not); undefined for an absent one
+Tensor dev_as(const Tensor& t, const c10::Device& dev, at::ScalarType type, const char* type_name)
 {
     if (!t.defined() || t.numel() == 0) return Tensor();
     if (t.device() != dev) throw std::runtime_error("expected a tensor on " + dev.str() + ", got " + t.device().str());
-    if (t.scalar_type() != at::kFloat) throw std::runtime_error(std::string("expected float32, got ") + c10::toString(t.scalar_type()));
+    if (t.scalar_type() != type) throw std::runtime_error(std::string("expected ") + type_name + ", got " + c10::toString(t.scalar_type()));
     return t.contiguous();
 }
+Tensor dev_f32(const Tensor& t, const c10::Device& dev) { return dev_as(t, dev, at::kFloat, "float32"); }
+Tensor dev_i32(const Tensor& t, const c10::Device& dev) { return dev_as(t, dev, at::kInt, "int32"); }
 
-Tensor dev_i32(const Tensor& t, const c10::Device& dev)
+// a backward's result for P == 0: zeros of the given shapes
+std::vector<Tensor> zero_grads(const at::TensorOptions& f32, std::initializer_list<std::vector<int64_t>> shapes)
 {
-    if (!t.defined() || t.numel() == 0) return Tensor();
-    if (t.device() != dev) throw std::runtime_error("expected a tensor on " + dev.str() + ", got " + t.device().str());
-    if (t.scalar_type() != at::kInt) throw std::runtime_error(std::string("expected int32, got ") + c10::toString(t.scalar_type()));
-    return t.contiguous();
+    std::vector<Tensor> out;
+    for (const std::vector<int64_t>& shape : shapes) out.push_back(at::zeros(shape, f32));
+    return out;
 }
 
 void* cur_stream(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
@@ -277,10 +265,7 @@ std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, co
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
     const int M = (sh.defined() && sh.numel() != 0) ? (int)sh.size(1) : 0;
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    if (P == 0) {
-        return {at::zeros({0, 3}, f32), at::zeros({0, 3}, f32), at::zeros({0, 1}, f32), at::zeros({0, 3}, f32),
-                at::zeros({0, 6}, f32), at::zeros({0, M, 3}, f32), at::zeros({0, 3}, f32), at::zeros({0, 4}, f32)};
-    }
+    if (P == 0) return zero_grads(f32, {{0, 3}, {0, 3}, {0, 1}, {0, 3}, {0, 6}, {0, M, 3}, {0, 3}, {0, 4}});
     Tensor dL_dmeans3D = at::empty({P, 3}, f32), dL_dmeans2D = at::empty({P, 3}, f32), dL_dcolors = at::empty({P, 3}, f32);
     Tensor dL_dopacity = at::empty({P, 1}, f32), dL_dcov3D = at::empty({P, 6}, f32), dL_dsh = at::empty({P, M, 3}, f32);
     Tensor dL_dscales = at::empty({P, 3}, f32), dL_drotations = at::empty({P, 4}, f32);
@@ -290,17 +275,15 @@ std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, co
     const Tensor vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev), cp = dev_f32(campos, dev);
     const Tensor g = dev_f32(dL_dout_color, dev), shc = dev_f32(sh, dev), deg = dev_i32(degrees, dev), rad = dev_i32(radii, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    void* stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-    auto blob = [](const Tensor& t) { return t.defined() && t.numel() != 0 ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
     const int st = api.r3dgs_backward(
         P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, opt_ptr<float>(m3), opt_ptr<float>(shc),
         opt_ptr<float>(col), opt_ptr<float>(sc), (float)scale_modifier, opt_ptr<float>(rot), opt_ptr<float>(cov),
         opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy, opt_ptr<int>(rad),
-        blob(geomBuffer), blob(binningBuffer), blob(imageBuffer), opt_ptr<float>(g), dL_dmeans2D.data_ptr<float>(),
+        blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g), dL_dmeans2D.data_ptr<float>(),
         dL_dconic.defined() ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
         dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(),
         M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
-        (float)lambda_sh_sparsity, debug ? 1 : 0, stream);
+        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev));
     if (st < 0) fail("rasterize_gaussians_backward");
     std::vector<Tensor> out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
     if (want_conic) out.push_back(dL_dconic);
@@ -310,12 +293,7 @@ std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, co
 // ---- raster from the model's raw parameters (r3dgs_*_params): the same marshalling as diff_gaussian_rasterization/_C.py's
 // rasterize_gaussian_params*; refusals (shapes, dtypes, contiguity) carry the same messages.
 
-void need_params()
-{
-    need_bound();
-    if (!api.r3dgs_forward_params_reserved)
-        throw std::runtime_error("the loaded libr3dgs_hip.so has no raw-parameter entry points: rebuild it with build.py");
-}
+void need_params() { need(api.r3dgs_forward_params_reserved, "raw-parameter entry points"); }
 
 // a raw parameter tensor: on `dev`, fp32, contiguous AS PASSED (a copy would defeat the point of the path)
 const float* param_ptr(const Tensor& t, const c10::Device& dev, const char* name)
@@ -449,10 +427,7 @@ std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz,
     const int P = p.P, M = p.M;
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    if (P == 0) {
-        return {at::zeros({0, 3}, f32), at::zeros({0, 1}, f32), at::zeros({0, 3}, f32), at::zeros({0, 1, 3}, f32),
-                at::zeros({0, M - 1, 3}, f32), at::zeros({0, 3}, f32), at::zeros({0, 4}, f32)};
-    }
+    if (P == 0) return zero_grads(f32, {{0, 3}, {0, 1}, {0, 3}, {0, 1, 3}, {0, M - 1, 3}, {0, 3}, {0, 4}});
     Tensor dL_dmeans3D = at::empty({P, 3}, f32), dL_dmeans2D = at::empty({P, 3}, f32), dL_dopacity = at::empty({P, 1}, f32);
     Tensor dL_ddc = at::empty({P, 1, 3}, f32), dL_drest = at::empty({P, M - 1, 3}, f32);
     Tensor dL_dscaling = at::empty({P, 3}, f32), dL_drotation = at::empty({P, 4}, f32);
@@ -461,11 +436,10 @@ std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz,
     const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
     const Tensor cp = dev_f32(campos, dev), g = dev_f32(dL_dout_color, dev), deg = dev_i32(degrees, dev), rad = dev_i32(radii, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    auto blob = [](const Tensor& t) { return t.defined() && t.numel() != 0 ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
     const int st = api.r3dgs_backward_params(
         P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest, p.scaling, (float)scale_modifier,
         p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy,
-        opt_ptr<int>(rad), blob(geomBuffer), blob(binningBuffer), blob(imageBuffer), opt_ptr<float>(g),
+        opt_ptr<int>(rad), blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g),
         dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), scratch.data_ptr<float>(),
         dL_dmeans3D.data_ptr<float>(), scratch.data_ptr<float>() + 3 * (size_t)P, dL_ddc.data_ptr<float>(),
         M > 1 ? dL_drest.data_ptr<float>() : nullptr, dL_dscaling.data_ptr<float>(), dL_drotation.data_ptr<float>(),
@@ -500,9 +474,7 @@ Tensor quantised_codebook_grad(const Tensor& geom_ids, const Tensor& sh_ids, con
                                const Tensor& dL_dfeatures_rest, const Tensor& dL_dopacity, const Tensor& dL_dscaling,
                                const Tensor& dL_drotation)
 {
-    need_bound();
-    if (!api.r3dgs_quantised_codebook_grad || !api.r3dgs_quantised_codebook_grad_workspace_bytes)
-        throw std::runtime_error("the loaded libr3dgs_hip.so has no r3dgs_quantised_codebook_grad: rebuild it with build.py");
+    need(api.r3dgs_quantised_codebook_grad_workspace_bytes, "r3dgs_quantised_codebook_grad");
     const c10::Device dev = geom_ids.device();
     if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
     if (geom_ids.scalar_type() != at::kByte || geom_ids.dim() != 2 || geom_ids.size(1) != 8)
@@ -558,7 +530,7 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
         if (api.r3dgs_mark_visible(P, opt_ptr<float>(m3), opt_ptr<float>(vm), opt_ptr<float>(pm),
                                reinterpret_cast<unsigned char*>(present.data_ptr()),
-                               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream()) < 0)
+                               cur_stream(dev)) < 0)
             fail("mark_visible");
     }
     return present;
@@ -567,11 +539,7 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
 // ---- fused L1 + D-SSIM loss (r3dgs_loss.h): the same calls as diff_gaussian_rasterization/_C.py's l1_ssim_* / l1_*;
 // r3dgs_loss.py has checked the inputs (device fp32, contiguous, same shape).  Absent optional tensors are empty.
 
-void need_loss()
-{
-    need_bound();
-    if (!api.r3dgs_l1_ssim_forward) throw std::runtime_error("the loaded libr3dgs_hip.so has no fused loss: rebuild it with build.py");
-}
+void need_loss() { need(api.r3dgs_l1_ssim_workspace_bytes, "fused loss"); }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> l1_ssim_forward(
     const Tensor& img1, const Tensor& img2, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials,
@@ -642,67 +610,33 @@ Tensor l1_backward(const Tensor& x, const Tensor& y, const Tensor& grad)
 // ---- fused Adam step (r3dgs_optim.h): the same calls as diff_gaussian_rasterization/_C.py's adam_step*; r3dgs_optim.py has
 // checked the tensors (one device, fp32, contiguous, matching sizes).  Scalars arrive as doubles and are rounded to fp32 once.
 
-void need_optim()
-{
-    need_bound();
-    if (!api.r3dgs_adam_step) throw std::runtime_error("the loaded libr3dgs_hip.so has no fused Adam: rebuild it with build.py");
-}
+template <class Seg>
+constexpr bool is_capturable = std::is_same<Seg, r3dgs_adam_capturable_segment>::value;
 
-void check_rows(size_t n, const std::vector<Tensor>& g, const std::vector<Tensor>& m, const std::vector<Tensor>& v,
-                size_t n_scalars, size_t per_row)
+// the segments of a step from its tensor lists: six scalars per tensor (r3dgs_adam_segment) or, with steps and lrs, four
+// (r3dgs_adam_capturable_segment: lr_value, beta1, beta2, eps; lrs[i] an empty tensor or a 0-d device float32 lr)
+template <class Seg>
+std::vector<Seg> pack(const char* what, const std::vector<Tensor>& params, const std::vector<Tensor>& grads,
+                      const std::vector<Tensor>& exp_avgs, const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars,
+                      const std::vector<Tensor>* steps = nullptr, const std::vector<Tensor>* lrs = nullptr)
 {
-    if (g.size() != n || m.size() != n || v.size() != n || n_scalars != per_row * n)
+    constexpr size_t per = is_capturable<Seg> ? 4 : 6;
+    const size_t n = params.size();
+    if (grads.size() != n || exp_avgs.size() != n || exp_avg_sqs.size() != n || scalars.size() != per * n)
         throw std::runtime_error("adam_step: list lengths differ");
-}
-
-void adam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
-               const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars)
-{
-    need_optim();
-    const size_t n = params.size();
-    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 6);
-    if (n == 0) return;
-    const c10::Device dev = params[0].device();
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    std::vector<r3dgs_adam_segment> segs(n);
+    if (is_capturable<Seg> && (steps->size() != n || lrs->size() != n)) throw std::runtime_error(std::string(what) + ": list lengths differ");
+    std::vector<Seg> segs(n);
     for (size_t i = 0; i < n; i++) {
-        const double* s = &scalars[6 * i];
-        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
-                   exp_avg_sqs[i].data_ptr<float>(), (long long)params[i].numel(), (float)s[0], (float)s[1], (float)s[2],
-                   (float)s[3], (float)s[4], (float)s[5]};
+        const double* s = &scalars[per * i];
+        float *p = params[i].data_ptr<float>(), *g = grads[i].data_ptr<float>(), *m = exp_avgs[i].data_ptr<float>(),
+              *v = exp_avg_sqs[i].data_ptr<float>();
+        const long long count = params[i].numel();
+        if constexpr (is_capturable<Seg>)
+            segs[i] = {p, g, m, v, (*steps)[i].data_ptr<float>(), opt_ptr<float>((*lrs)[i]), count, s[0], s[1], s[2], s[3]};
+        else
+            segs[i] = {p, g, m, v, count, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4], (float)s[5]};
     }
-    if (api.r3dgs_adam_step((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step");
-}
-
-// scalars: lr_value, beta1, beta2, eps per row; lrs[i] an empty tensor or a 0-d device float32 lr
-void adam_step_capturable(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
-                          const std::vector<Tensor>& exp_avg_sqs, const std::vector<Tensor>& steps, const std::vector<Tensor>& lrs,
-                          const std::vector<double>& scalars)
-{
-    need_optim();
-    const size_t n = params.size();
-    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 4);
-    if (steps.size() != n || lrs.size() != n) throw std::runtime_error("adam_step_capturable: list lengths differ");
-    if (n == 0) return;
-    const c10::Device dev = params[0].device();
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    std::vector<r3dgs_adam_capturable_segment> segs(n);
-    for (size_t i = 0; i < n; i++) {
-        const double* s = &scalars[4 * i];
-        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
-                   exp_avg_sqs[i].data_ptr<float>(), steps[i].data_ptr<float>(), opt_ptr<float>(lrs[i]),
-                   (long long)params[i].numel(), s[0], s[1], s[2], s[3]};
-    }
-    if (api.r3dgs_adam_step_capturable((int)n, segs.data(), cur_stream(dev)) < 0) fail("adam_step_capturable");
-}
-
-// ---- the visibility-gated step: radii is the rasterizer's device int32 [P], every tensor [P, ...]
-
-void need_optim_visible()
-{
-    need_bound();
-    if (!api.r3dgs_adam_step_visible)
-        throw std::runtime_error("the loaded libr3dgs_hip.so has no visibility-gated Adam: rebuild it with build.py");
+    return segs;
 }
 
 // floats per Gaussian of each tensor (the C ABI checks n == P * row_len again)
@@ -717,26 +651,53 @@ std::vector<int> row_lens(const std::vector<Tensor>& params, long long P, const 
     return out;
 }
 
-void adam_step_visible(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
-                       const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars, const Tensor& radii)
+// the dense step of the segments, or -- radii given: the rasterizer's device int32 [P], every tensor [P, ...] -- the
+// visibility-gated one
+template <class Seg>
+void adam_run(const char* what, const std::vector<Tensor>& params, const std::vector<Seg>& segs, const Tensor* radii = nullptr)
 {
-    need_optim_visible();
-    const size_t n = params.size();
-    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 6);
+    const int n = (int)segs.size();
     if (n == 0) return;
     const c10::Device dev = params[0].device();
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const long long P = radii.numel();
-    const std::vector<int> lens = row_lens(params, P, "adam_step_visible");
-    std::vector<r3dgs_adam_segment> segs(n);
-    for (size_t i = 0; i < n; i++) {
-        const double* s = &scalars[6 * i];
-        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
-                   exp_avg_sqs[i].data_ptr<float>(), (long long)params[i].numel(), (float)s[0], (float)s[1], (float)s[2],
-                   (float)s[3], (float)s[4], (float)s[5]};
+    int st;
+    if (radii) {
+        const long long P = radii->numel();
+        const std::vector<int> lens = row_lens(params, P, what);
+        if constexpr (is_capturable<Seg>)
+            st = api.r3dgs_adam_step_capturable_visible(n, segs.data(), lens.data(), opt_ptr<int>(*radii), P, cur_stream(dev));
+        else
+            st = api.r3dgs_adam_step_visible(n, segs.data(), lens.data(), opt_ptr<int>(*radii), P, cur_stream(dev));
+    } else if constexpr (is_capturable<Seg>) {
+        st = api.r3dgs_adam_step_capturable(n, segs.data(), cur_stream(dev));
+    } else {
+        st = api.r3dgs_adam_step(n, segs.data(), cur_stream(dev));
     }
-    if (api.r3dgs_adam_step_visible((int)n, segs.data(), lens.data(), opt_ptr<int>(radii), P, cur_stream(dev)) < 0)
-        fail("adam_step_visible");
+    if (st < 0) fail(what);
+}
+
+void adam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+               const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars)
+{
+    need(api.r3dgs_adam_step, "fused Adam");
+    adam_run("adam_step", params, pack<r3dgs_adam_segment>("adam_step", params, grads, exp_avgs, exp_avg_sqs, scalars));
+}
+
+void adam_step_capturable(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+                          const std::vector<Tensor>& exp_avg_sqs, const std::vector<Tensor>& steps, const std::vector<Tensor>& lrs,
+                          const std::vector<double>& scalars)
+{
+    need(api.r3dgs_adam_step_capturable, "fused Adam");
+    adam_run("adam_step_capturable", params,
+             pack<r3dgs_adam_capturable_segment>("adam_step_capturable", params, grads, exp_avgs, exp_avg_sqs, scalars, &steps, &lrs));
+}
+
+void adam_step_visible(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
+                       const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& scalars, const Tensor& radii)
+{
+    need(api.r3dgs_adam_step_visible, "visibility-gated Adam");
+    adam_run("adam_step_visible", params, pack<r3dgs_adam_segment>("adam_step_visible", params, grads, exp_avgs, exp_avg_sqs, scalars),
+             &radii);
 }
 
 void adam_step_capturable_visible(const std::vector<Tensor>& params, const std::vector<Tensor>& grads,
@@ -744,35 +705,18 @@ void adam_step_capturable_visible(const std::vector<Tensor>& params, const std::
                                   const std::vector<Tensor>& steps, const std::vector<Tensor>& lrs,
                                   const std::vector<double>& scalars, const Tensor& radii)
 {
-    need_optim_visible();
-    const size_t n = params.size();
-    check_rows(n, grads, exp_avgs, exp_avg_sqs, scalars.size(), 4);
-    if (steps.size() != n || lrs.size() != n) throw std::runtime_error("adam_step_capturable_visible: list lengths differ");
-    if (n == 0) return;
-    const c10::Device dev = params[0].device();
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const long long P = radii.numel();
-    const std::vector<int> lens = row_lens(params, P, "adam_step_capturable_visible");
-    std::vector<r3dgs_adam_capturable_segment> segs(n);
-    for (size_t i = 0; i < n; i++) {
-        const double* s = &scalars[4 * i];
-        segs[i] = {params[i].data_ptr<float>(), grads[i].data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
-                   exp_avg_sqs[i].data_ptr<float>(), steps[i].data_ptr<float>(), opt_ptr<float>(lrs[i]),
-                   (long long)params[i].numel(), s[0], s[1], s[2], s[3]};
-    }
-    if (api.r3dgs_adam_step_capturable_visible((int)n, segs.data(), lens.data(), opt_ptr<int>(radii), P, cur_stream(dev)) < 0)
-        fail("adam_step_capturable_visible");
+    need(api.r3dgs_adam_step_capturable_visible, "visibility-gated Adam");
+    adam_run("adam_step_capturable_visible", params,
+             pack<r3dgs_adam_capturable_segment>("adam_step_capturable_visible", params, grads, exp_avgs, exp_avg_sqs, scalars, &steps,
+                                                 &lrs),
+             &radii);
 }
 
 // ---- per-iteration training statistics (r3dgs_trainstats.h): the same calls as diff_gaussian_rasterization/_C.py's
 // visible_means / alpha_regul_backward / densification_stats; r3dgs_train_stats.py has checked the tensors (one device, dtypes,
 // shapes, contiguity).  Absent optional tensors are empty.
 
-void need_stats()
-{
-    need_bound();
-    if (!api.r3dgs_visible_means) throw std::runtime_error("the loaded libr3dgs_hip.so has no training statistics: rebuild it with build.py");
-}
+void need_stats() { need(api.r3dgs_train_stats_workspace_bytes, "training statistics"); }
 
 // -> (visibility bool[P], n_visible int32 0-d, alpha_mean fp32 0-d, sh_abs_mean fp32 0-d); a mean that was not asked for (want_alpha /
 // want_sh false) comes back as an empty tensor.  features_rest may be empty with want_sh set: M == 1, the mean of nothing.
@@ -831,6 +775,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "compiled torch binding of libr3dgs_hip.so's hot calls (see diff_gaussian_rasterization/_C.py)";
     m.def("bind", &bind);
+    m.def("entry_points", &entry_points);
     m.def("forward_reserved", &forward_reserved);
     m.def("backward", &backward);
     m.def("mark_visible", &mark_visible);

@@ -26,196 +26,184 @@ if not os.path.exists(_LIB_PATH):
 _lib = C.CDLL(_LIB_PATH)
 
 _ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
-_vp, _i, _f = C.c_void_p, C.c_int, C.c_float
-
-_lib.r3dgs_version.restype = C.c_char_p
-_lib.r3dgs_last_error.restype = C.c_char_p
-_lib.r3dgs_geometry_bytes.restype = C.c_size_t
-_lib.r3dgs_geometry_bytes.argtypes = [_i]
-_lib.r3dgs_geometry_bytes_lean.restype = C.c_size_t
-_lib.r3dgs_geometry_bytes_lean.argtypes = [_i]
-_lib.r3dgs_binning_bytes.restype = C.c_size_t
-_lib.r3dgs_binning_bytes.argtypes = [_i, _i, _i, _i]
-_lib.r3dgs_image_bytes.restype = C.c_size_t
-_lib.r3dgs_image_bytes.argtypes = [_i, _i]
-_lib.r3dgs_binning_capacity.restype = _i
-_lib.r3dgs_binning_capacity.argtypes = [_i, _i, _i, C.c_size_t]
-_lib.r3dgs_mark_visible.restype = _i
-_lib.r3dgs_mark_visible.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
-_FWD_TAIL = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i,
-             _i, _vp]
-_lib.r3dgs_forward.restype = _i
-_lib.r3dgs_forward.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i] + _FWD_TAIL
-_lib.r3dgs_inference_forward.restype = _i
-_lib.r3dgs_inference_forward.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i, _vp, _vp, _vp] + _FWD_TAIL
-_lib.r3dgs_reserve_hint.restype = _i
-_lib.r3dgs_reserve_hint.argtypes = [_i, _i, _i]
-_lib.r3dgs_reserve_hint_view.restype = _i
-_lib.r3dgs_reserve_hint_view.argtypes = [_i, _i, _i, _vp]
-_lib.r3dgs_forward_reserved.restype = C.c_longlong
-_lib.r3dgs_forward_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i] + _FWD_TAIL
-_lib.r3dgs_inference_forward_reserved.restype = C.c_longlong
-_lib.r3dgs_inference_forward_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + _FWD_TAIL
-_lib.r3dgs_pass_query.restype = _i
-_lib.r3dgs_pass_query.argtypes = [C.c_longlong, _i, _vp, _vp, _vp, _vp]
-_lib.r3dgs_pass_pairs.restype = _i
-_lib.r3dgs_pass_pairs.argtypes = [C.c_longlong, _i]
-_lib.r3dgs_forward_pairs.restype = _i
-_lib.r3dgs_set_tight_rects.restype = _i
-_lib.r3dgs_set_tight_rects.argtypes = [_i]
-_lib.r3dgs_forward_hint.restype = None
-_lib.r3dgs_forward_hint.argtypes = [_i]
-_lib.r3dgs_set_sh_cache.restype = _i
-_lib.r3dgs_set_sh_cache.argtypes = [_i]
-_lib.r3dgs_reserve_forget_view.restype = None
-_lib.r3dgs_reserve_forget_view.argtypes = [C.c_void_p]
-_lib.r3dgs_set_f64_chain.restype = _i
-_lib.r3dgs_set_f64_chain.argtypes = [_i]
-_lib.r3dgs_set_tile_order.restype = _i
-_lib.r3dgs_set_tile_order.argtypes = [_i]
-_lib.r3dgs_export_tile_order.restype = _i
-_lib.r3dgs_export_tile_order.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
-if hasattr(_lib, "r3dgs_bwd_units_cap"):   # (absent from an older A/B build loaded through R3DGS_LIB)
-    _lib.r3dgs_bwd_units_cap.restype = _i
-    _lib.r3dgs_bwd_units_cap.argtypes = [_i, _i, _i]
-    _lib.r3dgs_set_bwd_segments.restype = _i
-    _lib.r3dgs_set_bwd_segments.argtypes = [_i]
-_lib.r3dgs_export_rects.restype = _i
-_lib.r3dgs_export_rects.argtypes = [_i, _vp, _vp, _vp]
-_lib.r3dgs_reserve_overflow_events.restype = C.c_longlong
-_lib.r3dgs_reserve_overflow_events.argtypes = [_vp, _vp]
-_lib.r3dgs_backward.restype = _i
-_lib.r3dgs_backward.argtypes = ([_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,
-                                 _vp, _vp, _vp, _vp] + [_vp] * 10 + [_f, _i, _vp])
-_lib.r3dgs_export_binning.restype = _i
-_lib.r3dgs_export_binning.argtypes = [_i, _i, _i, _i, _i] + [_vp] * 10
-if hasattr(_lib, "r3dgs_forward_params"):   # raster from the model's raw parameters (absent from older A/B builds)
-    _FWD_PARAMS_TAIL = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
-    _lib.r3dgs_forward_params.restype = _i
-    _lib.r3dgs_forward_params.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i] + _FWD_PARAMS_TAIL
-    _lib.r3dgs_forward_params_reserved.restype = C.c_longlong
-    _lib.r3dgs_forward_params_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i] + _FWD_PARAMS_TAIL
-    _lib.r3dgs_backward_params.restype = _i
-    _lib.r3dgs_backward_params.argtypes = ([_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f,
-                                            _vp, _vp, _vp, _vp] + [_vp] * 11 + [_f, _i, _vp])
-    _lib.r3dgs_activate_params.restype = _i
-    _lib.r3dgs_activate_params.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
-
-if hasattr(_lib, "r3dgs_quantised_forward"):   # include/r3dgs_quantised.h
-    _FWD_QUANT_TAIL = [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
-    _lib.r3dgs_quantised_forward.restype = _i
-    _lib.r3dgs_quantised_forward.argtypes = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp, _i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL
-    _lib.r3dgs_quantised_forward_reserved.restype = C.c_longlong
-    _lib.r3dgs_quantised_forward_reserved.argtypes = [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL
-    _lib.r3dgs_quantised_decode.restype = _i
-    _lib.r3dgs_quantised_decode.argtypes = [_i, _vp, _vp, _vp, _vp, _i] + [_vp] * 11
-    _lib.r3dgs_quantised_bytes.restype = C.c_size_t
-    _lib.r3dgs_quantised_bytes.argtypes = [_i, C.POINTER(_i), _i]
-if hasattr(_lib, "r3dgs_quantised_codebook_grad"):   # the lookup's adjoint (absent from older A/B builds)
-    _lib.r3dgs_quantised_codebook_grad_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_quantised_codebook_grad_workspace_bytes.argtypes = [_i]
-    _lib.r3dgs_quantised_codebook_grad.restype = _i
-    _lib.r3dgs_quantised_codebook_grad.argtypes = [_i] + [_vp] * 13
-_lib.r3dgs_colour_variance_accumulate.restype = _i
-_lib.r3dgs_colour_variance_accumulate.argtypes = [_i, _vp, _i, _i] + [_vp] * 12
-_lib.r3dgs_min_pixel_size.restype = _i
-_lib.r3dgs_min_pixel_size.argtypes = [_i, _i] + [_vp] * 7
-_lib.r3dgs_sphere_ellipsoid_intersection.restype = _i
-_lib.r3dgs_sphere_ellipsoid_intersection.argtypes = [_i, _i] + [_vp] * 8
-_lib.r3dgs_min_redundancy.restype = _i
-_lib.r3dgs_min_redundancy.argtypes = [_i, _i] + [_vp] * 5
-_lib.r3dgs_kmeans_workspace_bytes.restype = C.c_size_t
-_lib.r3dgs_kmeans_workspace_bytes.argtypes = [_i, _i]
-_lib.r3dgs_kmeans.restype = _i
-_lib.r3dgs_kmeans.argtypes = [_i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]
-_lib.r3dgs_pack_view_stats.restype = _i
-_lib.r3dgs_pack_view_stats.argtypes = [_i] + [_vp] * 6
-_lib.r3dgs_reduce_shards.restype = _i
-_lib.r3dgs_reduce_shards.argtypes = [_i, C.c_longlong, C.c_longlong, C.c_longlong, _vp, _vp, _vp]
-if hasattr(_lib, "r3dgs_reduce_shards_mixed"):   # (absent from an older A/B build loaded through R3DGS_LIB)
-    _lib.r3dgs_reduce_shards_mixed.restype = _i
-    _lib.r3dgs_reduce_shards_mixed.argtypes = [_i, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _vp, _vp, _vp]
-if hasattr(_lib, "r3dgs_l1_ssim_forward"):   # fused L1 + D-SSIM loss (include/r3dgs_loss.h; absent from older A/B builds)
-    _lib.r3dgs_ssim_window.restype = None
-    _lib.r3dgs_ssim_window.argtypes = [_vp]
-    _lib.r3dgs_l1_ssim_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_l1_ssim_workspace_bytes.argtypes = [_i, _i, _i, _i]
-    _lib.r3dgs_l1_ssim_forward.restype = _i
-    _lib.r3dgs_l1_ssim_forward.argtypes = [_i, _i, _i, _i, _vp, _vp, _f] + [_vp] * 9
-    _lib.r3dgs_l1_ssim_backward.restype = _i
-    _lib.r3dgs_l1_ssim_backward.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _vp, _vp]
-    _lib.r3dgs_l1_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_l1_workspace_bytes.argtypes = [C.c_longlong]
-    _lib.r3dgs_l1_forward.restype = _i
-    _lib.r3dgs_l1_forward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
-    _lib.r3dgs_l1_backward.restype = _i
-    _lib.r3dgs_l1_backward.argtypes = [C.c_longlong, _vp, _vp, _vp, _vp, _vp]
+_vp, _i, _f, _ll, _sz, _str = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_char_p
 
 
 class _AdamSegment(C.Structure):   # r3dgs_adam_segment (include/r3dgs_optim.h)
-    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("n", C.c_longlong),
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("n", _ll),
                 ("lerp_weight", _f), ("beta2", _f), ("addcmul_value", _f), ("bc2_sqrt", _f), ("eps", _f), ("step_size", _f)]
 
 
 class _AdamCapturableSegment(C.Structure):   # r3dgs_adam_capturable_segment (include/r3dgs_optim.h)
     _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("step", _vp), ("lr", _vp),
-                ("n", C.c_longlong), ("lr_value", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
-                ("eps", C.c_double)]
+                ("n", _ll), ("lr_value", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
-if hasattr(_lib, "r3dgs_adam_step"):   # fused Adam step (include/r3dgs_optim.h; absent from older A/B builds)
-    _lib.r3dgs_adam_step.restype = _i
-    _lib.r3dgs_adam_step.argtypes = [_i, C.POINTER(_AdamSegment), _vp]
-    _lib.r3dgs_adam_step_capturable.restype = _i
-    _lib.r3dgs_adam_step_capturable.argtypes = [_i, C.POINTER(_AdamCapturableSegment), _vp]
-if hasattr(_lib, "r3dgs_adam_step_visible"):   # the visibility-gated step (absent from older A/B builds)
-    _lib.r3dgs_adam_step_visible.restype = _i
-    _lib.r3dgs_adam_step_visible.argtypes = [_i, C.POINTER(_AdamSegment), C.POINTER(_i), _vp, C.c_longlong, _vp]
-    _lib.r3dgs_adam_step_capturable_visible.restype = _i
-    _lib.r3dgs_adam_step_capturable_visible.argtypes = [_i, C.POINTER(_AdamCapturableSegment), C.POINTER(_i), _vp,
-                                                        C.c_longlong, _vp]
-if hasattr(_lib, "r3dgs_visible_means"):   # per-iteration training statistics (include/r3dgs_trainstats.h; absent from older A/B builds)
-    _lib.r3dgs_train_stats_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_train_stats_workspace_bytes.argtypes = [_i]
-    _lib.r3dgs_visible_means.restype = _i
-    _lib.r3dgs_visible_means.argtypes = [_i, _i] + [_vp] * 9
-    _lib.r3dgs_alpha_regul_backward.restype = _i
-    _lib.r3dgs_alpha_regul_backward.argtypes = [_i] + [_vp] * 6
-    _lib.r3dgs_densification_stats.restype = _i
-    _lib.r3dgs_densification_stats.argtypes = [_i] + [_vp] * 6
-if hasattr(_lib, "r3dgs_image_metrics"):   # evaluation metrics (include/r3dgs_metrics.h; absent from older A/B builds)
-    _lib.r3dgs_image_metrics_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_image_metrics_workspace_bytes.argtypes = [_i, _i, _i]
-    _lib.r3dgs_image_metrics.restype = _i
-    _lib.r3dgs_image_metrics.argtypes = [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]
-    _lib.r3dgs_row_mse_workspace_bytes.restype = C.c_size_t
-    _lib.r3dgs_row_mse_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong]
-    _lib.r3dgs_row_mse.restype = _i
-    _lib.r3dgs_row_mse.argtypes = [C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp, _vp]
-    _lib.r3dgs_image_to_uint8.restype = _i
-    _lib.r3dgs_image_to_uint8.argtypes = [_i, _i, _i, _vp, _vp, _vp]
-_lib.r3dgs_profile_enable.argtypes = [_i]
-_lib.r3dgs_profile_stage_name.restype = C.c_char_p
-_lib.r3dgs_profile_stage_name.argtypes = [_i]
-_lib.r3dgs_profile_read.argtypes = [_vp, _vp]
+class _DensifyTensor(C.Structure):   # r3dgs_densify_tensor (include/r3dgs_densify.h); filled by r3dgs_densify.py
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_words", _i), ("kind", _i)]
+
+
+# ---- the C ABI of libr3dgs_hip.so, once: {group: (sentence, {name: (restype, [argtypes])})}, a row for every prototype under
+# include/ (tests/test_abi_table.py holds names, arity and the kind of every parameter to the headers; the package itself never
+# reads them).  "required" is what every build of the library exports; each other group is a family an older A/B build loaded
+# through R3DGS_LIB may lack, with the sentence _need(group) then raises ({lib}: the library's path).
+_BLOBS_EXACT = [_ALLOC, _vp, _ALLOC, _vp, _ALLOC, _vp]   # three (allocator, user) pairs: geometry, binning, image
+_BLOBS_RESERVED = [_vp, _vp, _vp, _i]                    # the three blobs sized up front + the pair reservation
+# what a forward takes behind its blobs and its (P, degrees, M[, ragged tables]) head, by colour source:
+# background, W, H, the source's arrays .. tan_fovx, tan_fovy, prefiltered, out_color, touched, transmittance, radii, counter
+# mode, debug, stream
+_FWD_TAIL = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+_FWD_PARAMS_TAIL = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+_FWD_QUANT_TAIL = [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+_NO_SUCH = "the loaded libr3dgs_hip.so has no {}: rebuild it with build.py".format
+_NO_FAMILY = "{{lib}} has no {}: rebuild it with build.py".format
+_ABI = {
+    "required": (None, {
+        # include/r3dgs_rasterizer.h
+        "r3dgs_version": (_str, []),
+        "r3dgs_last_error": (_str, []),
+        "r3dgs_geometry_bytes": (_sz, [_i]),
+        "r3dgs_geometry_bytes_lean": (_sz, [_i]),
+        "r3dgs_binning_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_image_bytes": (_sz, [_i, _i]),
+        "r3dgs_binning_capacity": (_i, [_i, _i, _i, _sz]),
+        "r3dgs_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_forward": (_i, _BLOBS_EXACT + [_i, _vp, _i] + _FWD_TAIL),
+        "r3dgs_inference_forward": (_i, _BLOBS_EXACT + [_i, _vp, _i, _vp, _vp, _vp] + _FWD_TAIL),
+        "r3dgs_reserve_hint": (_i, [_i, _i, _i]),
+        "r3dgs_reserve_hint_view": (_i, [_i, _i, _i, _vp]),
+        "r3dgs_forward_reserved": (_ll, _BLOBS_RESERVED + [_i, _vp, _i] + _FWD_TAIL),
+        "r3dgs_inference_forward_reserved": (_ll, _BLOBS_RESERVED + [_i, _vp, _i, _vp, _vp, _vp] + _FWD_TAIL),
+        "r3dgs_pass_query": (_i, [_ll, _i, _vp, _vp, _vp, _vp]),
+        "r3dgs_reserve_overflow_events": (_ll, [_vp, _vp]),
+        "r3dgs_pass_pairs": (_i, [_ll, _i]),
+        "r3dgs_forward_pairs": (_i, []),
+        "r3dgs_set_tight_rects": (_i, [_i]),
+        "r3dgs_export_rects": (_i, [_i, _vp, _vp, _vp]),
+        "r3dgs_set_tile_order": (_i, [_i]),
+        "r3dgs_set_sh_cache": (_i, [_i]),
+        "r3dgs_set_f64_chain": (_i, [_i]),
+        "r3dgs_forward_hint": (None, [_i]),
+        "r3dgs_export_tile_order": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_reserve_forget": (None, []),
+        "r3dgs_reserve_forget_view": (None, [_vp]),
+        "r3dgs_backward": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
+                                _vp, _vp, _vp, _vp, _vp,                             # radii, the three blobs, dL_dpix
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,         # the nine gradients
+                                _f, _i, _vp]),
+        "r3dgs_export_binning": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_colour_variance_accumulate": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_profile_enable": (_i, [_i]),
+        "r3dgs_profile_stage_count": (_i, []),
+        "r3dgs_profile_stage_name": (_str, [_i]),
+        "r3dgs_profile_read": (_i, [_vp, _vp]),
+        # include/r3dgs_reduction.h
+        "r3dgs_min_pixel_size": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_sphere_ellipsoid_intersection": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_min_redundancy": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_kmeans_workspace_bytes": (_sz, [_i, _i]),
+        "r3dgs_kmeans": (_i, [_i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_knn_max_k": (_i, []),                                    # the knn calls are made by simple_knn/_C.py
+        "r3dgs_knn_workspace_bytes": (_sz, [_i]),
+        "r3dgs_knn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_knn_query_workspace_bytes": (_sz, [_i]),
+        "r3dgs_knn_query": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_pack_view_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_reduce_shards": (_i, [_i, _ll, _ll, _ll, _vp, _vp, _vp]),
+    }),
+    "params": (_NO_SUCH("raw-parameter entry points"), {   # raster from the model's raw parameters
+        "r3dgs_forward_params": (_i, _BLOBS_EXACT + [_i, _vp, _i] + _FWD_PARAMS_TAIL),
+        "r3dgs_forward_params_reserved": (_ll, _BLOBS_RESERVED + [_i, _vp, _i] + _FWD_PARAMS_TAIL),
+        "r3dgs_backward_params": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
+                                       _vp, _vp, _vp, _vp, _vp,                               # radii, the three blobs, dL_dpix
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,      # the ten gradients
+                                       _f, _i, _vp]),
+        "r3dgs_activate_params": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    }),
+    "quantised": (_NO_SUCH("quantised entry points"), {   # include/r3dgs_quantised.h
+        "r3dgs_quantised_forward": (_i, _BLOBS_EXACT + [_i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL),
+        "r3dgs_quantised_forward_reserved": (_ll, _BLOBS_RESERVED + [_i, _vp, _i, _vp, _vp, _vp] + _FWD_QUANT_TAIL),
+        "r3dgs_quantised_decode": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_quantised_bytes": (_sz, [_i, C.POINTER(_i), _i]),
+    }),
+    "quantised_grad": (_NO_SUCH("r3dgs_quantised_codebook_grad"), {   # the lookup's adjoint
+        "r3dgs_quantised_codebook_grad_workspace_bytes": (_sz, [_i]),
+        "r3dgs_quantised_codebook_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    }),
+    "reduce_shards_mixed": (_NO_SUCH("r3dgs_reduce_shards_mixed"), {
+        "r3dgs_reduce_shards_mixed": (_i, [_i, _ll, _ll, _ll, _ll, _vp, _vp, _vp]),
+    }),
+    "bwd_segments": (_NO_SUCH("r3dgs_set_bwd_segments"), {
+        "r3dgs_set_bwd_segments": (_i, [_i]),
+        "r3dgs_bwd_units_cap": (_i, [_i, _i, _i]),
+    }),
+    "loss": (_NO_FAMILY("fused loss (r3dgs_l1_ssim_forward)"), {   # include/r3dgs_loss.h
+        "r3dgs_ssim_window": (None, [_vp]),
+        "r3dgs_l1_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_l1_ssim_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_l1_ssim_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _f, _vp, _vp]),
+        "r3dgs_l1_workspace_bytes": (_sz, [_ll]),
+        "r3dgs_l1_forward": (_i, [_ll, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_l1_backward": (_i, [_ll, _vp, _vp, _vp, _vp, _vp]),
+    }),
+    "adam": (_NO_FAMILY("fused Adam (r3dgs_adam_step)"), {   # include/r3dgs_optim.h
+        "r3dgs_adam_step": (_i, [_i, C.POINTER(_AdamSegment), _vp]),
+        "r3dgs_adam_step_capturable": (_i, [_i, C.POINTER(_AdamCapturableSegment), _vp]),
+    }),
+    "adam_visible": (_NO_FAMILY("visibility-gated Adam (r3dgs_adam_step_visible)"), {
+        "r3dgs_adam_step_visible": (_i, [_i, C.POINTER(_AdamSegment), C.POINTER(_i), _vp, _ll, _vp]),
+        "r3dgs_adam_step_capturable_visible": (_i, [_i, C.POINTER(_AdamCapturableSegment), C.POINTER(_i), _vp, _ll, _vp]),
+    }),
+    "train_stats": (_NO_FAMILY("training statistics (r3dgs_visible_means)"), {   # include/r3dgs_trainstats.h
+        "r3dgs_train_stats_workspace_bytes": (_sz, [_i]),
+        "r3dgs_visible_means": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_alpha_regul_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_densification_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    }),
+    "metrics": (_NO_FAMILY("evaluation metrics (r3dgs_image_metrics)"), {   # include/r3dgs_metrics.h
+        "r3dgs_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+        "r3dgs_image_metrics": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+        "r3dgs_row_mse_workspace_bytes": (_sz, [_ll, _ll]),
+        "r3dgs_row_mse": (_i, [_ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_image_to_uint8": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    }),
+    "densify": (_NO_FAMILY("densification (r3dgs_densify_plan)"), {   # include/r3dgs_densify.h; called by r3dgs_densify.py
+        "r3dgs_densify_workspace_bytes": (_sz, [_i]),
+        "r3dgs_densify_plan": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp]),
+        "r3dgs_prune_plan": (_i, [_i, _vp, _vp, _vp, _vp]),
+        "r3dgs_densify_move": (_i, [_i, _i, _i, _i, _i, C.POINTER(_DensifyTensor), _vp, _vp, _vp, _vp, _vp, _vp]),
+    }),
+}
+
+
+def _apply_abi(lib):
+    """Sets restype / argtypes of every row on `lib` -> the set of groups it has.  An optional group is there when the library
+    exports all of its names; a name of the required group that is missing raises AttributeError."""
+    present = set()
+    for group, (_, rows) in _ABI.items():
+        if group != "required" and not all(hasattr(lib, name) for name in rows):
+            continue
+        present.add(group)
+        for name, (restype, argtypes) in rows.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return present
+
+
+_present = _apply_abi(_lib)
+
+
+def _need(group, error=RuntimeError):
+    if group not in _present:
+        raise error(_ABI[group][0].format(lib=_LIB_PATH))
+
 
 LIBRARY_PATH = _LIB_PATH
 
-# ---- compiled torch binding of the two hot calls (csrc_torch/r3dgs_torch.cpp; the reference's layer is a torch C++
-# extension too, DGR/ext.cpp:16-25).  It is handed the entry points of the library loaded above, so both bindings drive
-# ONE library instance.  R3DGS_BINDING = auto (default: compiled if it was built, else ctypes) | torch (required) | ctypes.
-_EXT_FUNCS = ("r3dgs_last_error", "r3dgs_version", "r3dgs_geometry_bytes", "r3dgs_geometry_bytes_lean", "r3dgs_binning_bytes",
-              "r3dgs_image_bytes", "r3dgs_forward_hint", "r3dgs_reserve_hint_view", "r3dgs_forward_reserved",
-              "r3dgs_pass_query", "r3dgs_backward", "r3dgs_mark_visible")
-_EXT_LOSS_FUNCS = ("r3dgs_l1_ssim_workspace_bytes", "r3dgs_l1_ssim_forward", "r3dgs_l1_ssim_backward", "r3dgs_l1_workspace_bytes",
-                   "r3dgs_l1_forward", "r3dgs_l1_backward",   # optional: an older A/B build has no loss
-                   "r3dgs_adam_step", "r3dgs_adam_step_capturable",   # ... nor a fused Adam
-                   "r3dgs_adam_step_visible", "r3dgs_adam_step_capturable_visible")   # ... nor its gated form
-_EXT_PARAMS_FUNCS = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r3dgs_backward_params",
-                     "r3dgs_activate_params")   # ... nor the raw-parameter entry points
-_EXT_STATS_FUNCS = ("r3dgs_train_stats_workspace_bytes", "r3dgs_visible_means", "r3dgs_alpha_regul_backward",
-                    "r3dgs_densification_stats")   # ... nor the training statistics
-_EXT_QUANT_FUNCS = ("r3dgs_quantised_codebook_grad_workspace_bytes", "r3dgs_quantised_codebook_grad")   # ... nor the lookup's adjoint
+# ---- compiled torch binding of the hot calls (csrc_torch/r3dgs_torch.cpp; the reference's layer is a torch C++ extension
+# too, DGR/ext.cpp:16-25).  It names the entry points it wants (entry_points()) and is handed their addresses in the library
+# loaded above, so both bindings drive ONE library instance; an optional one whose group the library lacks is left out.
+# R3DGS_BINDING = auto (default: compiled if it was built, else ctypes) | torch (required) | ctypes.
 _ext = None
 _ext_loaded = None
 _binding_request = os.environ.get("R3DGS_BINDING", "auto")
@@ -224,9 +212,8 @@ if _binding_request not in ("auto", "torch", "ctypes"):
 if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
-        _ext_loaded.bind({n: C.cast(getattr(_lib, n), C.c_void_p).value
-                          for n in _EXT_FUNCS + tuple(f for f in _EXT_LOSS_FUNCS + _EXT_PARAMS_FUNCS + _EXT_STATS_FUNCS + _EXT_QUANT_FUNCS
-                                                         if hasattr(_lib, f))})
+        _rows = {name for group in _present for name in _ABI[group][1]}
+        _ext_loaded.bind({name: C.cast(getattr(_lib, name), _vp).value for name, _ in _ext_loaded.entry_points() if name in _rows})
         _ext = _ext_loaded
     except ImportError:
         if _binding_request == "torch":
@@ -305,23 +292,14 @@ def _ptr(t):
     return t.data_ptr()
 
 
-def _dev_f32(t, dev):
+def _dev(t, dev, dtype=torch.float32):
+    """An input as the library reads it: on `dev`, of `dtype`, contiguous (copied if it is not); None for an absent one."""
     if t is None or t.numel() == 0:
         return None
     if t.device != dev:
         raise RuntimeError(f"expected a tensor on {dev}, got {t.device}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"expected float32, got {t.dtype}")
-    return t.contiguous()
-
-
-def _dev_i32(t, dev):
-    if t is None or t.numel() == 0:
-        return None
-    if t.device != dev:
-        raise RuntimeError(f"expected a tensor on {dev}, got {t.device}")
-    if t.dtype != torch.int32:
-        raise RuntimeError(f"expected int32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"expected {str(dtype)[6:]}, got {t.dtype}")
     return t.contiguous()
 
 
@@ -550,11 +528,24 @@ def _forget_view(ptr, ident):
         pass
 
 
-def _empty_forward(dev, H, W):
-    """The forward's result for P == 0: a black image, nothing rendered, empty state."""
-    e = torch.empty(0, dtype=torch.uint8, device=dev)
-    return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
-            torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone())
+def _forward_prologue(P, dev, H, W, strict_override):
+    """What every forward wrapper does once its arguments are checked -> (empty, trains, strict).  empty: the result for
+    P == 0 (a black image, nothing rendered, empty state), else None; trains: what hint_next_forward said about this forward
+    (one-shot, per thread like the library's own r3dgs_forward_hint state), or whether gradients are enabled; strict: the
+    module's mode, or the caller's override."""
+    if P == 0:
+        e = torch.empty(0, dtype=torch.uint8, device=dev)
+        return (NumRendered(0, 0, 0, 0), torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.int32, device=dev), e, e.clone(), e.clone()), False, False
+    hint = getattr(_tls, "next_forward_trains", None)
+    _tls.next_forward_trains = None
+    return (None, torch.is_grad_enabled() if hint is None else hint,
+            _strict if strict_override is None else bool(strict_override))
+
+
+def _zero_grads(dev, *shapes):
+    """A backward's result for P == 0: zeros of the given shapes."""
+    return tuple(torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes)
 
 
 def _pair_capacity(R, P, W, H, binningBuffer):
@@ -630,12 +621,9 @@ def _forward_common(ragged, background, means3D, colors, opacity, scales, rotati
     if dev.type != "cuda":
         raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    if P == 0:
-        return _empty_forward(dev, H, W)
-    hint = getattr(_tls, "next_forward_trains", None)   # per thread, like the library's own r3dgs_forward_hint state
-    trains = torch.is_grad_enabled() if hint is None else hint
-    _tls.next_forward_trains = None
-    strict = _strict if _strict_override is None else bool(_strict_override)
+    empty, trains, strict = _forward_prologue(P, dev, H, W, _strict_override)
+    if empty is not None:
+        return empty
     if _ext is not None and ragged is None and counters is None and not exact and not debug and _reserve is None:
         # the hot call: compiled marshalling (csrc_torch/r3dgs_torch.cpp), same library entry points as below
         if viewmatrix is not None and viewmatrix.is_contiguous() and viewmatrix.dtype == torch.float32:
@@ -652,11 +640,11 @@ def _forward_common(ragged, background, means3D, colors, opacity, scales, rotati
         exact = True   # the exact-size path below
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    bg = _dev_f32(background, dev)
-    m3, col, op = _dev_f32(means3D, dev), _dev_f32(colors, dev), _dev_f32(opacity, dev)
-    sc, rot, cov = _dev_f32(scales, dev), _dev_f32(rotations, dev), _dev_f32(cov3D_precomp, dev)
-    vm, pm, cp = _dev_f32(viewmatrix, dev), _dev_f32(projmatrix, dev), _dev_f32(campos, dev)
-    shc, deg = _dev_f32(sh, dev), _dev_i32(degrees, dev)
+    bg = _dev(background, dev)
+    m3, col, op = _dev(means3D, dev), _dev(colors, dev), _dev(opacity, dev)
+    sc, rot, cov = _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
+    vm, pm, cp = _dev(viewmatrix, dev), _dev(projmatrix, dev), _dev(campos, dev)
+    shc, deg = _dev(sh, dev), _dev(degrees, dev, torch.int32)
     touched = transm = None
     if counters is not None:
         touched, transm = counters
@@ -670,7 +658,7 @@ def _forward_common(ragged, background, means3D, colors, opacity, scales, rotati
             head = (P, _ptr(deg), int(shc.size(1)) if shc is not None else 0)
             fn_exact, fn_reserved = _lib.r3dgs_forward, _lib.r3dgs_forward_reserved
         else:
-            coeffs, perband, cumsum = (_dev_i32(t, dev) for t in ragged)
+            coeffs, perband, cumsum = (_dev(t, dev, torch.int32) for t in ragged)
             head = (P, _ptr(deg), int(perband.numel()) if perband is not None else 0, _ptr(coeffs), _ptr(perband),
                     _ptr(cumsum))
             fn_exact, fn_reserved = _lib.r3dgs_inference_forward, _lib.r3dgs_inference_forward_reserved
@@ -728,8 +716,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
     opts = dict(dtype=torch.float32, device=dev)
     if P == 0:
-        z = lambda *s: torch.zeros(s, **opts)
-        return z(0, 3), z(0, 3), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)
+        return _zero_grads(dev, (0, 3), (0, 3), (0, 1), (0, 3), (0, 6), (0, M, 3), (0, 3), (0, 4))
     if _ext is not None and _grad_arena is None:
         cap = _pair_capacity(R, P, W, H, binningBuffer)
         return tuple(_ext.backward(_t(background), means3D, _t(radii), _t(colors), _t(scales), _t(rotations),
@@ -749,10 +736,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dcolors, dL_dopacity = e("colors", P, 3), e("opacity", P, 1)
     dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = e("cov3D", P, 6), e("sh", P, M, 3), e("scales", P, 3), e("rotations", P, 4)
     dL_dconic = torch.empty((P, 2, 2), **opts) if _want_conic else None
-    bg, m3 = _dev_f32(background, dev), _dev_f32(means3D, dev)
-    col, sc, rot, cov = (_dev_f32(t, dev) for t in (colors, scales, rotations, cov3D_precomp))
-    vm, pm, cp = _dev_f32(viewmatrix, dev), _dev_f32(projmatrix, dev), _dev_f32(campos, dev)
-    g, shc, deg, rad = _dev_f32(dL_dout_color, dev), _dev_f32(sh, dev), _dev_i32(degrees, dev), _dev_i32(radii, dev)
+    bg, m3 = _dev(background, dev), _dev(means3D, dev)
+    col, sc, rot, cov = (_dev(t, dev) for t in (colors, scales, rotations, cov3D_precomp))
+    vm, pm, cp = _dev(viewmatrix, dev), _dev(projmatrix, dev), _dev(campos, dev)
+    g, shc = _dev(dL_dout_color, dev), _dev(sh, dev)
+    deg, rad = _dev(degrees, dev, torch.int32), _dev(radii, dev, torch.int32)
     cap = _pair_capacity(R, P, W, H, binningBuffer)
     with _on_device(dev):
         st = _lib.r3dgs_backward(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sc),
@@ -771,11 +759,6 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 # (log), _rotation (unnormalised).  The kernels apply the activations; the backward returns gradients of exactly these
 # tensors, each written whole by the library into storage of the leaf's own shape -- no cat, narrow or copy on either side.
 # A tensor that would need a copy (not contiguous, not float32) is refused instead of converted.
-
-def _need_params():
-    if not hasattr(_lib, "r3dgs_forward_params"):
-        raise RuntimeError("the loaded libr3dgs_hip.so has no raw-parameter entry points: rebuild it with build.py")
-
 
 def _param(t, dev, name):
     if t.device != dev:
@@ -822,15 +805,12 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
                               prefiltered, debug, exact=False, _reserve=None, _strict_override=None):
     """rasterize_gaussians from the model's raw parameters -> (num_rendered, out_color[3,H,W], radii[P], geomBuffer,
     binningBuffer, imgBuffer); same asynchronous / exact-size / strict-mode behaviour."""
-    _need_params()
+    _need("params")
     P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
     H, W = int(image_height), int(image_width)
-    if P == 0:
-        return _empty_forward(dev, H, W)
-    hint = getattr(_tls, "next_forward_trains", None)
-    trains = torch.is_grad_enabled() if hint is None else hint
-    _tls.next_forward_trains = None
-    strict = _strict if _strict_override is None else bool(_strict_override)
+    empty, trains, strict = _forward_prologue(P, dev, H, W, _strict_override)
+    if empty is not None:
+        return empty
     rest = _NO_TENSOR if M == 1 else features_rest
     if viewmatrix is not None and viewmatrix.is_contiguous() and viewmatrix.dtype == torch.float32:
         _track_view(viewmatrix)
@@ -847,8 +827,8 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
         return _exact_result(*_ext.forward_params(*common, bool(debug)))
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
-    deg = _dev_i32(degrees, dev)
+    bg, vm, pm, cp = (_dev(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    deg = _dev(degrees, dev, torch.int32)
     _lib.r3dgs_forward_hint(int(trains))
     with _on_device(dev):
         args = (P, _ptr(deg), M, _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest), _ptr(opacity), _ptr(scaling),
@@ -863,13 +843,12 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
                                        geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug):
     """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dxyz[P,3], dL_dfeatures_dc[P,1,3], dL_dfeatures_rest[P,M-1,3],
     dL_dscaling[P,3], dL_drotation[P,4]): gradients of the tensors passed in (raw scaling / rotation included)."""
-    _need_params()
+    _need("params")
     P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     opts = dict(dtype=torch.float32, device=dev)
     if P == 0:
-        z = lambda *s: torch.zeros(s, **opts)
-        return z(0, 3), z(0, 1), z(0, 3), z(0, 1, 3), z(0, M - 1, 3), z(0, 3), z(0, 4)
+        return _zero_grads(dev, (0, 3), (0, 1), (0, 3), (0, 1, 3), (0, M - 1, 3), (0, 3), (0, 4))
     rest = _NO_TENSOR if M == 1 else features_rest
     cap = _pair_capacity(R, P, W, H, binningBuffer)
     if _ext is not None:
@@ -881,8 +860,8 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
     dL_dmeans3D, dL_dmeans2D, dL_dopacity = e(P, 3), e(P, 3), e(P, 1)
     dL_ddc, dL_drest, dL_dscaling, dL_drotation = e(P, 1, 3), e(P, M - 1, 3), e(P, 3), e(P, 4)
     scratch = e(P, 9)   # dL_dcolor [P,3] + dL_dcov3D [P,6]: written by the C ABI, no leaf on this path
-    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
-    g, deg, rad = _dev_f32(dL_dout_color, dev), _dev_i32(degrees, dev), _dev_i32(radii, dev)
+    bg, vm, pm, cp = (_dev(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    g, deg, rad = _dev(dL_dout_color, dev), _dev(degrees, dev, torch.int32), _dev(radii, dev, torch.int32)
     with _on_device(dev):
         st = _lib.r3dgs_backward_params(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest),
                                         _ptr(scaling), float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp),
@@ -898,7 +877,7 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
 def activate_params(scaling, rotation):
     """(exp(scaling), F.normalize(rotation)) evaluated by the functions the raw-parameter kernels use (csrc/param_math.h):
     the existing entry points fed these give the fused path's image and binning bit for bit."""
-    _need_params()
+    _need("params")
     dev = scaling.device
     if dev.type != "cuda":
         raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
@@ -920,11 +899,6 @@ def activate_params(scaling, rotation):
 
 # ---- the quantised (codebook-indexed) model: include/r3dgs_quantised.h ------------------------------------------------
 # Inference only.  The arrays are read in place; a tensor that would need a copy is refused.
-
-def _need_quantised():
-    if not hasattr(_lib, "r3dgs_quantised_forward"):
-        raise RuntimeError("the loaded libr3dgs_hip.so has no quantised entry points: rebuild it with build.py")
-
 
 def _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum):
     """-> (P, xyz_is_half, device); the refusals of the quantised path."""
@@ -965,16 +939,15 @@ def rasterize_gaussians_quantised(background, xyz, geom_ids, sh_ids, codebooks, 
     radii[P], geomBuffer, binningBuffer, imgBuffer); same asynchronous / exact-size / strict-mode behaviour.  `counters`:
     (out_touched_pixels int32 [P], out_transmittance float [P]) for counter mode.  sh_ids is not length-checked against the
     band tables here (they live on the device); QuantisedModel builds them together."""
-    _need_quantised()
+    _need("quantised")
     P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
     H, W = int(image_height), int(image_width)
-    if P == 0:
-        return _empty_forward(dev, H, W)
-    _tls.next_forward_trains = None
-    strict = _strict if _strict_override is None else bool(_strict_override)
+    empty, _, strict = _forward_prologue(P, dev, H, W, _strict_override)   # (no backward exists for this model: trains is moot)
+    if empty is not None:
+        return empty
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    bg, vm, pm, cp = (_dev_f32(t, dev) for t in (background, viewmatrix, projmatrix, campos))
+    bg, vm, pm, cp = (_dev(t, dev) for t in (background, viewmatrix, projmatrix, campos))
     touched = transm = None
     if counters is not None:
         touched, transm = counters
@@ -997,7 +970,7 @@ def quantised_decode(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cu
     quantised kernels use (csrc/quant_math.h) -> (xyz [P,3], features_dc [P,1,3], features_rest [P,15,3], opacity [P,1],
     scaling [P,3], rotation [P,4], degrees int32 [P,1]).  want_xyz=False: the positions are not decoded (xyz_out NULL) and
     the first entry is None -- for a caller that holds them in float already."""
-    _need_quantised()
+    _need("quantised")
     P, half, dev = _check_quantised(xyz, geom_ids, sh_ids, codebooks, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum)
     f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # every element is written by the library
     out = (f(P, 3) if want_xyz else None, f(P, 1, 3), f(P, 15, 3), f(P, 1), f(P, 3), f(P, 4),
@@ -1050,8 +1023,7 @@ def quantised_codebook_grad(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimi
     gradients of the decoded tensors, shaped as quantised_decode returns them (None = zeros), summed into the centres the ids
     name -> dL_dcodebooks float32 [20,256].  Double accumulation in a fixed order, one rounding, no atomics: the same inputs
     give the same bits.  Rows of dL_dfeatures_rest above a Gaussian's degree are not read."""
-    if not hasattr(_lib, "r3dgs_quantised_codebook_grad"):
-        raise RuntimeError("the loaded libr3dgs_hip.so has no r3dgs_quantised_codebook_grad: rebuild it with build.py")
+    _need("quantised_grad")
     grads = (dL_dfeatures_dc, dL_dfeatures_rest, dL_dopacity, dL_dscaling, dL_drotation)
     if _ext is not None:
         return _ext.quantised_codebook_grad(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimitiveCount, coeffsNum,
@@ -1068,7 +1040,7 @@ def quantised_codebook_grad(geom_ids, sh_ids, perBandPrimitiveCount, cumSumPrimi
 
 def quantised_bytes(P, per_band_count, xyz_is_half):
     """Resident bytes of a quantised model with `per_band_count` Gaussians of degree 0..3 (needs no GPU)."""
-    _need_quantised()
+    _need("quantised")
     counts = (_i * 4)(*[int(c) for c in per_band_count])
     n = int(_lib.r3dgs_quantised_bytes(int(P), counts, int(bool(xyz_is_half))))
     if n == 0:
@@ -1084,7 +1056,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     P = int(means3D.size(0))
     present = torch.zeros((P,), dtype=torch.bool, device=dev)
     if P:
-        m3, vm, pm = _dev_f32(means3D, dev), _dev_f32(viewmatrix, dev), _dev_f32(projmatrix, dev)
+        m3, vm, pm = _dev(means3D, dev), _dev(viewmatrix, dev), _dev(projmatrix, dev)
         with _on_device(dev):
             _check(_lib.r3dgs_mark_visible(P, _ptr(m3), _ptr(vm), _ptr(pm), _ptr(present), _stream()), "mark_visible")
     return present
@@ -1178,10 +1150,12 @@ def set_bwd_segments(on):
     workgroups per tile, from checkpoints the forward leaves; False: one workgroup per tile.  Gradients agree to rounding (the state at a
     segment's end is the forward's running product instead of the backward's own division chain).  A forward issued while
     this is off leaves no checkpoints, and its backward never splits.  Returns the previous setting."""
+    _need("bwd_segments")
     return bool(_lib.r3dgs_set_bwd_segments(int(bool(on))))
 
 
 def bwd_segments():
+    _need("bwd_segments")
     return bool(_lib.r3dgs_set_bwd_segments(-1))
 
 
@@ -1197,6 +1171,7 @@ def export_tile_order(H, W, imageBuffer, P=0, num_rendered=0, binningBuffer=None
     if binningBuffer is not None and binningBuffer.numel():
         R = (num_rendered.capacity if isinstance(num_rendered, NumRendered) else
              _lib.r3dgs_binning_capacity(int(P), W, H, int(binningBuffer.numel())))
+        _need("bwd_segments")
         cap = int(_lib.r3dgs_bwd_units_cap(R, W, H))
         order = torch.empty((cap + 2 * _ORDER_LISTS,), dtype=torch.int32, device=imageBuffer.device)
     with _on_device(imageBuffer.device):
@@ -1247,9 +1222,9 @@ def calculate_colours_variance_partial(cam_positions, means3D, opacity, scales, 
     wSum, wSumSq = torch.zeros((P, 1), **opts), torch.zeros((P, 1), **opts)
     mean, variance = torch.zeros((P, 1, 3), **opts), torch.zeros((P, 1, 3), **opts)
     if P:
-        m3, shc, deg = _dev_f32(means3D, dev), _dev_f32(sh, dev), _dev_i32(degrees, dev)
+        m3, shc, deg = _dev(means3D, dev), _dev(sh, dev), _dev(degrees, dev, torch.int32)
         M = int(shc.size(1))
-        cams = _dev_f32(cam_positions, dev)
+        cams = _dev(cam_positions, dev)
         Hs, Ws = image_height.tolist(), image_width.tolist()
         txs, tys = tan_fovxs.tolist(), tan_fovys.tolist()
         bg = torch.zeros(3, **opts)
@@ -1305,10 +1280,10 @@ def find_minimum_projected_pixel_size(w2ndc_transforms, w2ndc_transforms_inverse
     P = int(means3D.size(0))
     out = torch.empty((P, 1), dtype=torch.float32, device=dev)
     if P:
-        m, mi = _dev_f32(w2ndc_transforms, dev), _dev_f32(w2ndc_transforms_inverse, dev)
-        Hs, Ws = _dev_i32(image_height, dev), _dev_i32(image_width, dev)
+        m, mi = _dev(w2ndc_transforms, dev), _dev(w2ndc_transforms_inverse, dev)
+        Hs, Ws = _dev(image_height, dev, torch.int32), _dev(image_width, dev, torch.int32)
         with _on_device(dev):
-            _check(_lib.r3dgs_min_pixel_size(P, int(w2ndc_transforms.size(0)), _ptr(m), _ptr(mi), _ptr(_dev_f32(means3D, dev)),
+            _check(_lib.r3dgs_min_pixel_size(P, int(w2ndc_transforms.size(0)), _ptr(m), _ptr(mi), _ptr(_dev(means3D, dev)),
                                              _ptr(Hs), _ptr(Ws), _ptr(out), _stream()),
                    "find_minimum_projected_pixel_size")
     return out
@@ -1322,13 +1297,13 @@ def sphere_ellipsoid_intersection(means3D, scales, rotations, neighbours_indices
     red = torch.empty((P, 1), dtype=torch.int32, device=dev)
     mask = torch.empty((P, knn), dtype=torch.bool, device=dev)
     if P:
-        nbr = _dev_i32(neighbours_indices, dev)
+        nbr = _dev(neighbours_indices, dev, torch.int32)
         if nbr.numel() != P * knn:
             raise RuntimeError("neighbours_indices must hold P * knn entries")
         with _on_device(dev):
             _check(_lib.r3dgs_sphere_ellipsoid_intersection(
-                P, knn, _ptr(_dev_f32(means3D, dev)), _ptr(_dev_f32(scales, dev)), _ptr(_dev_f32(rotations, dev)),
-                _ptr(nbr), _ptr(_dev_f32(sphere_radius, dev)), _ptr(red), mask.data_ptr() if knn else None,
+                P, knn, _ptr(_dev(means3D, dev)), _ptr(_dev(scales, dev)), _ptr(_dev(rotations, dev)),
+                _ptr(nbr), _ptr(_dev(sphere_radius, dev)), _ptr(red), mask.data_ptr() if knn else None,
                 _stream()), "sphere_ellipsoid_intersection")
     return red, mask
 
@@ -1339,11 +1314,11 @@ def allocate_minimum_redundancy_value(redundancy_values, neighbours_indices, int
     P, knn = int(redundancy_values.size(0)), int(knn)
     out = torch.empty((P, 1), dtype=torch.int32, device=dev)
     if P:
-        nbr, msk = _dev_i32(neighbours_indices, dev), _dev_u8(intersection_mask, dev)
+        nbr, msk = _dev(neighbours_indices, dev, torch.int32), _dev_u8(intersection_mask, dev)
         if nbr.numel() != P * knn or msk.numel() != P * knn:
             raise RuntimeError("neighbours_indices / intersection_mask must hold P * knn entries")
         with _on_device(dev):
-            _check(_lib.r3dgs_min_redundancy(P, knn, _ptr(_dev_i32(redundancy_values, dev)), _ptr(nbr), _ptr(msk),
+            _check(_lib.r3dgs_min_redundancy(P, knn, _ptr(_dev(redundancy_values, dev, torch.int32)), _ptr(nbr), _ptr(msk),
                                              _ptr(out), _stream()), "allocate_minimum_redundancy_value")
     return (out,)
 
@@ -1362,7 +1337,7 @@ def kmeans_cuda(values, centers, tol, max_iterations, _want_iterations=False):
         if ws_bytes == 0:
             raise RuntimeError(f"kmeans_cuda: {_lib.r3dgs_last_error().decode()}")
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        _check(_lib.r3dgs_kmeans(n, nc, _ptr(_dev_f32(values, dev)), _ptr(_dev_f32(centers, dev)), float(tol),
+        _check(_lib.r3dgs_kmeans(n, nc, _ptr(_dev(values, dev)), _ptr(_dev(centers, dev)), float(tol),
                                  int(max_iterations), _ptr(ids), _ptr(new_centers), _ptr(iters), _ptr(ws),
                                  _stream()), "kmeans_cuda")
     if _want_iterations:
@@ -1378,7 +1353,7 @@ def pack_view_stats(viewspace_grad, radii, grad_norm_out, visible_out, radii_out
     P = int(radii.numel())
     if P == 0:
         return
-    vg, rd = _dev_f32(viewspace_grad, dev), _dev_i32(radii, dev)
+    vg, rd = _dev(viewspace_grad, dev), _dev(radii, dev, torch.int32)
     for t, dt in ((grad_norm_out, torch.float32), (visible_out, torch.float32), (radii_out, torch.int32)):
         if t.device != dev or t.dtype != dt or t.numel() != P or not t.is_contiguous():
             raise RuntimeError("pack_view_stats: outputs must be contiguous [P] tensors on the same GPU")
@@ -1402,6 +1377,7 @@ def reduce_shards(recv, world, shard_begin, sum_len, out):
 def reduce_shards_mixed(recv, world, shard_begin, sum_len, half_end, out):
     """r3dgs_reduce_shards_mixed (include/r3dgs_reduction.h): as reduce_shards, with the words [sum_len, half_end) of the
     buffer holding bfloat16 pairs (fp32 accumulation in rank order, one rounding to nearest even)."""
+    _need("reduce_shards_mixed")
     dev = _need_gpu(recv, "reduce_shards_mixed")
     shard = int(out.numel())
     if recv.numel() != world * shard or not recv.is_contiguous() or not out.is_contiguous():
@@ -1415,14 +1391,9 @@ def reduce_shards_mixed(recv, world, shard_begin, sum_len, half_end, out):
 # Inputs are checked there (device fp32, contiguous, same shape); these calls only allocate and launch, on the current
 # stream, without a host synchronisation, so a forward + backward pair can be captured in a graph.
 
-def _need_loss():
-    if not hasattr(_lib, "r3dgs_l1_ssim_forward"):
-        raise RuntimeError(f"{_LIB_PATH} has no fused loss (r3dgs_l1_ssim_forward): rebuild it with build.py")
-
-
 def ssim_window():
     """The 11 fp32 weights of the reference's 1-D SSIM window (utils/loss_utils.py:24-26), computed on the host."""
-    _need_loss()
+    _need("loss")
     w = (C.c_float * 11)()
     _lib.r3dgs_ssim_window(w)
     return np.array(w[:], np.float32)
@@ -1431,7 +1402,7 @@ def ssim_window():
 def l1_ssim_forward(img1, img2, B, Cc, H, W, lambda_dssim, want_partials, want_map):
     """-> (l1, ssim, loss, dssim, ssim_image[B], ssim_map or empty, partials[3,B,C,H,W] or empty); 0-d tensors for the
     scalars.  One tile kernel + one fixed-order reduction."""
-    _need_loss()
+    _need("loss")
     if _ext is not None:
         return _ext.l1_ssim_forward(img1, img2, B, Cc, H, W, float(lambda_dssim), bool(want_partials), bool(want_map))
     dev = img1.device
@@ -1454,7 +1425,7 @@ def l1_ssim_forward(img1, img2, B, Cc, H, W, lambda_dssim, want_partials, want_m
 def l1_ssim_backward(img1, img2, partials, grad_l1, coef_l1, grad_ssim, ssim_grad_mode, coef_ssim, B, Cc, H, W):
     """-> d/d img1 [B,C,H,W] (r3dgs_l1_ssim_backward).  grad_l1 / grad_ssim: device tensors (empty: absent);
     ssim_grad_mode 0: scalar upstream of the mean, 1: per image [B], 2: per pixel [B,C,H,W]."""
-    _need_loss()
+    _need("loss")
     if _ext is not None:
         return _ext.l1_ssim_backward(img1, img2, partials, grad_l1, float(coef_l1), grad_ssim, int(ssim_grad_mode),
                                      float(coef_ssim), B, Cc, H, W)
@@ -1469,7 +1440,7 @@ def l1_ssim_backward(img1, img2, partials, grad_l1, coef_l1, grad_ssim, ssim_gra
 
 def l1_forward(x, y):
     """mean |x - y| over all elements (0-d tensor): one chunk kernel + the fixed-order reduction."""
-    _need_loss()
+    _need("loss")
     if _ext is not None:
         return _ext.l1_forward(x, y)
     dev = x.device
@@ -1486,7 +1457,7 @@ def l1_forward(x, y):
 
 def l1_backward(x, y, grad):
     """grad[0] * sign(x - y) / n, shaped like x."""
-    _need_loss()
+    _need("loss")
     if _ext is not None:
         return _ext.l1_backward(x, y, grad)
     dev = x.device
@@ -1500,55 +1471,37 @@ def l1_backward(x, y, grad):
 # (one device, fp32, contiguous, matching sizes) and computes the scalars.  One launch per 32 tensors on the current stream,
 # no host synchronisation.
 
-def _need_optim():
-    if not hasattr(_lib, "r3dgs_adam_step"):
-        raise RuntimeError(f"{_LIB_PATH} has no fused Adam (r3dgs_adam_step): rebuild it with build.py")
+def _adam_segments(params, grads, exp_avgs, exp_avg_sqs, scalars):
+    segs = (_AdamSegment * len(params))()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        segs[i] = _AdamSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), *scalars[6 * i:6 * i + 6])
+    return segs
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars):
-    """One Adam step of the tensors (lists of equal length, params[0]'s device).  scalars: a flat list of six Python floats
-    per tensor -- 1 - beta1, beta2, 1 - beta2, bc2_sqrt, eps, step_size (r3dgs_adam_segment) -- each rounded to fp32 once."""
-    _need_optim()
-    if _ext is not None:
-        return _ext.adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars)
-    n = len(params)
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n and len(scalars) == 6 * n):
-        raise RuntimeError("adam_step: list lengths differ")
+def _adam_capturable_segments(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars):
+    segs = (_AdamCapturableSegment * len(params))()
+    for i, (p, g, m, v, step, lr) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs, steps, lrs)):
+        segs[i] = _AdamCapturableSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(), _ptr(lr),
+                                         p.numel(), *scalars[4 * i:4 * i + 4])
+    return segs
+
+
+def _adam(what, fn, pack, per, lists, scalars, radii=None):
+    """The ctypes route of the four adam_step* functions: `pack` makes the segments of entry point `fn` from the tensor lists
+    and `per` scalars per tensor; radii: the gated forms' tail (row lengths, radii, P)."""
+    params, n = lists[0], len(lists[0])
+    if any(len(l) != n for l in lists) or len(scalars) != per * n:
+        raise RuntimeError(f"{what}: list lengths differ")
     if n == 0:
         return None
-    segs = (_AdamSegment * n)()
-    for i in range(n):
-        segs[i] = _AdamSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(),
-                               params[i].numel(), *scalars[6 * i:6 * i + 6])
+    tail = ()
+    if radii is not None:
+        P = radii.numel()
+        tail = ((_i * n)(*_row_lens(params, P, what)), _ptr(radii), P)
+    segs = pack(*lists, scalars)
     with _on_device(params[0].device):
-        _check(_lib.r3dgs_adam_step(n, segs, _stream()), "adam_step")
+        _check(fn(n, segs, *tail, _stream()), what)
     return None
-
-
-def adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars):
-    """The capturable step: steps[i] a device float32 count (read + 1, then bumped), lrs[i] a 0-d device float32 lr or an
-    empty tensor; scalars: a flat list of lr_value, beta1, beta2, eps per tensor (r3dgs_adam_capturable_segment)."""
-    _need_optim()
-    if _ext is not None:
-        return _ext.adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars)
-    n = len(params)
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(lrs) == n and len(scalars) == 4 * n):
-        raise RuntimeError("adam_step_capturable: list lengths differ")
-    if n == 0:
-        return None
-    segs = (_AdamCapturableSegment * n)()
-    for i in range(n):
-        segs[i] = _AdamCapturableSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(),
-                                         exp_avg_sqs[i].data_ptr(), steps[i].data_ptr(), _ptr(lrs[i]), params[i].numel(),
-                                         *scalars[4 * i:4 * i + 4])
-    with _on_device(params[0].device):
-        _check(_lib.r3dgs_adam_step_capturable(n, segs, _stream()), "adam_step_capturable")
-    return None
-
-
-def _need_optim_visible():
-    if not hasattr(_lib, "r3dgs_adam_step_visible"):
-        raise RuntimeError(f"{_LIB_PATH} has no visibility-gated Adam (r3dgs_adam_step_visible): rebuild it with build.py")
 
 
 def _row_lens(params, P, what):
@@ -1561,65 +1514,53 @@ def _row_lens(params, P, what):
     return out
 
 
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars):
+    """One Adam step of the tensors (lists of equal length, params[0]'s device).  scalars: a flat list of six Python floats
+    per tensor -- 1 - beta1, beta2, 1 - beta2, bc2_sqrt, eps, step_size (r3dgs_adam_segment) -- each rounded to fp32 once."""
+    _need("adam")
+    if _ext is not None:
+        return _ext.adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars)
+    return _adam("adam_step", _lib.r3dgs_adam_step, _adam_segments, 6, (params, grads, exp_avgs, exp_avg_sqs), scalars)
+
+
+def adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars):
+    """The capturable step: steps[i] a device float32 count (read + 1, then bumped), lrs[i] a 0-d device float32 lr or an
+    empty tensor; scalars: a flat list of lr_value, beta1, beta2, eps per tensor (r3dgs_adam_capturable_segment)."""
+    _need("adam")
+    if _ext is not None:
+        return _ext.adam_step_capturable(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars)
+    return _adam("adam_step_capturable", _lib.r3dgs_adam_step_capturable, _adam_capturable_segments, 4,
+                 (params, grads, exp_avgs, exp_avg_sqs, steps, lrs), scalars)
+
+
 def adam_step_visible(params, grads, exp_avgs, exp_avg_sqs, scalars, radii):
     """adam_step for the Gaussians with radii > 0 only (radii: the rasterizer's device int32 [P]; every tensor [P, ...]).
     The rows of the others keep their bits and their gradients are not looked at (r3dgs_adam_step_visible)."""
-    _need_optim_visible()
+    _need("adam_visible")
     if _ext is not None:
         return _ext.adam_step_visible(params, grads, exp_avgs, exp_avg_sqs, scalars, radii)
-    n = len(params)
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n and len(scalars) == 6 * n):
-        raise RuntimeError("adam_step_visible: list lengths differ")
-    if n == 0:
-        return None
-    P = radii.numel()
-    lens = (_i * n)(*_row_lens(params, P, "adam_step_visible"))
-    segs = (_AdamSegment * n)()
-    for i in range(n):
-        segs[i] = _AdamSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(),
-                               params[i].numel(), *scalars[6 * i:6 * i + 6])
-    with _on_device(params[0].device):
-        _check(_lib.r3dgs_adam_step_visible(n, segs, lens, _ptr(radii), P, _stream()), "adam_step_visible")
-    return None
+    return _adam("adam_step_visible", _lib.r3dgs_adam_step_visible, _adam_segments, 6, (params, grads, exp_avgs, exp_avg_sqs),
+                 scalars, radii)
 
 
 def adam_step_capturable_visible(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars, radii):
     """adam_step_capturable for the Gaussians with radii > 0 only; radii is read at replay, like steps and lrs."""
-    _need_optim_visible()
+    _need("adam_visible")
     if _ext is not None:
         return _ext.adam_step_capturable_visible(params, grads, exp_avgs, exp_avg_sqs, steps, lrs, scalars, radii)
-    n = len(params)
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(lrs) == n and len(scalars) == 4 * n):
-        raise RuntimeError("adam_step_capturable_visible: list lengths differ")
-    if n == 0:
-        return None
-    P = radii.numel()
-    lens = (_i * n)(*_row_lens(params, P, "adam_step_capturable_visible"))
-    segs = (_AdamCapturableSegment * n)()
-    for i in range(n):
-        segs[i] = _AdamCapturableSegment(params[i].data_ptr(), grads[i].data_ptr(), exp_avgs[i].data_ptr(),
-                                         exp_avg_sqs[i].data_ptr(), steps[i].data_ptr(), _ptr(lrs[i]), params[i].numel(),
-                                         *scalars[4 * i:4 * i + 4])
-    with _on_device(params[0].device):
-        _check(_lib.r3dgs_adam_step_capturable_visible(n, segs, lens, _ptr(radii), P, _stream()),
-               "adam_step_capturable_visible")
-    return None
+    return _adam("adam_step_capturable_visible", _lib.r3dgs_adam_step_capturable_visible, _adam_capturable_segments, 4,
+                 (params, grads, exp_avgs, exp_avg_sqs, steps, lrs), scalars, radii)
 
 
 # ---- per-iteration training statistics (include/r3dgs_trainstats.h, csrc/train_stats.hip); the surface is r3dgs_train_stats.py,
 # which checks the tensors (one device, dtypes, shapes, contiguity).  These calls only allocate and launch, on the current
 # stream, without a host synchronisation, so they can be captured in a graph.
 
-def _need_stats():
-    if not hasattr(_lib, "r3dgs_visible_means"):
-        raise RuntimeError(f"{_LIB_PATH} has no training statistics (r3dgs_visible_means): rebuild it with build.py")
-
-
 def visible_means(radii, opacity, features_rest):
     """-> (visibility bool[P], n_visible int32 0-d, alpha_mean fp32 0-d or None, sh_abs_mean fp32 0-d or None) of
     r3dgs_visible_means.  opacity: raw fp32 [P] / [P,1] or None; features_rest: fp32 [P,M-1,3] or None (M - 1 may be 0: the mean
     of nothing, NaN).  P == 0 gives n_visible = 0 and NaN means without a launch."""
-    _need_stats()
+    _need("train_stats")
     dev = _need_gpu(radii, "visible_means")
     P = int(radii.numel())
     M = 1 if features_rest is None else int(features_rest.size(1)) + 1
@@ -1645,7 +1586,7 @@ def visible_means(radii, opacity, features_rest):
 def alpha_regul_backward(radii, opacity, upstream, n_visible, grad):
     """grad[i] += upstream * (radii[i] > 0) * sigmoid'(opacity[i]) / n_visible, in place (r3dgs_alpha_regul_backward);
     upstream, n_visible: 0-d device tensors."""
-    _need_stats()
+    _need("train_stats")
     dev = _need_gpu(radii, "alpha_regul_backward")
     if _ext is not None:
         return _ext.alpha_regul_backward(radii, opacity, upstream, n_visible, grad)
@@ -1660,7 +1601,7 @@ def alpha_regul_backward(radii, opacity, upstream, n_visible, grad):
 def densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D):
     """train.py:134 and gaussian_model.py:693-695 in one launch, in place on the three accumulators
     (r3dgs_densification_stats)."""
-    _need_stats()
+    _need("train_stats")
     dev = _need_gpu(radii, "densification_stats")
     if _ext is not None:
         return _ext.densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D)
@@ -1681,21 +1622,16 @@ METRICS_CLAMP, METRICS_QUANTISE8 = 1, 2         # R3DGS_METRICS_*
 METRICS_ROW = 9                                 # R3DGS_METRICS_ROW
 
 
-def _need_metrics():
-    if not hasattr(_lib, "r3dgs_image_metrics"):
-        raise RuntimeError(f"{_LIB_PATH} has no evaluation metrics (r3dgs_image_metrics): rebuild it with build.py")
-
-
 def image_metrics_workspace_bytes(Cc, H, W):
     """Bytes of device scratch r3dgs_image_metrics needs for a [C,H,W] image (0: a shape it refuses)."""
-    _need_metrics()
+    _need("metrics")
     return int(_lib.r3dgs_image_metrics_workspace_bytes(Cc, H, W))
 
 
 def image_metrics(image, gt, gt_layout, flags, row, workspace):
     """Writes the float64 row [METRICS_ROW] of image [C,H,W] against gt (r3dgs_image_metrics); workspace: uint8 tensor of
     image_metrics_workspace_bytes(C, H, W) bytes."""
-    _need_metrics()
+    _need("metrics")
     Cc, H, W = image.shape
     with _on_device(image.device):
         _check(_lib.r3dgs_image_metrics(Cc, H, W, image.data_ptr(), gt.data_ptr(), int(gt_layout), int(flags), row.data_ptr(),
@@ -1705,7 +1641,7 @@ def image_metrics(image, gt, gt_layout, flags, row, workspace):
 
 def row_mse(a, b, rows):
     """-> float64 [rows]: the mean squared error of each of the `rows` equal contiguous slices of a and b (r3dgs_row_mse)."""
-    _need_metrics()
+    _need("metrics")
     dev = a.device
     n = a.numel() // rows
     out = torch.empty((rows,), dtype=torch.float64, device=dev)
@@ -1720,7 +1656,7 @@ def row_mse(a, b, rows):
 
 def image_to_uint8(image):
     """-> uint8 [H,W,C] of image [C,H,W]: save_image's 8-bit rounding (r3dgs_image_to_uint8)."""
-    _need_metrics()
+    _need("metrics")
     Cc, H, W = image.shape
     out = torch.empty((H, W, Cc), dtype=torch.uint8, device=image.device)
     with _on_device(image.device):

@@ -38,8 +38,6 @@ graph; nothing else waits.  No empty_cache().  P == 0 before or after is valid. 
 are non-contiguous tensors, wrong dtypes and tensors whose first dimension is not P.  n_points_cloned, n_points_split and
 n_points_pruned are stored as Python ints.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 from torch import nn
@@ -48,27 +46,14 @@ from diff_gaussian_rasterization import _C
 
 __all__ = ["densify_and_prune", "prune", "prune_points"]
 
-_lib = _C._lib
-if not hasattr(_lib, "r3dgs_densify_plan"):
-    raise ImportError(f"{_C._LIB_PATH} has no densification (r3dgs_densify_plan): rebuild it with build.py")
+_lib = _C._lib   # the r3dgs_densify_* / r3dgs_prune_plan prototypes are rows of _C's ABI table
+_C._need("densify", ImportError)
 
 COPY, ZERO_NEW, XYZ, SCALING = 0, 1, 2, 3     # R3DGS_DENSIFY_*
 MAX_TENSORS, TOTALS = 32, 8
 
 
-class _Tensor(C.Structure):   # r3dgs_densify_tensor
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int), ("kind", C.c_int)]
-
-
-_vp, _i, _f = C.c_void_p, C.c_int, C.c_float
-_lib.r3dgs_densify_workspace_bytes.restype = C.c_size_t
-_lib.r3dgs_densify_workspace_bytes.argtypes = [_i]
-_lib.r3dgs_densify_plan.restype = _i
-_lib.r3dgs_densify_plan.argtypes = [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp]
-_lib.r3dgs_prune_plan.restype = _i
-_lib.r3dgs_prune_plan.argtypes = [_i, _vp, _vp, _vp, _vp]
-_lib.r3dgs_densify_move.restype = _i
-_lib.r3dgs_densify_move.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_Tensor), _vp, _vp, _vp, _vp, _vp, _vp]
+_Tensor = _C._DensifyTensor   # r3dgs_densify_tensor: the struct sits next to the table that declares the pointer to it
 
 _GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
            ("scaling", "_scaling"), ("rotation", "_rotation"))

@@ -9,18 +9,11 @@ marshalled onto r3dgs_knn (include/r3dgs_reduction.h).  No CPU path: tensors mus
      n_indices for the query points listed in q_indices (spatial.cu:43-58); rows ascending by (distance, index), unfilled
      slots FLT_MAX / -1.  Exact tiled scan, O(Q * N): the reference tree never calls it.
 """
-import ctypes as C
-
 import torch
 
 from diff_gaussian_rasterization import _C as _r
 
-_lib = _r._lib
-_lib.r3dgs_knn_max_k.restype = C.c_int
-_lib.r3dgs_knn_workspace_bytes.restype = C.c_size_t
-_lib.r3dgs_knn_workspace_bytes.argtypes = [C.c_int]
-_lib.r3dgs_knn.restype = C.c_int
-_lib.r3dgs_knn.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
+_lib = _r._lib   # the r3dgs_knn* prototypes are rows of diff_gaussian_rasterization._C's ABI table
 
 
 def _run(points, K, want_mean):
@@ -59,12 +52,6 @@ def distCUDA2(points):
 def distIndex2(points, K):
     d, i = _run(points, K, False)
     return [d, i]
-
-
-_lib.r3dgs_knn_query_workspace_bytes.restype = C.c_size_t
-_lib.r3dgs_knn_query_workspace_bytes.argtypes = [C.c_int]
-_lib.r3dgs_knn_query.restype = C.c_int
-_lib.r3dgs_knn_query.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
 
 
 def distIndexQ(points, q_indices, n_indices, K):
