@@ -11,6 +11,7 @@ Per-translation-unit flags matter for parity:
   * -munsafe-fp-atomics: float atomicAdd lowers to global_atomic_add_f32 instead of a CAS loop.
 hipcc cross-compiles without a GPU; the .so travels to the GPU box with the tree.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -51,13 +52,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "densify.hip": EXACT,
     "capi.hip": [],
 }
-HEADERS = ["common.h", "gauss_math.h", "blend_math.h", "depth_sort.h", "loss_math.h", "adam_math.h", "param_math.h", "quant_math.h", "stats_math.h",
-           "metrics_math.h", os.path.join("..", "..", "include", "r3dgs_metrics.h"),
-           os.path.join("..", "..", "include", "r3dgs_rasterizer.h"),
-           os.path.join("..", "..", "include", "r3dgs_quantised.h"),
-           os.path.join("..", "..", "include", "r3dgs_reduction.h"), os.path.join("..", "..", "include", "r3dgs_loss.h"),
-           os.path.join("..", "..", "include", "r3dgs_optim.h"), os.path.join("..", "..", "include", "r3dgs_trainstats.h"),
-           "densify_math.h", os.path.join("..", "..", "include", "r3dgs_densify.h")]
+# every header an object may depend on: all of csrc/ and of the C ABI in include/
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h")))
 
 
 def _newest(paths):
@@ -72,7 +68,7 @@ def build(force=False, verbose=True):
         OUT = os.path.join(HERE, f"libr3dgs_hip_{tag}.so")
     objdir = os.path.join(HERE, "build" + (f"_{tag}" if tag else ""))
     os.makedirs(objdir, exist_ok=True)
-    hdr_time = _newest([os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)])
+    hdr_time = _newest(HEADERS + [os.path.abspath(__file__)])
     jobs = []
     for src, extra in UNITS.items():
         s = os.path.join(CSRC, src)

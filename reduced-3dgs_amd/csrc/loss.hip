@@ -2,69 +2,28 @@
 //
 // What the reference does (utils/loss_utils.py:17-66, train.py:109-115): five 11x11 depthwise F.conv2d calls with zero
 // padding 5 (mu_x, mu_y, E[x^2], E[y^2], E[xy]), about fifteen elementwise ops and autograd's backward of all of them --
-// ~15 full-size intermediate maps forward and twice as many backward.  How it is issued here:
-//   * forward: one workgroup per 64 x 16 output tile of one (image, channel) plane.  x and y are staged with their 5-pixel
-//     halo in LDS (zeros outside the image), the five moments are filtered horizontally into LDS and then vertically in
-//     registers (separable window, the reference's fp32 1-D weights), and per pixel loss_math.h gives S and its three
-//     partials.  The workgroup writes its sums of S and |x - y| to its own workspace slot; in training mode it also
-//     writes the three partial maps (12 B per element), optionally the S map.
+// ~15 full-size intermediate maps forward and twice as many backward.  How it is issued here, on the tile filter of
+// ssim_tile.h (one workgroup per 64 x 16 output tile of one (image, channel) plane):
+//   * forward: x and y are staged, their five moments filtered, and per pixel loss_math.h gives S and its three partials.
+//     The workgroup writes its sums of S and |x - y| to its own workspace slot; in training mode it also writes the three
+//     partial maps (12 B per element), optionally the S map.
 //   * reduction: one workgroup adds the slots of each image in a fixed order (double accumulators) and writes the means,
 //     the per-image means and the combined loss.
-//   * backward: the same tiling over the three partial maps, each scaled by the upstream gradient of S at its pixel; the
-//     transpose of a zero-padded convolution with a symmetric window is the same filter over in-image positions, so
+//   * backward: the three partial maps are staged, each scaled by the upstream gradient of S at its pixel; the transpose
+//     of a zero-padded convolution with a symmetric window is the same filter over in-image positions, so
 //     dx = F[gS dS/dmu_x] + 2x F[gS dS/dE_xx] + y F[gS dS/dE_xy] + g_l1 sign(x - y) / n.
-// No atomics anywhere: every sum has a fixed order, so values and gradients are identical run to run.
+// No atomics anywhere: every sum has a fixed order (ssim_tile.h), so values and gradients are identical run to run.
 #include "../../include/r3dgs_loss.h"
-
-#include <cmath>
 
 #include "common.h"
 #include "loss_math.h"
+#include "ssim_tile.h"
+
+using namespace r3;
 
 namespace {
 
-using r3::kSsimRadius;
-using r3::kSsimTaps;
-
-constexpr int kBlock = 256;
-constexpr int kTW = 64;                     // tile width: one wave spans a tile row
-constexpr int kTH = 16;                     // tile height
-constexpr int kRows = kTH / (kBlock / kTW); // output rows per thread (4)
-constexpr int kInW = kTW + 2 * kSsimRadius; // staged width with halo (74)
-constexpr int kInH = kTH + 2 * kSsimRadius; // staged height with halo (26)
 constexpr int kL1Chunk = 4 * kBlock;        // elements per workgroup of the flat L1 kernel
-
-struct Window {
-    float w[kSsimTaps];
-};
-
-struct Plane {
-    int H, W, tiles_x, tiles_per_plane;
-};
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// Two block-wide sums in a fixed order; thread 0 gets the results.
-__device__ __forceinline__ void block_sum2(float& a, float& b, float (*red)[kBlock / 64])
-{
-    a = wave_sum(a);
-    b = wave_sum(b);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
-}
 
 struct FwdArgs {
     Plane p;
@@ -80,80 +39,27 @@ struct FwdArgs {
 
 __global__ __launch_bounds__(kBlock) void ssim_fwd_kernel(FwdArgs a)
 {
-    __shared__ float sx[kInH][kInW], sy[kInH][kInW];
+    __shared__ float sxy[2][kInH][kInW];
     __shared__ float sh[5][kInH][kTW];
     __shared__ float red[2][kBlock / 64];
-    const int t = threadIdx.x, H = a.p.H, W = a.p.W;
-    const int plane = blockIdx.x / a.p.tiles_per_plane, tile = blockIdx.x - plane * a.p.tiles_per_plane;
-    const int ty = tile / a.p.tiles_x, tx = tile - ty * a.p.tiles_x;
-    const int gx0 = tx * kTW, gy0 = ty * kTH;
-    const size_t base = (size_t)plane * H * W;
+    const int W = a.p.W;
+    const Tile tl = tile_of(a.p);
+    const size_t base = (size_t)tl.plane * a.p.H * W;
     const float* X = a.x + base;
     const float* Y = a.y + base;
-    for (int e = t; e < kInH * kInW; e += kBlock) {
-        const int r = e / kInW, c = e - r * kInW;
-        const int gy = gy0 - kSsimRadius + r, gx = gx0 - kSsimRadius + c;
-        float vx = 0.f, vy = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            const size_t o = (size_t)gy * W + gx;
-            vx = X[o];
-            vy = Y[o];
-        }
-        sx[r][c] = vx;
-        sy[r][c] = vy;
-    }
-    __syncthreads();
-    const int c = t & (kTW - 1), rg = t / kTW;
-    // horizontal pass of the five moments: (kInH rows) x (kTW columns)
-    for (int r = rg; r < kInH; r += kBlock / kTW) {
-        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < kSsimTaps; k++) {
-            const float w = a.win.w[k], xv = sx[r][c + k], yv = sy[r][c + k];
-            m1 = fmaf(w, xv, m1);
-            m2 = fmaf(w, yv, m2);
-            e11 = fmaf(w, xv * xv, e11);
-            e22 = fmaf(w, yv * yv, e22);
-            e12 = fmaf(w, xv * yv, e12);
-        }
-        sh[0][r][c] = m1;
-        sh[1][r][c] = m2;
-        sh[2][r][c] = e11;
-        sh[3][r][c] = e22;
-        sh[4][r][c] = e12;
-    }
-    __syncthreads();
-    // vertical pass: this thread's kRows consecutive output rows of column c
-    const int r0 = rg * kRows;
+    stage_tiles(a.p, tl, sxy, [&](int gy, int gx, float (&v)[2]) {
+        const size_t o = (size_t)gy * W + gx;
+        v[0] = X[o];
+        v[1] = Y[o];
+    });
     float acc[kRows][5];
-#pragma unroll
-    for (int o = 0; o < kRows; o++)
-#pragma unroll
-        for (int m = 0; m < 5; m++) acc[o][m] = 0.f;
-#pragma unroll
-    for (int j = 0; j < kRows + 2 * kSsimRadius; j++) {
-        float v[5];
-#pragma unroll
-        for (int m = 0; m < 5; m++) v[m] = sh[m][r0 + j][c];
-#pragma unroll
-        for (int o = 0; o < kRows; o++) {
-            const int k = j - o;
-            if (k >= 0 && k < kSsimTaps) {
-#pragma unroll
-                for (int m = 0; m < 5; m++) acc[o][m] = fmaf(a.win.w[k], v[m], acc[o][m]);
-            }
-        }
-    }
-    float sum_s = 0.f, sum_l1 = 0.f;
-    const int gx = gx0 + c;
-#pragma unroll
-    for (int o = 0; o < kRows; o++) {
-        const int gy = gy0 + r0 + o;
-        if (gx >= W || gy >= H) continue;
-        const float xv = sx[r0 + o + kSsimRadius][c + kSsimRadius], yv = sy[r0 + o + kSsimRadius][c + kSsimRadius];
-        const r3::SsimPixel px = r3::ssim_pixel(acc[o][0], acc[o][1], acc[o][2], acc[o][3], acc[o][4]);
-        sum_s += px.s;
-        sum_l1 += fabsf(xv - yv);
+    filter_tile(a.win, sh, acc, MomentTaps{sxy});
+    float sums[2] = {0.f, 0.f};   // S, |x - y|
+    for_each_output(a.p, tl, [&](int o, int gy, int gx, int r, int c) {
+        const float xv = sxy[0][r][c], yv = sxy[1][r][c];
+        const SsimPixel px = ssim_pixel(acc[o][0], acc[o][1], acc[o][2], acc[o][3], acc[o][4]);
+        sums[0] += px.s;
+        sums[1] += fabsf(xv - yv);
         const size_t q = base + (size_t)gy * W + gx;
         if (a.ssim_map) a.ssim_map[q] = px.s;
         if (a.partials) {
@@ -161,11 +67,11 @@ __global__ __launch_bounds__(kBlock) void ssim_fwd_kernel(FwdArgs a)
             a.partials[a.n + q] = px.d_exx;
             a.partials[2 * a.n + q] = px.d_exy;
         }
-    }
-    block_sum2(sum_s, sum_l1, red);
-    if (t == 0) {
-        a.slots[blockIdx.x] = sum_s;
-        a.slots[a.nblocks + blockIdx.x] = sum_l1;
+    });
+    block_sums(sums, red);
+    if (threadIdx.x == 0) {
+        a.slots[blockIdx.x] = sums[0];
+        a.slots[a.nblocks + blockIdx.x] = sums[1];
     }
 }
 
@@ -173,18 +79,18 @@ __global__ __launch_bounds__(kBlock) void ssim_fwd_kernel(FwdArgs a)
 __global__ __launch_bounds__(kBlock) void l1_fwd_kernel(long long n, int nblocks, const float* __restrict__ x,
                                                         const float* __restrict__ y, float* __restrict__ slots)
 {
-    __shared__ float red[2][kBlock / 64];
+    __shared__ float red[1][kBlock / 64];
     const long long b0 = (long long)blockIdx.x * kL1Chunk;
-    float s = 0.f, zero = 0.f;
+    float s[1] = {0.f};
 #pragma unroll
     for (int i = 0; i < kL1Chunk / kBlock; i++) {
         const long long e = b0 + i * kBlock + threadIdx.x;
-        if (e < n) s += fabsf(x[e] - y[e]);
+        if (e < n) s[0] += fabsf(x[e] - y[e]);
     }
-    block_sum2(zero, s, red);
+    block_sums(s, red);
     if (threadIdx.x == 0) {
         slots[blockIdx.x] = 0.f;
-        slots[nblocks + blockIdx.x] = s;
+        slots[nblocks + blockIdx.x] = s[0];
     }
 }
 
@@ -199,7 +105,7 @@ struct ReduceArgs {
 // One workgroup: per image, thread-strided double sums of its slots and a fixed tree; images in order.
 __global__ __launch_bounds__(kBlock) void loss_reduce_kernel(ReduceArgs a)
 {
-    __shared__ double rs[kBlock], rl[kBlock];
+    __shared__ double buf[2][kBlock];
     const int t = threadIdx.x;
     double tot_s = 0.0, tot_l = 0.0;
     for (int b = 0; b < a.nimages; b++) {
@@ -209,22 +115,11 @@ __global__ __launch_bounds__(kBlock) void loss_reduce_kernel(ReduceArgs a)
             s += a.slots[first + i];
             l += a.slots[a.nblocks + first + i];
         }
-        rs[t] = s;
-        rl[t] = l;
-        __syncthreads();
-        for (int stride = kBlock / 2; stride > 0; stride >>= 1) {
-            if (t < stride) {
-                rs[t] += rs[t + stride];
-                rl[t] += rl[t + stride];
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            if (a.ssim_image) a.ssim_image[b] = (float)(rs[0] / a.n_image);
-            tot_s += rs[0];
-            tot_l += rl[0];
-        }
-        __syncthreads();
+        s = tree_sum(s, buf[0]);
+        l = tree_sum(l, buf[1]);
+        if (t == 0 && a.ssim_image) a.ssim_image[b] = (float)(s / a.n_image);
+        tot_s += s;
+        tot_l += l;
     }
     if (t == 0) {
         const double l1 = tot_l / a.n_total, s = tot_s / a.n_total;
@@ -254,77 +149,33 @@ __global__ __launch_bounds__(kBlock) void ssim_bwd_kernel(BwdArgs a)
 {
     __shared__ float sq[3][kInH][kInW];
     __shared__ float sh[3][kInH][kTW];
-    const int t = threadIdx.x, H = a.p.H, W = a.p.W;
-    const int plane = blockIdx.x / a.p.tiles_per_plane, tile = blockIdx.x - plane * a.p.tiles_per_plane;
-    const int ty = tile / a.p.tiles_x, tx = tile - ty * a.p.tiles_x;
-    const int gx0 = tx * kTW, gy0 = ty * kTH;
-    const size_t base = (size_t)plane * H * W;
+    const int W = a.p.W;
+    const Tile tl = tile_of(a.p);
+    const size_t base = (size_t)tl.plane * a.p.H * W;
     // upstream gradient of S: uniform for modes 0 and 1
     float gs_uniform = 0.f;
     if (a.g_s && a.mode == 0) gs_uniform = a.coef_s * a.g_s[0] * a.inv_n;
-    if (a.g_s && a.mode == 1) gs_uniform = a.coef_s * a.g_s[plane / a.C] * a.inv_image;
+    if (a.g_s && a.mode == 1) gs_uniform = a.coef_s * a.g_s[tl.plane / a.C] * a.inv_image;
     const float gl = a.g_l1 ? a.coef_l1 * a.g_l1[0] * a.inv_n : 0.f;
-    for (int e = t; e < kInH * kInW; e += kBlock) {
-        const int r = e / kInW, c = e - r * kInW;
-        const int gy = gy0 - kSsimRadius + r, gx = gx0 - kSsimRadius + c;
-        float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-        if (a.g_s && gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            const size_t q = base + (size_t)gy * W + gx;
-            const float g = a.mode == 2 ? a.coef_s * a.g_s[q] : gs_uniform;
-            q0 = g * a.partials[q];
-            q1 = g * a.partials[a.n + q];
-            q2 = g * a.partials[2 * a.n + q];
-        }
-        sq[0][r][c] = q0;
-        sq[1][r][c] = q1;
-        sq[2][r][c] = q2;
-    }
-    __syncthreads();
-    const int c = t & (kTW - 1), rg = t / kTW;
-    for (int r = rg; r < kInH; r += kBlock / kTW) {
-        float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < kSsimTaps; k++) {
-            const float w = a.win.w[k];
-            h0 = fmaf(w, sq[0][r][c + k], h0);
-            h1 = fmaf(w, sq[1][r][c + k], h1);
-            h2 = fmaf(w, sq[2][r][c + k], h2);
-        }
-        sh[0][r][c] = h0;
-        sh[1][r][c] = h1;
-        sh[2][r][c] = h2;
-    }
-    __syncthreads();
-    const int r0 = rg * kRows;
+    stage_tiles(a.p, tl, sq, [&](int gy, int gx, float (&v)[3]) {
+        if (!a.g_s) return;
+        const size_t q = base + (size_t)gy * W + gx;
+        const float g = a.mode == 2 ? a.coef_s * a.g_s[q] : gs_uniform;
+        v[0] = g * a.partials[q];
+        v[1] = g * a.partials[a.n + q];
+        v[2] = g * a.partials[2 * a.n + q];
+    });
     float acc[kRows][3];
+    filter_tile(a.win, sh, acc, [&](int r, int c, float (&v)[3]) {
 #pragma unroll
-    for (int o = 0; o < kRows; o++)
-#pragma unroll
-        for (int m = 0; m < 3; m++) acc[o][m] = 0.f;
-#pragma unroll
-    for (int j = 0; j < kRows + 2 * kSsimRadius; j++) {
-        float v[3];
-#pragma unroll
-        for (int m = 0; m < 3; m++) v[m] = sh[m][r0 + j][c];
-#pragma unroll
-        for (int o = 0; o < kRows; o++) {
-            const int k = j - o;
-            if (k >= 0 && k < kSsimTaps) {
-#pragma unroll
-                for (int m = 0; m < 3; m++) acc[o][m] = fmaf(a.win.w[k], v[m], acc[o][m]);
-            }
-        }
-    }
-    const int gx = gx0 + c;
-#pragma unroll
-    for (int o = 0; o < kRows; o++) {
-        const int gy = gy0 + r0 + o;
-        if (gx >= W || gy >= H) continue;
+        for (int m = 0; m < 3; m++) v[m] = sq[m][r][c];
+    });
+    for_each_output(a.p, tl, [&](int o, int gy, int gx, int, int) {
         const size_t q = base + (size_t)gy * W + gx;
         const float xv = a.x[q], yv = a.y[q];
         const float ds = acc[o][0] + 2.f * xv * acc[o][1] + yv * acc[o][2];
-        a.dx[q] = gl * r3::l1_sign(xv, yv) + ds;
-    }
+        a.dx[q] = gl * l1_sign(xv, yv) + ds;
+    });
 }
 
 __global__ __launch_bounds__(kBlock) void l1_bwd_kernel(long long n, const float* __restrict__ x, const float* __restrict__ y,
@@ -335,43 +186,9 @@ __global__ __launch_bounds__(kBlock) void l1_bwd_kernel(long long n, const float
     dx[e] = grad[0] * inv_n * r3::l1_sign(x[e], y[e]);
 }
 
-// utils/loss_utils.py:24-26: torch.Tensor([exp(...)]) rounds each double to fp32; gauss.sum() of the 11 fp32 values
-// rounds to the same fp32 as their exact sum (checked bit for bit against the reference in tests/test_loss_cpu.py)
-Window make_window()
-{
-    Window w;
-    double sum = 0.0;
-    for (int i = 0; i < kSsimTaps; i++) {
-        const double d = i - kSsimRadius;
-        w.w[i] = (float)std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
-        sum += w.w[i];
-    }
-    const float fsum = (float)sum;
-    for (int i = 0; i < kSsimTaps; i++) w.w[i] = w.w[i] / fsum;
-    return w;
-}
-
-const Window& window()
-{
-    static const Window w = make_window();
-    return w;
-}
-
-Plane plane_of(int H, int W)
-{
-    Plane p;
-    p.H = H;
-    p.W = W;
-    p.tiles_x = (W + kTW - 1) / kTW;
-    p.tiles_per_plane = p.tiles_x * ((H + kTH - 1) / kTH);
-    return p;
-}
-
 long long ssim_blocks(int B, int C, int H, int W)
 {
-    if (B < 1 || C < 1 || H < 1 || W < 1) return -1;
-    const long long nb = (long long)B * C * plane_of(H, W).tiles_per_plane;
-    return nb > 0x7fffffffLL ? -1 : nb;
+    return B < 1 || C < 1 ? -1 : tile_blocks((long long)B * C, H, W);
 }
 
 void check_shape(int B, int C, int H, int W)

@@ -3,74 +3,38 @@
 // What the reference does (train.py:253-265; render.py + metrics.py:24-86): two clamps, l1_loss, psnr and, for metrics.py,
 // the torch-formula ssim -- five 11x11 depthwise convolutions and ~15 full-size intermediate maps -- per view, and one
 // .item()-style host read per metric per view.  How it is issued here:
-//   * image_metrics_kernel: one workgroup per 64 x 16 tile of one channel plane, the tiling of loss.hip's ssim_fwd_kernel.
-//     Image and ground truth are staged ONCE with their 5-pixel halo in LDS through metrics_math.h's metrics_load (uint8
-//     truth, either layout, clamp, 8-bit rounding of the render), zeros outside the image; the five moments are filtered
-//     horizontally into LDS and vertically in registers, loss_math.h gives S per pixel.  |x - y| and (x - y)^2 are taken in
-//     double from the staged values.  The workgroup writes its three double sums to its own workspace slots.  Nothing else
-//     is stored: no map, no partials for a backward.
+//   * image_metrics_kernel: one workgroup per tile of one channel plane, on the tile filter of ssim_tile.h that loss.hip's
+//     ssim_fwd_kernel runs on.  Image and ground truth are staged ONCE through metrics_math.h's metrics_load (uint8 truth,
+//     either layout, clamp, 8-bit rounding of the render); their five moments are filtered and loss_math.h gives S per
+//     pixel.  |x - y| and (x - y)^2 are taken in double from the staged values.  The workgroup writes its three double sums
+//     to its own workspace slots.  Nothing else is stored: no map, no partials for a backward.
 //   * metrics_finish_kernel: one workgroup adds the slots channel by channel in a fixed order and writes the row.
 //   * row_mse_kernel (+ row_mse_finish_kernel for rows longer than one chunk): the drop-in mse / psnr of any [R, n] view.
 //   * to_uint8_kernel: CHW float -> HWC bytes through metrics_quantise8.
-// No atomics anywhere: every sum has a fixed order, so results are identical run to run.
+// No atomics anywhere: every sum has a fixed order (ssim_tile.h), so results are identical run to run.
 #include "../../include/r3dgs_metrics.h"
 
-#include <cmath>
-
-#include "../../include/r3dgs_loss.h"
 #include "common.h"
 #include "loss_math.h"
 #include "metrics_math.h"
+#include "ssim_tile.h"
+
+using namespace r3;
 
 namespace {
 
-using r3::kSsimRadius;
-using r3::kSsimTaps;
-
-constexpr int kBlock = 256;
-constexpr int kTW = 64;                     // tile width: one wave spans a tile row
-constexpr int kTH = 16;                     // tile height
-constexpr int kRows = kTH / (kBlock / kTW); // output rows per thread (4)
-constexpr int kInW = kTW + 2 * kSsimRadius; // staged width with halo (74)
-constexpr int kInH = kTH + 2 * kSsimRadius; // staged height with halo (26)
 constexpr int kSums = 3;                    // per-workgroup slots: sum |x - y|, sum (x - y)^2, sum S
 constexpr int kMseChunk = 16 * kBlock;      // elements per workgroup of row_mse_kernel
 
-struct Window {
-    float w[kSsimTaps];
-};
-
 struct MetricsArgs {
-    int C, H, W, tiles_x, tiles_per_plane, flags;
+    int C;
+    Plane p;
+    int flags;
     const float* x;
     const void* y;
     double* slots;   // [C * tiles_per_plane][kSums]
     Window win;
 };
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// N block-wide double sums in a fixed order; thread 0 gets the results.
-template <int N>
-__device__ __forceinline__ void block_sums(double (&v)[N], double (*red)[kBlock / 64])
-{
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        v[k] = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][wave] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
-}
 
 template <int Layout>
 __device__ __forceinline__ float load_gt(const void* y, int C, int H, int W, int c, int gy, int gx, int flags)
@@ -85,98 +49,30 @@ __device__ __forceinline__ float load_gt(const void* y, int C, int H, int W, int
 template <int Layout>
 __global__ __launch_bounds__(kBlock) void image_metrics_kernel(MetricsArgs a)
 {
-    __shared__ float sx[kInH][kInW], sy[kInH][kInW];
+    __shared__ float sxy[2][kInH][kInW];
     __shared__ float sh[5][kInH][kTW];
     __shared__ double red[kSums][kBlock / 64];
-    const int t = threadIdx.x, H = a.H, W = a.W;
-    const int plane = blockIdx.x / a.tiles_per_plane, tile = blockIdx.x - plane * a.tiles_per_plane;
-    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const int gx0 = tx * kTW, gy0 = ty * kTH;
-    const float* X = a.x + (size_t)plane * H * W;
-    for (int e = t; e < kInH * kInW; e += kBlock) {
-        const int r = e / kInW, c = e - r * kInW;
-        const int gy = gy0 - kSsimRadius + r, gx = gx0 - kSsimRadius + c;
-        float vx = 0.f, vy = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            vx = r3::metrics_load(X[(size_t)gy * W + gx], a.flags);
-            vy = load_gt<Layout>(a.y, a.C, H, W, plane, gy, gx, a.flags);
-        }
-        sx[r][c] = vx;
-        sy[r][c] = vy;
-    }
-    __syncthreads();
-    const int c = t & (kTW - 1), rg = t / kTW;
-    // horizontal pass of the five moments: (kInH rows) x (kTW columns)
-    for (int r = rg; r < kInH; r += kBlock / kTW) {
-        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < kSsimTaps; k++) {
-            const float w = a.win.w[k], xv = sx[r][c + k], yv = sy[r][c + k];
-            m1 = fmaf(w, xv, m1);
-            m2 = fmaf(w, yv, m2);
-            e11 = fmaf(w, xv * xv, e11);
-            e22 = fmaf(w, yv * yv, e22);
-            e12 = fmaf(w, xv * yv, e12);
-        }
-        sh[0][r][c] = m1;
-        sh[1][r][c] = m2;
-        sh[2][r][c] = e11;
-        sh[3][r][c] = e22;
-        sh[4][r][c] = e12;
-    }
-    __syncthreads();
-    // vertical pass: this thread's kRows consecutive output rows of column c
-    const int r0 = rg * kRows;
+    const int H = a.p.H, W = a.p.W;
+    const Tile tl = tile_of(a.p);
+    const float* X = a.x + (size_t)tl.plane * H * W;
+    stage_tiles(a.p, tl, sxy, [&](int gy, int gx, float (&v)[2]) {
+        v[0] = metrics_load(X[(size_t)gy * W + gx], a.flags);
+        v[1] = load_gt<Layout>(a.y, a.C, H, W, tl.plane, gy, gx, a.flags);
+    });
     float acc[kRows][5];
-#pragma unroll
-    for (int o = 0; o < kRows; o++)
-#pragma unroll
-        for (int m = 0; m < 5; m++) acc[o][m] = 0.f;
-#pragma unroll
-    for (int j = 0; j < kRows + 2 * kSsimRadius; j++) {
-        float v[5];
-#pragma unroll
-        for (int m = 0; m < 5; m++) v[m] = sh[m][r0 + j][c];
-#pragma unroll
-        for (int o = 0; o < kRows; o++) {
-            const int k = j - o;
-            if (k >= 0 && k < kSsimTaps) {
-#pragma unroll
-                for (int m = 0; m < 5; m++) acc[o][m] = fmaf(a.win.w[k], v[m], acc[o][m]);
-            }
-        }
-    }
+    filter_tile(a.win, sh, acc, MomentTaps{sxy});
     double sums[kSums] = {0.0, 0.0, 0.0};
-    const int gx = gx0 + c;
-#pragma unroll
-    for (int o = 0; o < kRows; o++) {
-        const int gy = gy0 + r0 + o;
-        if (gx >= W || gy >= H) continue;
-        const float xv = sx[r0 + o + kSsimRadius][c + kSsimRadius], yv = sy[r0 + o + kSsimRadius][c + kSsimRadius];
-        sums[0] += r3::metrics_abs_err(xv, yv);
-        sums[1] += r3::metrics_sq_err(xv, yv);
-        sums[2] += (double)r3::ssim_pixel(acc[o][0], acc[o][1], acc[o][2], acc[o][3], acc[o][4]).s;
-    }
+    for_each_output(a.p, tl, [&](int o, int, int, int r, int c) {
+        const float xv = sxy[0][r][c], yv = sxy[1][r][c];
+        sums[0] += metrics_abs_err(xv, yv);
+        sums[1] += metrics_sq_err(xv, yv);
+        sums[2] += (double)ssim_pixel(acc[o][0], acc[o][1], acc[o][2], acc[o][3], acc[o][4]).s;
+    });
     block_sums(sums, red);
-    if (t == 0) {
+    if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < kSums; k++) a.slots[(size_t)blockIdx.x * kSums + k] = sums[k];
     }
-}
-
-// kBlock-wide tree sum of v in a fixed order through `buf`; every thread gets the total.
-__device__ __forceinline__ double tree_sum(double v, double* buf)
-{
-    const int t = threadIdx.x;
-    buf[t] = v;
-    __syncthreads();
-    for (int stride = kBlock / 2; stride > 0; stride >>= 1) {
-        if (t < stride) buf[t] += buf[t + stride];
-        __syncthreads();
-    }
-    const double total = buf[0];
-    __syncthreads();
-    return total;
 }
 
 __host__ __device__ inline double psnr_db(double mse) { return 10.0 * log10(1.0 / mse); }
@@ -262,22 +158,10 @@ __global__ __launch_bounds__(kBlock) void to_uint8_kernel(int C, long long plane
     out[e] = r3::metrics_quantise8(image[(size_t)c * plane + pix]);
 }
 
-const Window& window()
-{
-    static const Window w = [] {
-        Window v;
-        r3dgs_ssim_window(v.w);   // loss.hip: the reference's fp32 weights, shared rather than restated
-        return v;
-    }();
-    return w;
-}
-
 // workgroups of image_metrics_kernel, or -1 for a shape the entry points refuse
 long long metrics_blocks(int C, int H, int W)
 {
-    if (C < 1 || C > 4 || H < 1 || W < 1) return -1;
-    const long long nb = (long long)C * ((W + kTW - 1LL) / kTW) * ((H + kTH - 1LL) / kTH);
-    return nb > 0x7fffffffLL ? -1 : nb;
+    return C < 1 || C > 4 ? -1 : tile_blocks(C, H, W);
 }
 
 long long mse_chunks(long long R, long long n)
@@ -315,10 +199,7 @@ int r3dgs_image_metrics(int C, int H, int W, const float* image, const void* gt,
         hipStream_t s = static_cast<hipStream_t>(stream);
         MetricsArgs a;
         a.C = C;
-        a.H = H;
-        a.W = W;
-        a.tiles_x = (W + kTW - 1) / kTW;
-        a.tiles_per_plane = (int)(nb / C);
+        a.p = plane_of(H, W);
         a.flags = flags;
         a.x = image;
         a.y = gt;
@@ -331,7 +212,7 @@ int r3dgs_image_metrics(int C, int H, int W, const float* image, const void* gt,
         else
             image_metrics_kernel<R3DGS_GT_U8_HWC><<<(int)nb, kBlock, 0, s>>>(a);
         r3::check_launch("image metrics", s, false);
-        metrics_finish_kernel<<<1, kBlock, 0, s>>>(C, a.tiles_per_plane, (double)H * (double)W, a.slots, row);
+        metrics_finish_kernel<<<1, kBlock, 0, s>>>(C, a.p.tiles_per_plane, (double)H * (double)W, a.slots, row);
         r3::check_launch("metrics finish", s, false);
         return 0;
     });

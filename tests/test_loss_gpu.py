@@ -14,7 +14,7 @@ from tests import loss_ref
 pytestmark = pytest.mark.gpu
 
 LAM = 0.2
-SHAPES = [(3, 1062, 1600), (3, 1080, 1920), (2, 3, 37, 131), (1, 3, 5, 7), (1, 1, 1, 1)]
+SHAPES = [(3, 1062, 1600), (3, 1080, 1920), (2, 3, 37, 131), (1, 3, 5, 7), (1, 1, 1, 1), (1, 3, 16, 64), (1, 3, 17, 65)]
 VALUE_SETS = ["unrelated", "near", "bright"]
 
 

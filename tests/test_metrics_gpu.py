@@ -3,7 +3,7 @@ image_metrics over the shapes at which a tiled window kernel and a strided reduc
 flag combination, infinities and NaN, the drop-in psnr / mse and to_uint8 against the reference's recorded output, determinism,
 graph capture, and evaluate() over a camera set for a dense and a quantised model.
 
-The kernel's tile is 64 x 16 (csrc/metrics.hip kTW, kTH), so the shapes are the issue's: one pixel; 3x17x70, one pixel past a
+The kernel's tile is 64 x 16 (csrc/ssim_tile.h kTW, kTH), so the shapes are the issue's: one pixel; 3x17x70, one pixel past a
 tile edge in each direction; 3x5x3, smaller than the window; the fixture's 3x40x56; 4x33x130; and 2x64x64, exact tiles.
 
 Bars, all against tests/metrics_ref.py fed the same arrays (n = the element count of the mean in question):
@@ -27,6 +27,7 @@ from tests import metrics_ref
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (3, 17, 70), (3, 5, 3), (3, 40, 56), (4, 33, 130), (2, 64, 64)]
+PARITY_SHAPES = SHAPES + [(3, 16, 64), (3, 17, 65)]   # exactly one tile; one pixel past the tile edge in both directions
 LAYOUTS = {"f32": _C.GT_F32_CHW, "u8_chw": _C.GT_U8_CHW, "u8_hwc": _C.GT_U8_HWC}
 DB = 10.0 * math.log10(math.e)
 U = 2.0 ** -52
@@ -80,7 +81,7 @@ def check_row(got, ref, shape, what):
             assert abs(g - r) <= n * U * abs(r), (what, name, g, r)
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=["x".join(map(str, s)) for s in SHAPES])
+@pytest.mark.parametrize("shape", PARITY_SHAPES, ids=["x".join(map(str, s)) for s in PARITY_SHAPES])
 def test_image_metrics_float64_parity(shape):
     image, gts = inputs(shape, seed=sum(shape))
     xt = dv(image)
