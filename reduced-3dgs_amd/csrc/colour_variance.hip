@@ -9,19 +9,11 @@
 // mean in both factors (tensor aliasing at reduced_3dgs.cu:185), colour slots above a Gaussian's own degree are
 // 0, Gaussians not present in a view keep their statistics.
 #include "common.h"
+#include "sh_rows.h"
 
 namespace r3 {
 
 constexpr int kCvBlock = 256;
-constexpr int kCvWaveShFloats = 64 * 48 + (64 * 48) / 32;
-
-__device__ __forceinline__ int cskew(int e) { return e + (e >> 5); }
-
-struct CvShRowLds {
-    const float* base;
-    int roff;
-    __device__ __forceinline__ float at(int e) const { return base[cskew(roff + e)]; }
-};
 
 struct CvArgs {
     int P, M, max_deg;
@@ -41,7 +33,7 @@ struct CvArgs {
 
 __global__ __launch_bounds__(kCvBlock) void colour_variance_accumulate_kernel(CvArgs a)
 {
-    __shared__ float s_sh[kCvBlock / 64][kCvWaveShFloats];
+    __shared__ float s_sh[kCvBlock / 64][kWaveShFloats];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = a.P, M = a.M;
     const int i = blockIdx.x * kCvBlock + tid;
@@ -54,7 +46,7 @@ __global__ __launch_bounds__(kCvBlock) void colour_variance_accumulate_kernel(Cv
     float* lds = s_sh[wave];
     if (__ballot(present) != 0ull) {
         const float* src = a.shs + span_first;
-        for (int e = lane; e < span_len; e += 64) lds[cskew(e)] = src[e];
+        for (int e = lane; e < span_len; e += 64) lds[sh_skew<false>(e)] = src[e];   // (the general skew at every M: sh_rows.h)
     }
     __syncthreads();
     if (!valid) return;
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(kCvBlock) void colour_variance_accumulate_kernel(Cv
 #pragma unroll
     for (int k = 0; k < 12; k++) col[k] = 0.f;
     const float campos[3] = {a.campos[0], a.campos[1], a.campos[2]};
-    CvShRowLds row{lds, lane * 3 * M};
+    const ShRow<false, const float> row = sh_row<false, const float>(lds, lane, lane * 3 * M);
     sh_truncated_colours(a.degs[i], a.max_deg + 1, row, a.means[3 * i], a.means[3 * i + 1], a.means[3 * i + 2], campos, col);
     const float* full = col + 3 * a.max_deg;
     for (int cur = 0; cur < a.max_deg; cur++) {

@@ -19,149 +19,17 @@
 
 #include "depth_sort.h"
 #include "quant_math.h"
+#include "sh_rows.h"
 
 namespace r3 {
 
 constexpr int kPreBlock = kPreBlockSize;
-constexpr int kMaxCoeff = 16;
-constexpr int kRowFloats = 3 * kMaxCoeff;                        // 48
-constexpr int kWaveShFloats = 64 * kRowFloats + (64 * kRowFloats) / 32;  // + bank skew
 
-// Where float e of a wave's SH span sits in LDS (the lanes read the same element of 64 different rows: the rows must start
-// in different banks).  ROWS48 -- a dense [P,16,3] tensor, rows of 48 floats: one word of padding per row, element e of
-// the lane's row is base[49 * lane + e] and e folds into the instruction's offset field; otherwise (ragged rows, other M)
-// one word of padding per 32 and the address is computed per access.
-template <bool ROWS48>
-__device__ __forceinline__ int skew(int e)
+// chunks of BLOCK Gaussians (one round of a workgroup of the geometry kernel or of a colour role) that cover P
+template <int BLOCK = kPreBlock>
+__host__ __device__ constexpr int pre_chunks(int P)
 {
-    if (ROWS48) return e + (int)(((uint32_t)e * 43691u) >> 21);   // e + e / 48 for e < 2^16
-    return e + (e >> 5);
-}
-
-template <bool ROWS48>
-struct ShRowLds {
-    const float* base;   // ROWS48: the lane's row (span + 49 * lane); else the wave's span
-    int roff;            // ROWS48: 0; else first float of the lane's row in the span
-    __device__ __forceinline__ float at(int e) const { return ROWS48 ? base[e] : base[skew<false>(roff + e)]; }
-};
-
-// the wave's span (n4 float4s at src4) -> LDS, twelve loads per lane in flight
-template <bool ROWS48>
-__device__ __forceinline__ void stage_span(const float4* __restrict__ src4, int n4, float* dst, int lane)
-{
-    constexpr int kBatch = 12;
-    for (int base = 0; base < n4; base += 64 * kBatch) {
-        float4 v[kBatch];
-#pragma unroll
-        for (int k = 0; k < kBatch; k++) {
-            const int e4 = base + k * 64 + lane;
-            v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int k = 0; k < kBatch; k++) {
-            const int e4 = base + k * 64 + lane;
-            if (e4 < n4) {
-                const int e = e4 << 2;
-                if (ROWS48) {   // 48 % 4 == 0: the four floats are in one row
-                    float* d = dst + skew<true>(e);
-                    d[0] = v[k].x;
-                    d[1] = v[k].y;
-                    d[2] = v[k].z;
-                    d[3] = v[k].w;
-                } else {
-                    dst[skew<false>(e)] = v[k].x;
-                    dst[skew<false>(e + 1)] = v[k].y;
-                    dst[skew<false>(e + 2)] = v[k].z;
-                    dst[skew<false>(e + 3)] = v[k].w;
-                }
-            }
-        }
-    }
-}
-
-// ---- SH rows that arrive as two tensors (raw-parameter entry: features_dc [P,1,3], features_rest [P,M-1,3]) -------------
-// The wave's 64 rows are one contiguous span of EACH tensor; both are copied into the LDS row layout above, so that
-// everything behind the staging is untouched.  Float f of a span whose rows are `rl` floats long (3 for dc, 3 (M - 1) for
-// rest) and start at float `k0` of the joined row (0 / 3) belongs to row f / rl: joined-span element row * 3M + k0 + f % rl.
-// ROWS48 (M == 16): LDS word 49 * row + k0 + f % rl = f + (49 - rl) * row + k0 -- one multiply-high per float.
-template <bool ROWS48>
-__device__ __forceinline__ int split_lds_index(int f, int rl, int k0, int M)
-{
-    if (ROWS48) {
-        // rl is 3 or 45 here (k0 says which): f / 3 and f / 45 for f < 2^16 by multiply and shift
-        const int row = k0 == 0 ? (int)(((uint32_t)f * 43691u) >> 17) : (int)(((uint32_t)f * 46604u) >> 21);
-        return f + (49 - rl) * row + k0;
-    }
-    const int row = f / rl;
-    return skew<false>(row * 3 * M + k0 + (f - row * rl));
-}
-
-// one of the two spans (len floats at src, 16-byte aligned and len % 4 == 0 when VEC) -> LDS
-template <bool ROWS48, bool VEC>
-__device__ __forceinline__ void stage_split_span(const float* __restrict__ src, int len, int rl, int k0, int M, float* dst,
-                                                 int lane)
-{
-    if (VEC) {
-        constexpr int kBatch = 6;
-        const float4* src4 = reinterpret_cast<const float4*>(src);
-        const int n4 = len >> 2;
-        for (int base = 0; base < n4; base += 64 * kBatch) {
-            float4 v[kBatch];
-#pragma unroll
-            for (int k = 0; k < kBatch; k++) {
-                const int e4 = base + k * 64 + lane;
-                v[k] = e4 < n4 ? src4[e4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int k = 0; k < kBatch; k++) {
-                const int e4 = base + k * 64 + lane;
-                if (e4 < n4) {
-                    const int f = e4 << 2;
-                    dst[split_lds_index<ROWS48>(f, rl, k0, M)] = v[k].x;
-                    dst[split_lds_index<ROWS48>(f + 1, rl, k0, M)] = v[k].y;
-                    dst[split_lds_index<ROWS48>(f + 2, rl, k0, M)] = v[k].z;
-                    dst[split_lds_index<ROWS48>(f + 3, rl, k0, M)] = v[k].w;
-                }
-            }
-        }
-    } else {
-        for (int f = lane; f < len; f += 64) dst[split_lds_index<ROWS48>(f, rl, k0, M)] = src[f];
-    }
-}
-
-// both spans of the wave's `nrows` rows starting at Gaussian wave_first
-template <bool ROWS48>
-__device__ __forceinline__ void stage_split_rows(const float* __restrict__ dc, const float* __restrict__ rest, int wave_first,
-                                                 int nrows, int M, float* dst, int lane)
-{
-    const int rl = 3 * (M - 1);
-    const float* s_dc = dc + 3L * wave_first;
-    const int n_dc = 3 * nrows, n_rest = rl * nrows;
-    // 16-byte aligned spans: wave_first is a multiple of 64, so both start aligned; full waves have lengths % 4 == 0
-    if ((nrows & 3) == 0) {
-        stage_split_span<ROWS48, true>(s_dc, n_dc, 3, 0, M, dst, lane);
-        if (M > 1) stage_split_span<ROWS48, true>(rest + (long)rl * wave_first, n_rest, rl, 3, M, dst, lane);
-    } else {
-        stage_split_span<ROWS48, false>(s_dc, n_dc, 3, 0, M, dst, lane);
-        if (M > 1) stage_split_span<ROWS48, false>(rest + (long)rl * wave_first, n_rest, rl, 3, M, dst, lane);
-    }
-}
-
-// forward.cu:19-36 getSHOffset (float3 units)
-__device__ __forceinline__ int ragged_offset(int idx, const int* coeffs, const int* perband, const int* cumsum, int* deg)
-{
-    int off = 0;
-    *deg = 0;
-    if (idx < cumsum[0]) return idx * coeffs[0];
-    *deg = 1;
-    off += perband[0] * coeffs[0];
-    if (idx < cumsum[1]) return off + (idx - cumsum[0]) * coeffs[1];
-    *deg = 2;
-    off += perband[1] * coeffs[1];
-    if (idx < cumsum[2]) return off + (idx - cumsum[1]) * coeffs[2];
-    *deg = 3;
-    off += perband[2] * coeffs[2];
-    return off + (idx - cumsum[2]) * coeffs[3];
+    return (P + BLOCK - 1) / BLOCK;
 }
 
 // ---- kernel 1: geometry ---------------------------------------------------------------------------
@@ -290,7 +158,8 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
 // ---- kernel 2: colour -------------------------------------------------------------------------------
 // SH -> RGB (forward.cu:105-159, ragged variant :19-100) or copy of the precomputed colours into the
 // records of the visible Gaussians.  Streams the SH tensor (192 B per Gaussian at degree 3): the wave's 64 rows
-// are one contiguous span, staged through LDS with dwordx4 loads, evaluated per lane from LDS.
+// are one contiguous span, staged through LDS with dwordx4 loads, evaluated per lane from LDS (sh_rows.h: the layout, the
+// row accessor and the staging; twelve loads per lane in flight).
 // Launched as a SMALL persistent grid (issue_preprocess_color): the kernel is bandwidth-bound filler next to the
 // latency-bound depth-sort kernels of the main stream, and a full grid's LDS footprint (3 x 49 KB per CU) left their
 // workgroups no room -- the depth scatter kernel took 46 us instead of 14 us beside it.
@@ -307,7 +176,7 @@ __device__ __forceinline__ void store_color(GRec* r, const float* rgb, uint32_t 
 
 // chunks [first + wg, last) in steps of n_wg, BLOCK Gaussians each (BLOCK = workgroup size, always kPreBlock); smem: BLOCK / 64
 // wave windows.
-// SPLIT: the rows come from two tensors, in.shs = features_dc and shs_rest (stage_split_rows); the LDS layout is the same.
+// SPLIT: the rows come from two tensors, in.shs = features_dc and shs_rest (sh_rows.h stage_split_rows); the LDS layout is the same.
 template <bool RAGGED, int BLOCK, bool SPLIT = false>
 __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int first, int last, int wg, int n_wg,
                                            const float* shs_rest = nullptr)
@@ -331,12 +200,12 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
         if (RAGGED) {
             const int last_i = min(wave_first + 63, P - 1);
             int d0, dl;
-            const int off_first = wave_first < P ? ragged_offset(wave_first, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &d0) : 0;
-            const int off_last = wave_first < P ? ragged_offset(last_i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &dl) : 0;
+            const int off_first = wave_first < P ? quant_ragged_offset(wave_first, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &d0) : 0;
+            const int off_last = wave_first < P ? quant_ragged_offset(last_i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &dl) : 0;
             span_first = 3L * off_first;
             span_len = wave_first < P ? 3 * (off_last + (dl + 1) * (dl + 1) - off_first) : 0;
             if (valid) {
-                const int off = ragged_offset(i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &deg);
+                const int off = quant_ragged_offset(i, a.in.coeffs_num, a.in.per_band_count, a.in.cumsum_count, &deg);
                 roff = 3 * (off - off_first);
             }
         } else {
@@ -357,21 +226,8 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
             else
                 stage_split_rows<false>(a.in.shs, shs_rest, wave_first, nrows, M, s_sh[wave], lane);
         }
-    } else if (wave_needs) {
-        const float* src = a.in.shs + span_first;
-        float* dst = s_sh[wave];
-        if (((span_first | span_len) & 3) == 0) {  // 16-B aligned span (always true for M = 16): dwordx4 loads
-            // Twelve loads per lane cover a full degree-3 span (64 rows x 192 B).  They are issued back to back before the
-            // first LDS store: with one load in flight per wave (load, wait, store, next load) the kernel ran at the
-            // 2 TB/s that 12 waves/CU x 1 KB per memory latency allow.
-            const float4* src4 = reinterpret_cast<const float4*>(src);
-            if (rows48)
-                stage_span<true>(src4, span_len >> 2, dst, lane);
-            else
-                stage_span<false>(src4, span_len >> 2, dst, lane);
-        } else {
-            for (int e = lane; e < span_len; e += 64) dst[rows48 ? skew<true>(e) : skew<false>(e)] = src[e];
-        }
+    } else if (wave_needs) {   // twelve loads per lane cover a full degree-3 span (64 rows x 192 B)
+        stage_span<12>(a.in.shs, span_first, span_len, rows48, s_sh[wave], lane);
     }
     __syncthreads();
 
@@ -394,9 +250,9 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
                 }
             };
             if (rows48)
-                eval(ShRowLds<true>{s_sh[wave] + 49 * lane, 0});
+                eval(sh_row<true, const float>(s_sh[wave], lane, roff));
             else
-                eval(ShRowLds<false>{s_sh[wave], roff});
+                eval(sh_row<false, const float>(s_sh[wave], lane, roff));
         } else {
             rgb[0] = a.in.colors_precomp[3 * i];
             rgb[1] = a.in.colors_precomp[3 * i + 1];
@@ -416,7 +272,7 @@ __device__ __forceinline__ void color_role(const PreArgs& a, char* smem, int fir
 // codebooks (16 KB) are copied into LDS once per workgroup; a lane evaluates sh_to_rgb through an accessor that reads an id
 // byte of its row and gathers the centre -- the same values in the same order as the fp32 ragged path reads from its row.
 // LDS words of the id window are skewed one per 32 like the fp32 rows (lanes of a degree read 3 / 12 / 27 / 48 B apart).
-constexpr int kQuantSpanChunks = (64 * kRowFloats + 15 + 15) / 16 + 1;                 // 16-byte chunks of a misaligned span
+constexpr int kQuantSpanChunks = (64 * kShRowFloats + 15 + 15) / 16 + 1;                 // 16-byte chunks of a misaligned span
 constexpr int kQuantSpanWords = 4 * kQuantSpanChunks + (4 * kQuantSpanChunks) / 32 + 1;   // + skew
 constexpr size_t kQuantBooksLds = sizeof(float) * kQuantShBooks * kQuantCentres;
 constexpr size_t kQuantColorLds = kQuantBooksLds + sizeof(uint32_t) * (kPreBlock / 64) * kQuantSpanWords;
@@ -429,7 +285,7 @@ struct ShRowQuantLds {
     __device__ __forceinline__ float at(int e) const
     {
         const int b = roff + e, w = b >> 2;
-        const uint32_t id = ids[((w + (w >> 5)) << 2) | (b & 3)];
+        const uint32_t id = ids[(sh_skew<false>(w) << 2) | (b & 3)];
         return books[(quant_sh_book(e) << 8) + (int)id];
     }
 };
@@ -497,7 +353,7 @@ __device__ __forceinline__ void color_role_quant(const PreArgs& a, const QuantIn
             const int c = k * 64 + lane;
             if (c < nchunks) {
                 const int w = 4 * c;   // four words of one chunk never straddle a skew step: 4 c % 32 <= 28
-                uint32_t* d = s_ids[wave] + w + (w >> 5);
+                uint32_t* d = s_ids[wave] + w + (w >> 5);   // word sh_skew<false>(w)
                 d[0] = v[k].x;
                 d[1] = v[k].y;
                 d[2] = v[k].z;
@@ -526,7 +382,7 @@ __global__ __launch_bounds__(BLOCK) void preprocess_color_kernel(const PreArgs* 
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PreArgs a = *ap;
-    color_role<RAGGED, BLOCK>(a, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x);
+    color_role<RAGGED, BLOCK>(a, smem, 0, pre_chunks<BLOCK>(a.in.P), (int)blockIdx.x, (int)gridDim.x);
 }
 
 template <int BLOCK>
@@ -534,7 +390,7 @@ __global__ __launch_bounds__(BLOCK) void preprocess_color_params_kernel(const Fw
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PreArgs a = pa->pre;
-    color_role<false, BLOCK, true>(a, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x, pa->shs_rest);
+    color_role<false, BLOCK, true>(a, smem, 0, pre_chunks<BLOCK>(a.in.P), (int)blockIdx.x, (int)gridDim.x, pa->shs_rest);
 }
 
 template <int BLOCK>
@@ -543,12 +399,25 @@ __global__ __launch_bounds__(BLOCK) void preprocess_color_quant_kernel(const Fwd
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PreArgs a = pa->pre;
     const QuantInputs qi = pa->quant;
-    color_role_quant<BLOCK>(a, qi, smem, 0, (a.in.P + BLOCK - 1) / BLOCK, (int)blockIdx.x, (int)gridDim.x);
+    color_role_quant<BLOCK>(a, qi, smem, 0, pre_chunks<BLOCK>(a.in.P), (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- depth-sort kernels carrying a share of the colour stream in extra workgroups -------------------------------
 // Workgroups [0, n_sort) run the depth-sort role, workgroups [n_sort, n_sort + n_color) the colour chunks
 // [c0, c1).  One dynamic LDS window serves whichever role a workgroup has.
+// the sort role of launch STEP: histogram, scatter, bucket sort
+template <int STEP>
+__device__ __forceinline__ void depth_sort_role(const FwdPassArgs* __restrict__ pa, char* smem, int wg, int n_sort)
+{
+    const DepthArgs d = pa->depth;
+    if (STEP == 0)
+        depth_hist_role(d, pa->header, smem, wg);
+    else if (STEP == 1)
+        depth_scatter_role(d, smem, wg);
+    else
+        depth_bucket_group_role(d, smem, wg, n_sort);
+}
+
 template <int STEP, bool RAGGED>
 __global__ __launch_bounds__(kPreBlock) void depth_sort_color_kernel(const FwdPassArgs* __restrict__ pa, int n_sort,
                                                                      int c0, int c1)
@@ -556,13 +425,7 @@ __global__ __launch_bounds__(kPreBlock) void depth_sort_color_kernel(const FwdPa
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wg = (int)blockIdx.x;
     if (wg < n_sort) {
-        const DepthArgs d = pa->depth;
-        if (STEP == 0)
-            depth_hist_role(d, pa->header, smem, wg);
-        else if (STEP == 1)
-            depth_scatter_role(d, smem, wg);
-        else
-            depth_bucket_group_role(d, smem, wg, n_sort);
+        depth_sort_role<STEP>(pa, smem, wg, n_sort);
     } else {
         const PreArgs a = pa->pre;
         color_role<RAGGED, kPreBlock>(a, smem, c0, c1, wg - n_sort, (int)gridDim.x - n_sort);
@@ -577,13 +440,7 @@ __global__ __launch_bounds__(kPreBlock) void depth_sort_color_params_kernel(cons
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wg = (int)blockIdx.x;
     if (wg < n_sort) {
-        const DepthArgs d = pa->depth;
-        if (STEP == 0)
-            depth_hist_role(d, pa->header, smem, wg);
-        else if (STEP == 1)
-            depth_scatter_role(d, smem, wg);
-        else
-            depth_bucket_group_role(d, smem, wg, n_sort);
+        depth_sort_role<STEP>(pa, smem, wg, n_sort);
     } else {
         const PreArgs a = pa->pre;
         color_role<false, kPreBlock, true>(a, smem, c0, c1, wg - n_sort, (int)gridDim.x - n_sort, pa->shs_rest);
@@ -598,13 +455,7 @@ __global__ __launch_bounds__(kPreBlock) void depth_sort_color_quant_kernel(const
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wg = (int)blockIdx.x;
     if (wg < n_sort) {
-        const DepthArgs d = pa->depth;
-        if (STEP == 0)
-            depth_hist_role(d, pa->header, smem, wg);
-        else if (STEP == 1)
-            depth_scatter_role(d, smem, wg);
-        else
-            depth_bucket_group_role(d, smem, wg, n_sort);
+        depth_sort_role<STEP>(pa, smem, wg, n_sort);
     } else {
         const PreArgs a = pa->pre;
         const QuantInputs qi = pa->quant;
@@ -620,7 +471,7 @@ __global__ __launch_bounds__(64 * kColWaves) void depth_colscan_kernel(const Dep
 
 void issue_preprocess_geom(const FwdPlan& p, FwdPassArgs* dst, const FwdPassArgs& v, hipStream_t s)
 {
-    const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
+    const int blocks = pre_chunks(p.P);
     if (p.quant)
         hipLaunchKernelGGL(preprocess_geom_kernel<5>, dim3(blocks), dim3(kPreBlock), 0, s, dst, v);
     else if (p.raw_params)
@@ -661,7 +512,7 @@ static const ColorSource& color_source(const FwdPlan& p)
 
 void issue_preprocess_color(const FwdPlan& p, const PreArgs* a, hipStream_t s)
 {
-    const int blocks = (p.P + kPreBlock - 1) / kPreBlock;
+    const int blocks = pre_chunks(p.P);
     const int grid = p.color_grid > 0 && blocks > p.color_grid ? p.color_grid : blocks;
     const ColorSource& src = color_source(p);
     void* args[] = {&a};
@@ -702,7 +553,7 @@ void prepare_depth_bucket_sort(int nb)
 void issue_depth_sort_and_color(const FwdPlan& p, const FwdPassArgs* pa, hipStream_t s)
 {
     const int rows = (int)depth_hist_rows((size_t)p.P), nb = p.nb;
-    const int chunks = (p.P + kPreBlock - 1) / kPreBlock;
+    const int chunks = pre_chunks(p.P);
     int c[4] = {0, 0, 0, chunks};
     c[1] = (int)((long long)chunks * p.color_split[0] / 100);
     c[2] = c[1] + (int)((long long)chunks * p.color_split[1] / 100);

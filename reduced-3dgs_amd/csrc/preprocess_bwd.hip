@@ -14,6 +14,7 @@
 // Every output element of every Gaussian is written (zeros where the reference leaves its
 // zero-initialised tensors untouched), so outputs may be uninitialised memory.
 #include "common.h"
+#include "sh_rows.h"
 
 namespace r3 {
 
@@ -22,107 +23,6 @@ namespace r3 {
 // dL_dsh row stores of different waves overlap: 0.194 -> 0.181 ms at 2 M Gaussians, 0.574 -> 0.539 at 6 M, unchanged at
 // 500 k (0.062-0.064 either way); 128: in between.
 constexpr int kBwdBlock = 64;
-constexpr int kBwdWaveShFloats = 64 * 48 + (64 * 48) / 32;
-
-// Where float e of the wave's span (64 rows x 3M floats, row after row) sits in LDS.  The lanes of a wave read the same
-// element of 64 different rows, so the rows must start in different banks.
-//   ROWS48 (M == 16, every dense degree-3 tensor): one word of padding per row, i.e. rows 49 words apart.  Element e of
-//     lane's row is base[49 * lane + e]: the compiler folds e into the instruction's offset field, no address arithmetic
-//     per access (the general scheme below spent 30 % of the kernel's vector instructions on it).
-//   otherwise: one word of padding per 32.
-template <bool ROWS48>
-__device__ __forceinline__ int bskew(int e)
-{
-    if (ROWS48) return e + (int)(((uint32_t)e * 43691u) >> 21);   // e + e / 48 for e < 2^16
-    return e + (e >> 5);
-}
-
-template <bool ROWS48>
-struct ShRowLdsRW {
-    float* base;   // ROWS48: already advanced to the lane's row (base + 49 * lane); else the wave's span
-    int roff;      // ROWS48: 0; else first float of the lane's row in the span
-    __device__ __forceinline__ float at(int e) const { return ROWS48 ? base[e] : base[bskew<false>(roff + e)]; }
-    __device__ __forceinline__ void put(int e, float v) const
-    {
-        if (ROWS48)
-            base[e] = v;
-        else
-            base[bskew<false>(roff + e)] = v;
-    }
-};
-
-// ---- SH rows as two tensors (raw-parameter backward: features_dc [P,1,3] / features_rest [P,M-1,3] in, their gradients out)
-// Same scheme as the forward's colour role (preprocess.hip split_lds_index): float f of a span whose rows are `rl` floats long
-// (3 for dc, 3 (M - 1) for rest) and start at float `k0` of the joined row (0 / 3) is joined-span element
-// (f / rl) * 3M + k0 + f % rl; the LDS row layout -- the contract with sh_backward -- is the one above.
-template <bool ROWS48>
-__device__ __forceinline__ int split_lds_index(int f, int rl, int k0, int M)
-{
-    if (ROWS48) {   // rl is 3 or 45 (k0 says which): f / 3 and f / 45 for f < 2^16 by multiply and shift
-        const int row = k0 == 0 ? (int)(((uint32_t)f * 43691u) >> 17) : (int)(((uint32_t)f * 46604u) >> 21);
-        return f + (49 - rl) * row + k0;
-    }
-    const int row = f / rl;
-    return bskew<false>(row * 3 * M + k0 + (f - row * rl));
-}
-
-// one span (len floats, 16-byte aligned and len % 4 == 0 when VEC) global -> LDS
-template <bool ROWS48, bool VEC>
-__device__ __forceinline__ void stage_split_span(const R3_GLOBAL float* __restrict__ src, int len, int rl, int k0, int M, float* lds,
-                                                 int lane)
-{
-    if (VEC) {
-        constexpr int kBatch = 6;
-        const R3_GLOBAL float4* src4 = reinterpret_cast<const R3_GLOBAL float4*>(src);
-        const int n4 = len >> 2;
-        for (int base = 0; base < n4; base += 64 * kBatch) {
-            float4 v[kBatch];
-#pragma unroll
-            for (int k = 0; k < kBatch; k++) {
-                const int e4 = base + k * 64 + lane;
-                v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e4 < n4) v[k] = src4[e4];
-            }
-#pragma unroll
-            for (int k = 0; k < kBatch; k++) {
-                const int e4 = base + k * 64 + lane;
-                if (e4 < n4) {
-                    const int f = e4 << 2;
-                    lds[split_lds_index<ROWS48>(f, rl, k0, M)] = v[k].x;
-                    lds[split_lds_index<ROWS48>(f + 1, rl, k0, M)] = v[k].y;
-                    lds[split_lds_index<ROWS48>(f + 2, rl, k0, M)] = v[k].z;
-                    lds[split_lds_index<ROWS48>(f + 3, rl, k0, M)] = v[k].w;
-                }
-            }
-        }
-    } else {
-        for (int f = lane; f < len; f += 64) lds[split_lds_index<ROWS48>(f, rl, k0, M)] = src[f];
-    }
-}
-
-// one span LDS -> global (the gradient rows), or zeros when the wave built no rows
-template <bool ROWS48, bool VEC>
-__device__ __forceinline__ void unstage_split_span(R3_GLOBAL float* __restrict__ dst, int len, int rl, int k0, int M, const float* lds,
-                                                   int lane, bool rows)
-{
-    if (VEC) {
-        R3_GLOBAL float4* dst4 = reinterpret_cast<R3_GLOBAL float4*>(dst);
-        const int n4 = len >> 2;
-        if (rows) {
-            for (int e4 = lane; e4 < n4; e4 += 64) {
-                const int f = e4 << 2;
-                dst4[e4] = make_float4(lds[split_lds_index<ROWS48>(f, rl, k0, M)], lds[split_lds_index<ROWS48>(f + 1, rl, k0, M)],
-                                       lds[split_lds_index<ROWS48>(f + 2, rl, k0, M)], lds[split_lds_index<ROWS48>(f + 3, rl, k0, M)]);
-            }
-        } else {
-            for (int e4 = lane; e4 < n4; e4 += 64) dst4[e4] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else if (rows) {
-        for (int f = lane; f < len; f += 64) dst[f] = lds[split_lds_index<ROWS48>(f, rl, k0, M)];
-    } else {
-        for (int f = lane; f < len; f += 64) dst[f] = 0.f;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Per-Gaussian sums of the per-(tile, Gaussian)-pair gradients written by the backward blend.
@@ -262,7 +162,7 @@ void issue_pair_reduce(const BwdPlan& p, const PairReduceArgs* a, hipStream_t s)
 template <bool ROWS48, bool F64, bool RAW = false>
 __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdArgs* __restrict__ ap)
 {
-    __shared__ float s_sh[kBwdBlock / 64][kBwdWaveShFloats];
+    __shared__ float s_sh[kBwdBlock / 64][kWaveShFloats];
     const PreBwdArgs a = *ap;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = a.in.P, M = a.in.M;
@@ -338,56 +238,12 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         const int steps = (int)(blockIdx.x / (256u * (256 / kBwdBlock))) * a.stagger;
         for (int k = 0; k < steps; k += 127) __builtin_amdgcn_s_sleep(127);
     }
+    // sh_rows.h: the window's layout and the copies.  Six dwordx4 loads per lane in flight before the first LDS store
+    // (twelve, as in the forward's colour kernel, cost a wave of occupancy).
     if (RAW) {
-        if (wave_vis && !cached) {
-            const int rl = 3 * (M - 1);
-            const auto* dc = global_ptr(a.in.shs) + 3L * wave_first;
-            const auto* rest = global_ptr(a.shs_rest) + (long)rl * wave_first;
-            if ((nrows & 3) == 0) {   // both spans start 16-byte aligned (wave_first % 64 == 0); full waves: lengths % 4 == 0
-                stage_split_span<ROWS48, true>(dc, 3 * nrows, 3, 0, M, lds, lane);
-                if (M > 1) stage_split_span<ROWS48, true>(rest, rl * nrows, rl, 3, M, lds, lane);
-            } else {
-                stage_split_span<ROWS48, false>(dc, 3 * nrows, 3, 0, M, lds, lane);
-                if (M > 1) stage_split_span<ROWS48, false>(rest, rl * nrows, rl, 3, M, lds, lane);
-            }
-        }
+        if (wave_vis && !cached) stage_split_rows<ROWS48>(global_ptr(a.in.shs), global_ptr(a.shs_rest), wave_first, nrows, M, lds, lane);
     } else if (has_sh && wave_vis && !cached) {
-        const R3_GLOBAL float* src = global_ptr(a.in.shs) + span_first;
-        if (((span_first | span_len) & 3) == 0) {   // 16-B aligned span (always for M = 16): dwordx4 loads, six in
-            const auto* src4 = reinterpret_cast<const R3_GLOBAL float4*>(src);   // flight before the first LDS store (twelve, as in
-            const int n4 = span_len >> 2;                                // the forward's colour kernel, cost a wave of occupancy)
-            constexpr int kBatch = 6;
-            for (int base = 0; base < n4; base += 64 * kBatch) {
-                float4 v[kBatch];
-#pragma unroll
-                for (int k = 0; k < kBatch; k++) {
-                    const int e4 = base + k * 64 + lane;
-                    v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (e4 < n4) v[k] = src4[e4];
-                }
-#pragma unroll
-                for (int k = 0; k < kBatch; k++) {
-                    const int e4 = base + k * 64 + lane;
-                    if (e4 < n4) {
-                        const int e = e4 << 2;
-                        if (ROWS48) {   // 48 % 4 == 0: the four floats are in one row
-                            float* d = lds + bskew<true>(e);
-                            d[0] = v[k].x;
-                            d[1] = v[k].y;
-                            d[2] = v[k].z;
-                            d[3] = v[k].w;
-                        } else {
-                            lds[bskew<false>(e)] = v[k].x;
-                            lds[bskew<false>(e + 1)] = v[k].y;
-                            lds[bskew<false>(e + 2)] = v[k].z;
-                            lds[bskew<false>(e + 3)] = v[k].w;
-                        }
-                    }
-                }
-            }
-        } else {
-            for (int e = lane; e < span_len; e += 64) lds[bskew<ROWS48>(e)] = src[e];
-        }
+        stage_span<6>(global_ptr(a.in.shs), span_first, span_len, ROWS48, lds, lane);
     }
     __syncthreads();
 
@@ -395,7 +251,7 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
     float dscale[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
     float g2x = 0.f, g2y = 0.f, dop = 0.f, dcol[3] = {0.f, 0.f, 0.f}, gcon[3] = {0.f, 0.f, 0.f};
     int K = 0;
-    const ShRowLdsRW<ROWS48> row{ROWS48 ? lds + 49 * lane : lds, ROWS48 ? 0 : lane * 3 * M};
+    const ShRow<ROWS48, float> row = sh_row<ROWS48>(lds, lane, lane * 3 * M);
     if (vis) {
         const float mx = m3[0], my = m3[1], mz = m3[2];
         // 2D-stage gradient row: final in acc[], or in <= tiles/64 + 2 ordered pieces.  A Gaussian whose pairs did not
@@ -484,42 +340,11 @@ __global__ __launch_bounds__(kBwdBlock) void preprocess_bwd_kernel(const PreBwdA
         }
     }
     __syncthreads();
-    if (RAW) {
-        const int rl = 3 * (M - 1);
-        R3_GLOBAL float* dc = global_ptr(a.out.dL_dsh) + 3L * wave_first;
-        R3_GLOBAL float* rest = global_ptr(a.dL_dsh_rest) + (long)rl * wave_first;
-        if ((nrows & 3) == 0) {
-            unstage_split_span<ROWS48, true>(dc, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
-            if (M > 1) unstage_split_span<ROWS48, true>(rest, rl * nrows, rl, 3, M, lds, lane, wave_vis);
-        } else {
-            unstage_split_span<ROWS48, false>(dc, 3 * nrows, 3, 0, M, lds, lane, wave_vis);
-            if (M > 1) unstage_split_span<ROWS48, false>(rest, rl * nrows, rl, 3, M, lds, lane, wave_vis);
-        }
-    } else if (has_sh) {
-        R3_GLOBAL float* dst = global_ptr(a.out.dL_dsh) + span_first;
-        if (((span_first | span_len) & 3) == 0) {   // dwordx4 stores of the gradient rows (or of zeros)
-            auto* dst4 = reinterpret_cast<R3_GLOBAL float4*>(dst);
-            const int n4 = span_len >> 2;
-            if (wave_vis) {
-                for (int e4 = lane; e4 < n4; e4 += 64) {
-                    const int e = e4 << 2;
-                    if (ROWS48) {
-                        const float* q = lds + bskew<true>(e);
-                        dst4[e4] = make_float4(q[0], q[1], q[2], q[3]);
-                    } else {
-                        dst4[e4] = make_float4(lds[bskew<false>(e)], lds[bskew<false>(e + 1)], lds[bskew<false>(e + 2)],
-                                               lds[bskew<false>(e + 3)]);
-                    }
-                }
-            } else {
-                for (int e4 = lane; e4 < n4; e4 += 64) dst4[e4] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        } else if (wave_vis) {
-            for (int e = lane; e < span_len; e += 64) dst[e] = lds[bskew<ROWS48>(e)];
-        } else {
-            for (int e = lane; e < span_len; e += 64) dst[e] = 0.f;
-        }
-    }
+    // the gradient rows (or zeros) leave the way the rows came
+    if (RAW)
+        unstage_split_rows<ROWS48>(global_ptr(a.out.dL_dsh), global_ptr(a.dL_dsh_rest), wave_first, nrows, M, lds, lane, wave_vis);
+    else if (has_sh)
+        unstage_span<ROWS48>(global_ptr(a.out.dL_dsh), span_first, span_len, lds, lane, wave_vis);
     if (valid) {
         R3_GLOBAL float* o;
         o = global_ptr(a.out.dL_dmean2D) + 3 * (size_t)i;

@@ -3,12 +3,11 @@ gradient derived in numpy from tests/quant_ref.np_decode's layout (not from quan
 it, the error bar of "double accumulation, one rounding", and the host-check shim of quant_math.h's quant_grad_slot."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from tests import quant_ref as qr
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_quant_grad", "hostcheck_quant_grad.hip")
@@ -18,12 +17,7 @@ SHAPES = {"dc": (1, 3), "rest": (15, 3), "opacity": (1,), "scaling": (3,), "rota
 
 
 def shim():
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(qr.HDR)):
-        if not os.path.exists(qr.HIPCC):
-            pytest.skip("hipcc not available to build the codebook-gradient host-check shim")
-        subprocess.check_call([qr.HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the codebook-gradient host-check shim")
     lib.hqg_enumerate.restype = C.c_longlong
     return lib
 

@@ -2,17 +2,14 @@
 restatement of the decode written from the format's description (not from quant_math.h), and the host-check shim."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck_quant", "hostcheck_quant.hip")
 SO = os.path.join(HERE, "hostcheck_quant", "libhostcheck_quant.so")
-HDR = os.path.join(ROOT, "reduced-3dgs_amd", "csrc", "quant_math.h")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 # per-degree counts the issue names
 MIXES = [(37, 0, 150, 70), (0, 0, 0, 300), (300, 0, 0, 0), (1, 1, 1, 1), (63, 65, 1, 130), (64, 64, 64, 64)]
@@ -22,12 +19,7 @@ SPECIAL_HALVES = np.array([0x0000, 0x8000, 0x0001, 0x8001, 0x03FF, 0x83FF, 0x040
 
 
 def shim():
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the quantised host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the quantised host-check shim")
     lib.hq_sh_bytes.restype = C.c_longlong
     lib.hq_model_bytes.restype = C.c_longlong
     lib.hq_model_bytes.argtypes = [C.c_longlong, C.c_void_p, C.c_int]

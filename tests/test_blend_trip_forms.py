@@ -6,14 +6,14 @@ explicit fma has to reproduce it.  The sweep contains alpha exactly at 1/255 and
 sums that start at -0.0, and NaN / inf conics.  No GPU needed."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.hostcheck_build import build_shim
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_trip", "hostcheck_trip.hip")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def _cpu_has_fma():
@@ -25,12 +25,7 @@ def _cpu_has_fma():
 
 def _lib(old):
     so = os.path.join(HERE, "hostcheck_trip", f"libtrip_{'old' if old else 'new'}.so")
-    hdr = os.path.join(HERE, "..", "reduced-3dgs_amd", "csrc", "blend_math.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        assert os.path.exists(HIPCC), "hipcc is needed to build the host shim"
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast", "-mfma",
-                               "-o", so, SRC] + (["-DR3_OLD_TRIP_FORMS"] if old else []))
-    return C.CDLL(so)
+    return build_shim(SRC, so, ["-ffp-contract=fast", "-mfma"] + (["-DR3_OLD_TRIP_FORMS"] if old else []), None)
 
 
 def _sweep():

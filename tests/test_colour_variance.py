@@ -83,10 +83,9 @@ def test_oracle_outputs_are_sane():
     assert (d[deg0, 0] > 0).any()
 
 
-@pytest.mark.gpu
-def test_gpu_matches_oracle():
+def check_gpu_against_oracle(a):
+    """`_C.calculate_colours_variance` over the cameras of `a` against the oracle (shared with tests/test_sh_rows_gpu.py)."""
     from diff_gaussian_rasterization import _C
-    a = _scene()
     ref_d, ref_v, ref_m = oracle_ccv(**a)
 
     def dv(x):
@@ -95,7 +94,7 @@ def test_gpu_matches_oracle():
                                             dv(a["scales"]), dv(a["rotations"]), dv(a["cam_viewmatrices"]),
                                             dv(a["cam_projmatrices"]), dv(a["tan_fovxs"]), dv(a["tan_fovys"]),
                                             dv(a["image_height"]), dv(a["image_width"]), dv(a["sh"]),
-                                            dv(a["degrees"]), 3)
+                                            dv(a["degrees"]), a["max_sh_deg"])
     d, v, m = d.cpu().numpy(), v.cpu().numpy(), m.cpu().numpy()
     assert d.shape == ref_d.shape and v.shape == ref_v.shape and m.shape == ref_m.shape
     np.testing.assert_array_equal(np.isnan(d), np.isnan(ref_d))
@@ -129,3 +128,8 @@ def test_gpu_matches_oracle():
     np.testing.assert_allclose(d, ref_d, rtol=2e-3, atol=2e-4, equal_nan=True)
     np.testing.assert_allclose(v, ref_v, rtol=5e-3, atol=1e-5, equal_nan=True)
     np.testing.assert_allclose(m, ref_m, rtol=2e-3, atol=2e-4)
+
+
+@pytest.mark.gpu
+def test_gpu_matches_oracle():
+    check_gpu_against_oracle(_scene())

@@ -6,7 +6,6 @@ restatement's segment order equals a literal cat / mask / cat / mask / mask; the
 take.  No GPU needed."""
 import ctypes as C
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -15,24 +14,17 @@ import torch
 
 import r3dgs_densify as dn
 from tests import densify_ref as ref
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck_densify", "hostcheck_densify.hip")
 SO = os.path.join(HERE, "hostcheck_densify", "libhostcheck_densify.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 CLONE, SPLIT, PRUNED_SELF, PRUNED_CHILD = 1, 2, 4, 8   # csrc/densify_math.h kFlag*
 
 
 def _shim():
-    hdrs = [os.path.join(ROOT, "reduced-3dgs_amd", "csrc", h) for h in ("densify_math.h", "stats_math.h", "param_math.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max([os.path.getmtime(SRC)] + [os.path.getmtime(h) for h in hdrs]):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the densification host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the densification host-check shim")
     lib.hc_densify_flags.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float] + \
         [C.c_void_p] * 6
     return lib

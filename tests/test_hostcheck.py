@@ -4,29 +4,21 @@ transcription errors in the per-lane arithmetic before any GPU time is spent.  T
 parts (LDS staging, DPP reductions, atomics, sorts) are covered by the -m gpu tests only."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import synth_scene as ss
 from oracle import oracle as orc
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck", "hostcheck.hip")
 SO = os.path.join(HERE, "hostcheck", "libhostcheck.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def _lib():
-    hdrs = [os.path.join(HERE, "..", "reduced-3dgs_amd", "csrc", h) for h in ("gauss_math.h", "blend_math.h", "common.h")]
-    newest = max(os.path.getmtime(p) for p in [SRC] + hdrs)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < newest:
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    return C.CDLL(SO)
+    return build_shim(SRC, SO, EXACT, "hipcc not available to build the host-check shim")
 
 
 def p(a):

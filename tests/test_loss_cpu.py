@@ -5,7 +5,6 @@ Python surface has the reference's signatures and refuses what it does not suppo
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,21 +13,15 @@ import torch
 import r3dgs_loss
 from diff_gaussian_rasterization import _C
 from tests import loss_ref
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_loss", "hostcheck_loss.hip")
 SO = os.path.join(HERE, "hostcheck_loss", "libhostcheck_loss.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def _shim():
-    hdr = os.path.join(HERE, "..", "reduced-3dgs_amd", "csrc", "loss_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the loss host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the loss host-check shim")
     lib.hc_ssim_c1.restype = C.c_float
     lib.hc_ssim_c2.restype = C.c_float
     return lib

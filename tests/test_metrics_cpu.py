@@ -7,7 +7,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,23 +14,17 @@ import torch
 
 import r3dgs_metrics
 from tests import metrics_ref
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck_metrics", "hostcheck_metrics.hip")
 SO = os.path.join(HERE, "hostcheck_metrics", "libhostcheck_metrics.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 EPS32 = 2.0 ** -24   # unit roundoff of fp32
 
 
 def _shim():
-    hdr = os.path.join(ROOT, "reduced-3dgs_amd", "csrc", "metrics_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the metrics host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    return C.CDLL(SO)
+    return build_shim(SRC, SO, EXACT, "hipcc not available to build the metrics host-check shim")
 
 
 def _p(a):

@@ -5,7 +5,6 @@ refuses what the kernel does not implement, and its state_dict() loads into torc
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,22 +12,16 @@ import torch
 
 import r3dgs_optim
 from tests import adam_ref
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_optim", "hostcheck_optim.hip")
 SO = os.path.join(HERE, "hostcheck_optim", "libhostcheck_optim.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 
 
 def _shim():
-    hdr = os.path.join(HERE, "..", "reduced-3dgs_amd", "csrc", "adam_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the optimizer host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    return C.CDLL(SO)
+    return build_shim(SRC, SO, EXACT, "hipcc not available to build the optimizer host-check shim")
 
 
 def _p(a):

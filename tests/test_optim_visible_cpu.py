@@ -8,7 +8,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 import zlib
 
 import numpy as np
@@ -18,25 +17,19 @@ import torch
 import r3dgs_optim
 from tests import adam_ref
 from tests.test_optim_cpu import _bits_equal, _inputs
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_optim_rows", "hostcheck_optim_rows.hip")
 SO = os.path.join(HERE, "hostcheck_optim_rows", "libhostcheck_optim_rows.so")
 HEADER = os.path.join(HERE, "..", "include", "r3dgs_optim.h")
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 ROW_LENS = [1, 2, 3, 4, 5, 7, 45, 48]
 CHUNK_UNITS = 1024   # optim.hip: 256 threads x 4 units
 
 
 def _shim():
-    hdr = os.path.join(HERE, "..", "reduced-3dgs_amd", "csrc", "adam_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the gated-step host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the gated-step host-check shim")
     lib.hc_row_divmod.restype = C.c_uint
     lib.hc_row_divmod.argtypes = [C.c_int, C.c_uint, C.POINTER(C.c_uint)]
     lib.hc_chunk_origin.restype = C.c_longlong

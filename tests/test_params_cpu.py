@@ -8,31 +8,25 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from tests.hostcheck_build import EXACT, build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_params", "hostcheck_params.hip")
 SO = os.path.join(HERE, "hostcheck_params", "libhostcheck_params.so")
 HDR = os.path.join(ROOT, "reduced-3dgs_amd", "csrc", "param_math.h")
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 REF = "/root/reference"   # as tests/test_reference_imports.py: only present where the suite is authored
 NEW = ("r3dgs_forward_params", "r3dgs_forward_params_reserved", "r3dgs_backward_params", "r3dgs_activate_params")
 
 
 def shim():
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the parameter host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the parameter host-check shim")
     lib.hc_normalize_eps.restype = C.c_float
     return lib
 

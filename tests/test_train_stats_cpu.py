@@ -7,7 +7,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 import zlib
 
 import numpy as np
@@ -16,23 +15,17 @@ import torch
 
 import r3dgs_train_stats as ts
 from tests import trainstats_ref as ref
+from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck_stats", "hostcheck_stats.hip")
 SO = os.path.join(HERE, "hostcheck_stats", "libhostcheck_stats.so")
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 
 
 def _shim():
-    hdr = os.path.join(ROOT, "reduced-3dgs_amd", "csrc", "stats_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        if not os.path.exists(HIPCC):
-            pytest.skip("hipcc not available to build the statistics host-check shim")
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-o", SO, SRC])
-    lib = C.CDLL(SO)
+    lib = build_shim(SRC, SO, EXACT, "hipcc not available to build the statistics host-check shim")
     lib.hc_alpha_regul_term.argtypes = [C.c_int, C.c_void_p, C.c_float, C.c_void_p]
     return lib
 
