@@ -10,6 +10,7 @@ import pytest
 
 import synth_scene as ss
 from oracle import oracle as orc
+from tests import camera_cases as cc
 from tests.hostcheck_build import EXACT, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,17 +31,24 @@ CASES = [
     dict(P=500, W=70, H=45, f=60.0, cam_seed=2, gseed=1, degree_mode="mixed", lam=0.1, spread=1.0),
     dict(P=400, W=64, H=64, f=50.0, cam_seed=4, gseed=2, degree_mode="all0", lam=0.0, spread=1.35),
     dict(P=500, W=70, H=45, f=60.0, cam_seed=3, gseed=5, degree_mode="mixed", lam=0.0, spread=1.0),
+    # tests/camera_cases.py: portrait, fx != fy, a view rotation far from the identity (W, H and the spread are the entry's)
+    dict(P=500, camera="portrait_far", gseed=6, degree_mode="mixed", lam=0.1),
 ]
 
 
-@pytest.mark.parametrize("kw", CASES, ids=["deg3", "mixed_sparsity", "deg0_clamp", "mixed"])
+@pytest.mark.parametrize("kw", CASES, ids=["deg3", "mixed_sparsity", "deg0_clamp", "mixed", "portrait_far_camera"])
 @pytest.mark.parametrize("precomp", [False, True], ids=["sh_scale_rot", "precomp_colour_cov"])
 def test_device_math_on_host_matches_oracle(kw, precomp):
     L = _lib()
-    W, H, P = kw["W"], kw["H"], kw["P"]
-    cam = ss.make_camera(W, H, kw["f"], kw["cam_seed"])
-    g = ss.make_gaussians(P, cam, seed=kw["gseed"], degree_mode=kw["degree_mode"], scale_mu=0.12, scale_sigma=0.7)
-    g["means3D"][:, :2] *= kw["spread"]
+    P = kw["P"]
+    if "camera" in kw:
+        W, H = cc.CAMERAS[kw["camera"]]["cpu"][:2]
+        cam, g = cc.cloud(kw["camera"], "cpu", P, kw["gseed"], kw["degree_mode"], scale_mu=0.12, scale_sigma=0.7)
+    else:
+        W, H = kw["W"], kw["H"]
+        cam = ss.make_camera(W, H, kw["f"], kw["cam_seed"])
+        g = ss.make_gaussians(P, cam, seed=kw["gseed"], degree_mode=kw["degree_mode"], scale_mu=0.12, scale_sigma=0.7)
+        g["means3D"][:, :2] *= kw["spread"]
     bg = np.array([0.3, 0.5, 0.7], np.float32)
     rng = np.random.default_rng(5)
     colors = cov = None

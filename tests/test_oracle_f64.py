@@ -13,6 +13,7 @@ import torch
 import synth_scene as ss
 from oracle import oracle as orc
 from oracle import torch_ref as tr
+from tests import camera_cases as cc
 
 DT = torch.float64
 
@@ -21,7 +22,9 @@ def T(a):
     return torch.tensor(np.asarray(a), dtype=DT)
 
 
-def scene(P, W, H, f, cam_seed, gseed, degree_mode, scale_mu=0.15, scale_sigma=0.7, spread=1.0):
+def scene(P, W, H, f, cam_seed, gseed, degree_mode, scale_mu=0.15, scale_sigma=0.7, spread=1.0, camera=None):
+    if camera is not None:    # an entry of tests/camera_cases.CAMERAS at its cpu size, with its own spread
+        return cc.cloud(camera, "cpu", P, gseed, degree_mode, scale_mu=scale_mu, scale_sigma=scale_sigma)
     cam = ss.make_camera(W, H, f, cam_seed)
     g = ss.make_gaussians(P, cam, seed=gseed, degree_mode=degree_mode, scale_mu=scale_mu, scale_sigma=scale_sigma)
     g["means3D"][:, :2] *= spread
@@ -50,15 +53,18 @@ def relerr(ref, got):
     dict(P=350, W=56, H=40, f=45.0, cam_seed=7, gseed=8, degree_mode="mixed", bg=(0.5, 0.5, 0.5), lam=0.1),
     dict(P=350, W=56, H=40, f=45.0, cam_seed=8, gseed=9, degree_mode="all3", bg=(0.1, 0.2, 0.3), lam=0.0, spread=1.35),
     dict(P=300, W=48, H=40, f=40.0, cam_seed=2, gseed=3, degree_mode="all3", bg=(0.9, 0.2, 0.3), lam=0.0, mod=1.3),
-], ids=["mixed", "deg3_black_idcam", "sh_sparsity", "ewa_clamp", "scale_modifier"])
+] + [dict(P=400, camera=name, gseed=20 + i, degree_mode="mixed", bg=(0.3, 0.6, 0.1), lam=0.1) for i, name in enumerate(cc.CAMERAS)],
+    ids=["mixed", "deg3_black_idcam", "sh_sparsity", "ewa_clamp", "scale_modifier"] + list(cc.CAMERAS))
 def test_f64_backward_is_the_autograd_gradient(kw):
     """Fed the fp64 forward's own per-Gaussian numbers (means, conic, opacity, colour, covariance), and with the pixels
     whose skip decisions fp32 and fp64 may take differently removed from the upstream gradient, the hand-derived double
     backward must BE the autograd gradient: 1e-10 of each tensor's maximum in its `pure` mode.  With the reference's
     conventions (the default: focal lengths and clamp limits formed in fp32, and backward.cu:234's 1 / (det^2 + 1e-7), which
     is not the derivative of the forward's 1 / det) it stays within 1e-6 of it."""
-    W, H, P, mod = kw["W"], kw["H"], kw["P"], f32(kw.get("mod", 1.0))
-    cam, g = scene(P, W, H, kw["f"], kw["cam_seed"], kw["gseed"], kw["degree_mode"], spread=kw.get("spread", 1.0))
+    P, mod = kw["P"], f32(kw.get("mod", 1.0))
+    W, H = cc.CAMERAS[kw["camera"]]["cpu"][:2] if "camera" in kw else (kw["W"], kw["H"])
+    cam, g = scene(P, W, H, kw.get("f"), kw.get("cam_seed"), kw["gseed"], kw["degree_mode"], spread=kw.get("spread", 1.0),
+                   camera=kw.get("camera"))
     bg = np.array(kw["bg"], np.float32)
     out = oracle_fwd(cam, g, bg, W, H, mod=mod)
     dl = ss.upstream_grad(W, H, seed=kw["gseed"] + 3) * W * H

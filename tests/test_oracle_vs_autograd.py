@@ -10,6 +10,7 @@ import torch
 import synth_scene as ss
 from oracle import oracle as orc
 from oracle import torch_ref as tr
+from tests import camera_cases as cc
 
 DT = torch.float64
 
@@ -18,11 +19,17 @@ def T(a):
     return torch.tensor(np.asarray(a), dtype=DT)
 
 
-def run_case(P, W, H, f, cam_seed, gseed, degree_mode, bg, lam=0.0, precomp_color=False, precomp_cov=False,
-             spread=1.0, dl=None, mod=1.0):
-    cam = ss.make_camera(W, H, f, cam_seed)
-    g = ss.make_gaussians(P, cam, seed=gseed, degree_mode=degree_mode, scale_mu=0.15, scale_sigma=0.7)
-    g["means3D"][:, :2] *= spread  # >1 pushes Gaussians beyond 1.3*tanfov => exercises the EWA clamp
+def run_case(P, W=None, H=None, f=None, cam_seed=None, gseed=0, degree_mode="mixed", bg=(0, 0, 0), lam=0.0,
+             precomp_color=False, precomp_cov=False, spread=1.0, dl=None, mod=1.0, camera=None):
+    """camera: the name of an entry of tests/camera_cases.CAMERAS (its cpu size, rotation, translation and spread) instead
+    of synth_scene.make_camera(W, H, f, cam_seed)."""
+    if camera is not None:
+        W, H = cc.CAMERAS[camera]["cpu"][:2]
+        cam, g = cc.cloud(camera, "cpu", P, gseed, degree_mode, scale_mu=0.15, scale_sigma=0.7)
+    else:
+        cam = ss.make_camera(W, H, f, cam_seed)
+        g = ss.make_gaussians(P, cam, seed=gseed, degree_mode=degree_mode, scale_mu=0.15, scale_sigma=0.7)
+        g["means3D"][:, :2] *= spread  # >1 pushes Gaussians beyond 1.3*tanfov => exercises the EWA clamp
     bg = np.array(bg, np.float32)
     colors = cov = None
     rng = np.random.default_rng(gseed + 77)
@@ -73,7 +80,8 @@ def close(name, ref, got, rel=3e-4):
     dict(P=300, W=33, H=47, f=40.0, cam_seed=6, gseed=2, degree_mode="all0", bg=(1, 1, 1)),
     dict(P=350, W=56, H=40, f=45.0, cam_seed=7, gseed=8, degree_mode="mixed", bg=(0.5, 0.5, 0.5), lam=0.1),
     dict(P=350, W=56, H=40, f=45.0, cam_seed=8, gseed=9, degree_mode="all3", bg=(0.1, 0.2, 0.3), spread=1.35),
-], ids=["mixed", "deg3_black_idcam", "deg0_white_ragged_edges", "sh_sparsity", "ewa_clamp"])
+] + [dict(P=400, camera=name, gseed=20 + i, degree_mode="mixed", bg=(0.3, 0.6, 0.1), lam=0.1) for i, name in enumerate(cc.CAMERAS)],
+    ids=["mixed", "deg3_black_idcam", "deg0_white_ragged_edges", "sh_sparsity", "ewa_clamp"] + list(cc.CAMERAS))
 def test_forward_and_backward_match_autograd(kw):
     out, col, radii, lv, gr = run_case(**kw)
     np.testing.assert_array_equal(out["radii"], radii)
@@ -91,6 +99,41 @@ def test_forward_and_backward_match_autograd(kw):
     inv = out["radii"] == 0
     for k in ("dL_dmeans3D", "dL_dsh", "dL_dscales", "dL_drotations", "dL_dopacity", "dL_dmeans2D"):
         assert (gr[k][inv] == 0).all()
+
+
+def test_camera_table_and_swapped_fov_sensitivity():
+    """tests/camera_cases.CAMERAS keeps what it promises (|fx / fy - 1| >= 0.2 at both sizes, a portrait entry, rotations
+    far from the identity), and a cloud drawn for such a camera notices an exchange of x and y: handed tanfovx and tanfovy
+    exchanged, the oracle gives another radius to at least 10 % of the visible Gaussians of the non-square case."""
+    for name, c in cc.CAMERAS.items():
+        for size in ("cpu", "gpu"):
+            W, H, fx, fy = c[size]
+            assert abs(fx / fy - 1.0) >= 0.2, (name, size)
+            cam = cc.camera(name, size)
+            assert abs(cam.tanfovx - W / (2 * fx)) < 1e-12 and abs(cam.tanfovy - H / (2 * fy)) < 1e-12
+        W, H = c["gpu"][:2]
+        assert max(W, H) <= 203 and min(W, H) <= 117 and W % 16 and H % 16 and min(W, H) >= 4 * 16
+    assert any(c["gpu"][0] < c["gpu"][1] and c["cpu"][0] < c["cpu"][1] for c in cc.CAMERAS.values())
+    assert sum(np.abs(cc.camera(n, "cpu").world_view_transform[:3, :3] - np.eye(3)).max() > 0.9 for n in cc.CAMERAS) >= 3
+    assert max(np.linalg.norm(cc.camera(n, "cpu").camera_center) for n in cc.CAMERAS) > 5.0
+    # place_in_view: the camera sees the cloud where the identity camera with its intrinsics did
+    W, H = cc.CAMERAS["portrait_far"]["cpu"][:2]
+    g0 = ss.make_gaussians(400, cc.identity_camera("portrait_far", "cpu"), seed=3, degree_mode="mixed", scale_mu=0.15)
+    cam = cc.camera("portrait_far", "cpu")
+    g1 = cc.place_in_view(g0, cam)
+    np.testing.assert_array_equal(g1["rotations"], g0["rotations"])
+    np.testing.assert_allclose(cc.view_space(g1, cam), g0["means3D"], atol=2e-6)
+    # the sensitivity of the non-square case
+    cam, g = cc.cloud("aniso", "cpu", 400, 20, "mixed", scale_mu=0.15, scale_sigma=0.7)
+    W, H = cc.CAMERAS["aniso"]["cpu"][:2]
+    fwd = lambda tx, ty: orc.forward(np.zeros(3, np.float32), g["means3D"], None, g["opacity"], g["scales"], g["rotations"],
+                                     1.0, None, cam.world_view_transform, cam.full_proj_transform, tx, ty, H, W, g["sh"],
+                                     g["degrees"], cam.camera_center, geometry_only=True)
+    right, swapped = fwd(cam.tanfovx, cam.tanfovy), fwd(cam.tanfovy, cam.tanfovx)
+    vis = right["radii"] > 0
+    assert vis.sum() > 300
+    changed = (right["radii"] != swapped["radii"])[vis].mean()
+    assert changed >= 0.10, f"only {changed:.3f} of the visible Gaussians notice tanfovx <-> tanfovy"
 
 
 def test_precomputed_colour_and_covariance_paths():
