@@ -37,6 +37,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     # max-ilp scheduling: blend_bwd 0.497 -> 0.484 ms, blend_fwd 0.179 -> 0.176 (max-memory-clause: no change; -O2: worse;
     # with SLP vectorisation: 0.76 / 0.20)
     "blend.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # the backward blend's unit order (split out of blend.hip): compiled as it was there
+    "unit_order.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's

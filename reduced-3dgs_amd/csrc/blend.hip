@@ -34,6 +34,7 @@
 
 #include "blend_math.h"
 #include "common.h"
+#include "unit_order.h"
 
 namespace r3 {
 
@@ -481,7 +482,7 @@ constexpr int kGradStride = 9;   // the 9 sums of a list entry (odd stride: the 
 // [lo, hi) starts as ever, one that ends in front of lo has nothing to do here.  Every list entry belongs to exactly one
 // segment, so every row of the per-pair slab still has ONE writer: no atomics, bit-reproducible.
 // FIRST: this is the first kernel of the backward (no unit order): it installs the pass block for the kernels behind it and
-// reads its own arguments from the kernarg segment; otherwise unit_order_kernel did and the arguments come from the block
+// reads its own arguments from the kernarg segment; otherwise unit_order_kernel (unit_order.hip) did and the arguments come from the block
 // (a graph replay refreshes the by-value arguments of its first node only).
 template <int PPL, bool REUSE, bool FIRST>
 __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdPassArgs v)
@@ -498,16 +499,17 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
     constexpr int PARTS = 4 / PPL;
     const int lane = threadIdx.x;
     uint32_t wg, seg = 0u, nseg = 1u, walk_log2 = 0u;
-    if (a.tile_order) {
+    if (a.unit_order) {
         // entry b / lists of list b % lists (each list is heaviest first; the grid covers the most units a pass may have)
-        const uint32_t g = blockIdx.x % kOrderLists, i = blockIdx.x / kOrderLists, per_list = a.units_cap / kOrderLists;
-        const uint32_t* trailer = a.tile_order + a.units_cap + 2u * g;
+        const uint32_t g = blockIdx.x % kOrderLists, i = blockIdx.x / kOrderLists;
+        const uint32_t* trailer = unit_trailer_at(a.unit_order, a.units_cap, g);
         if (i >= trailer[0]) return;
         walk_log2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)trailer[1]);   // segment length this list's units walk
-        const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tile_order[g * per_list + i]);
-        wg = u & ((1u << kUnitTileBits) - 1u);
-        seg = (u >> kUnitTileBits) & 63u;
-        nseg = u >> (kUnitTileBits + 6u);
+        const Unit u = unit_unpack(
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)a.unit_order[unit_list_base(a.units_cap, g) + i]));
+        wg = u.tile;
+        seg = u.segment;
+        nseg = u.segments;
     } else {
         wg = xcd_remap(blockIdx.x, a.nblocks);
     }
@@ -724,306 +726,16 @@ extern "C" int r3dgs_debug_timeline(unsigned long long* host, int n)
 }
 #endif
 
-// Launch order of the backward blend's units: heaviest first.  All units are resident at once for the first half of the
-// kernel and each wave's duration is set by how many share its SIMD, so in row-major order the chip drains for the whole
-// second half (profiles/r03_bwd_timeline_row_major.txt: 20 resident waves per CU for five tenths of a CU's span, then 17, 12, 9, 6,
-// 3); started by decreasing weight, the long walks are under way when the short ones fill the gaps (0.367 -> 0.313 ms on
-// the metric shape).  A unit is a tile, or one segment of a tile whose list is long and deep (common.h):
-// on a scene with the load of a real capture the heaviest tile walks three times the mean and the kernel was as long as
-// that walk.  Weight of a unit = sum over the four quadrants of the entries it will visit there (ImageState::quad_depth
-// clamped to the segment).  Tiles nothing contributed to are left out.  Counting sort over 1024 weight classes (64
-// classes: +2 us for the stage, 16: +10, 4: +22), one workgroup per unit list (below); the order inside a class is whatever
-// the LDS atomics make it -- every unit's arithmetic is its own, so the gradients do not depend on the order
-// (tests/test_gpu_parity.py compares the two orders bit for bit).  The hardware deals consecutive workgroups over the eight
-// XCDs: as ONE sorted list every XCD got every eighth unit -- equal work per XCD, and every XCD's L2 saw every Gaussian's
-// record (FETCH_SIZE 62 -> 150 MB); keeping each XCD on a BAND of the image and ordering inside the band only (74 MB)
-// measured 0.315 ms against 0.305 ms for the stage.  The eight lists of 4 x 4 tile blocks (common.h TileGrid) are the
-// middle: each XCD walks blocks from all over the image, heaviest first, and neighbouring tiles stay on one XCD.
-constexpr int kOrderThreads = 1024, kOrderClasses = 1024;
-
-// segments of 2^walk entries the backward walks a tile in: 1 unless the forward left checkpoints for it (list length)
-// and it is deeper than one segment
-__device__ __forceinline__ uint32_t unit_segments(uint32_t list_len, uint32_t deepest, uint32_t thr, uint32_t walk)
-{
-    if (list_len < thr || deepest <= (1u << walk)) return 1u;
-    return min((deepest + (1u << walk) - 1u) >> walk, (uint32_t)kBwdSegMax);
-}
-// entries segment `s` of `n` visits in the four quadrants whose deepest contributors are d
-__device__ __forceinline__ uint32_t unit_weight(const uint4& d, uint32_t s, uint32_t n, uint32_t walk)
-{
-    if (n == 1u) return d.x + d.y + d.z + d.w;
-    const uint32_t lo = s << walk, hi = s + 1u < n ? lo + (1u << walk) : 0xFFFFFFFFu;
-    auto part = [&](uint32_t q) { return min(max(q, lo), hi) - lo; };
-    return part(d.x) + part(d.y) + part(d.z) + part(d.w);
-}
-
-// KEEP: tiles a thread holds in registers between the passes.  Since the order became kOrderLists lists a thread of the metric
-// shape holds ONE tile (864 slots per list), and every further slot still issued its (clamped) loads and its unrolled counting
-// code: 12.7 us with eight slots, 7.5 with two (profiles/r05_exp_unit_order.txt); the launch takes the smallest that covers
-// the image's longest list (1: <= 1024 slots per list, i.e. up to ~8 k tiles; 2; 8: up to 64 k tiles, beyond that the
-// passes re-read).
-template <int KEEP>
-__global__ __launch_bounds__(kOrderThreads) void unit_order_kernel(BwdPassArgs* dst, BwdPassArgs v)
-{
-    __shared__ uint32_t s_count[kOrderClasses];
-    __shared__ uint32_t s_scan[kOrderThreads / 64];
-    constexpr int kWalks = 4;   // segment lengths a pass may walk: S, 2 S, 4 S, 8 S (the first whose units fit the launch)
-    __shared__ uint32_t s_max;
-    const uint32_t tid = threadIdx.x, lane_id = tid & 63u;
-    if (blockIdx.x == 0) install_block_from_kernarg(dst, (int)tid, kOrderThreads);   // first kernel of the backward: the pass block
-    // One workgroup per LIST: workgroup g orders the tiles of list g (common.h TileGrid: the 4 x 4 tile blocks g, g + lists, ...
-    // of the image) with its own class counters, no word exchanged with the others; the blend kernel's workgroup b takes entry
-    // b / lists of list b % lists, so the lists are consumed side by side and the launch order is the interleaving of eight
-    // orders of statistically alike tile sets.
-    // (As ONE workgroup over all tiles the kernel was bound by the vector issue of the one compute unit it ran on: 18 us.)
-    const uint32_t list = blockIdx.x, all_tiles = v.blend.nblocks;
-    const TileGrid grid{(uint32_t)v.blend.gx, all_tiles / (uint32_t)v.blend.gx};
-    const uint4* __restrict__ qd = reinterpret_cast<const uint4*>(v.blend.quad_depth);
-    const uint2* __restrict__ ranges = v.blend.ranges;
-    const uint32_t cap = v.blend.units_cap / kOrderLists;                 // slots of this list
-    uint32_t* __restrict__ order = v.blend.tile_order + list * cap;
-    uint32_t* __restrict__ trailer = v.blend.tile_order + v.blend.units_cap + 2u * list;
-    const uint32_t n_tiles = grid.list_slots(list);   // slots of this list; a slot of a block at the image's edge may hold no tile
-    auto tile_of = [&](uint32_t j) { return grid.list_tile(list, j); };   // slot -> tile (~0: none)
-    const uint32_t seg_log2 = (v.blend.segments != 0 && v.blend.ckpt != nullptr && all_tiles <= (1u << kUnitTileBits))
-                                  ? v.blend.hdr->ckpt : 0u;   // 0: the forward left no checkpoints / segments are off
-    const uint32_t thr = seg_log2 ? v.blend.hdr->ckpt_thr : 0xFFFFFFFFu;
-    // Units a list may hold.  The bound is taken from the pass's pair count, not from the capacity its binning blob happens
-    // to have: the exact-size path and the reserved path of one view then walk the same segments and give the same bits.
-    const uint32_t fit = bwd_list_fit(v.blend.hdr->num_pairs, grid);   // <= cap: the reservation holds the pairs
-    s_count[tid] = 0u;
-    if (tid == 0) s_max = 0u;
-    __syncthreads();
-    // up to KEEP tiles per thread stay in registers between the passes (one memory round trip instead of four: the
-    // kernel is a chain of latencies, 9.5 us when every pass went back to memory); a larger grid re-reads
-    const bool keep = n_tiles <= (uint32_t)(KEEP * kOrderThreads);
-    uint4 w[KEEP];
-    uint32_t len[KEEP], tl[KEEP];   // weights, list length and tile of the kept slots
-    auto load = [&](uint32_t t, uint4& d, uint32_t& l) {
-        d = make_uint4(0u, 0u, 0u, 0u);
-        l = 0u;
-        const uint32_t tile = t < n_tiles ? tile_of(t) : 0xFFFFFFFFu;
-        if (tile != 0xFFFFFFFFu) {
-            d = qd[tile];
-            const uint2 r = ranges[tile];
-            l = r.y - r.x;
-        }
-    };
-    if (keep) {
-        // every load in flight before the first use (written as `load` per tile the compiler reused one register pair for the
-        // ranges and waited for each of the loads in turn: 12 us of the kernel's 22)
-        uint2 rr[KEEP];
-#pragma unroll
-        for (int k = 0; k < KEEP; k++) {
-            const uint32_t j = tid + (uint32_t)(k * kOrderThreads);
-            tl[k] = j < n_tiles ? tile_of(j) : 0xFFFFFFFFu;
-            w[k] = qd[min(tl[k], all_tiles - 1u)];
-            rr[k] = ranges[min(tl[k], all_tiles - 1u)];
-        }
-#pragma unroll
-        for (int k = 0; k < KEEP; k++) {
-            const bool in = tl[k] != 0xFFFFFFFFu;
-            if (!in) w[k] = make_uint4(0u, 0u, 0u, 0u);
-            len[k] = in ? rr[k].y - rr[k].x : 0u;
-        }
-    }
-    auto wave_prefix = [&](uint32_t x, uint32_t* total) {   // exclusive prefix and total of x over the wave
-        uint32_t incl = x;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
-            if (lane_id >= (uint32_t)off) incl += up;
-        }
-        *total = (uint32_t)__shfl((int)incl, 63);
-        return incl - x;
-    };
-    // (the kernel runs on ONE compute unit per list and is bound by its vector-instruction issue -- integer min / max at half
-    // rate -- so nothing is worked out twice: segment counts and the classes of a tile's first three partial segments wait in
-    // registers for the placement pass)
-    constexpr uint32_t kCached = 3u;
-    uint32_t nf[KEEP], pc[KEEP];   // segments | full segments << 8, and the cached classes, of the kept tiles
-    // The segment length is settled by TRYING: the counting pass runs with the shortest segments (2^seg_log2 entries) and its
-    // class scan says how many units that makes; only a pass whose lists are so long that they exceed what the list may
-    // launch (tens of millions of pairs: fit = tiles + min(pairs / S, 8 tiles) / lists) counts again with 2 S, 4 S, 8 S and
-    // finally whole tiles.  (Round 5 counted the units of all four candidate lengths in a pass of their own before the
-    // counting pass, on every backward: 1.3 of the kernel's 12.7 us)
-    uint32_t walk = seg_log2, total_units = 0u, full_class = 0u;
-    float scale = 0.f;
-    for (;;) {
-        // The heaviest unit.  A pass that splits knows a bound without looking: a whole tile is shorter than `thr` entries (or it
-        // would be split) and no deeper than its list, a segment weighs at most 4 x its length -- only the last segment of a tile
-        // capped at kBwdSegMax can be heavier, and lands in the heaviest class.  Without segments: one more pass over the tiles.
-        uint32_t heaviest;
-        if (walk) {
-            heaviest = max(4u << walk, 4u * min(thr, 1u << 20));
-        } else {
-            uint32_t kmax = 0u;
-            if (keep) {
-#pragma unroll
-                for (int k = 0; k < KEEP; k++) kmax = max(kmax, w[k].x + w[k].y + w[k].z + w[k].w);
-            } else {
-                for (uint32_t t = tid; t < n_tiles; t += kOrderThreads) {
-                    uint4 d;
-                    uint32_t l;
-                    load(t, d, l);
-                    kmax = max(kmax, d.x + d.y + d.z + d.w);
-                }
-            }
-            for (int off = 32; off > 0; off >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off));
-            if (lane_id == 0u) atomicMax(&s_max, kmax);
-            __syncthreads();
-            heaviest = s_max;
-        }
-        scale = (float)(kOrderClasses - 1) / (float)max(heaviest, 1u);
-        // class 0 = the heaviest
-        auto klass = [&](uint32_t wt) {
-            return (uint32_t)(kOrderClasses - 1) - min((uint32_t)((float)wt * scale), (uint32_t)(kOrderClasses - 1));
-        };
-        full_class = klass(4u << walk);
-        auto segs = [&](const uint4& d, uint32_t l) -> uint32_t {
-            if (d.x + d.y + d.z + d.w == 0u) return 0u;   // nothing contributed to this tile: no unit
-            return walk ? unit_segments(l, max(max(d.x, d.y), max(d.z, d.w)), thr, walk) : 1u;
-        };
-        // Leading segments of a split tile that all four quadrants walk in full: they all weigh 4 x the segment length -- one
-        // class, thousands of units in a deep scene, and one LDS counter they would all queue on (the kernel took 52 us at
-        // 2 M Gaussians that way).  A tile's FULL segments are therefore counted and placed as a group, and the groups of the
-        // tiles a wave holds at the same step add up among themselves (a shuffle scan): one atomic per wave and step.
-        auto full_segments = [&](const uint4& d, uint32_t n) -> uint32_t {
-            if (n <= 1u) return 0u;
-            const uint32_t f = min(min(d.x, d.y), min(d.z, d.w)) >> walk;
-            return min(f, n == (uint32_t)kBwdSegMax ? n - 1u : n);   // (a capped tile's last segment takes the rest: not "full")
-        };
-        // (a) the partial units of a tile: one LDS atomic each; (b) its full segments: the lanes of a wave add theirs up (one
-        // shuffle scan per pass over the sum of a thread's tiles) and send one atomic.
-        auto count_partials = [&](const uint4& d, uint32_t n, uint32_t f, uint32_t* classes) {
-            uint32_t packed = 0u;
-            for (uint32_t k = f; k < n; k++) {
-                const uint32_t c = klass(unit_weight(d, k, n, walk));
-                atomicAdd(&s_count[c], 1u);
-                if (k - f < kCached) packed |= c << (10u * (k - f));
-            }
-            *classes = packed;
-        };
-        if (keep) {
-            uint32_t fsum = 0u, total;
-#pragma unroll
-            for (int k = 0; k < KEEP; k++) {
-                const uint32_t n = segs(w[k], len[k]), f = full_segments(w[k], n);
-                nf[k] = n | (f << 8);
-                fsum += f;
-                count_partials(w[k], n, f, &pc[k]);
-            }
-            wave_prefix(fsum, &total);
-            if (lane_id == 0u && total) atomicAdd(&s_count[full_class], total);
-        } else {
-            for (uint32_t t0 = 0; t0 < n_tiles; t0 += kOrderThreads) {   // uniform trip count: the wave scan needs every lane
-                uint4 d;
-                uint32_t l, unused, total;
-                load(t0 + tid, d, l);
-                const uint32_t n = segs(d, l), f = full_segments(d, n);
-                count_partials(d, n, f, &unused);
-                wave_prefix(f, &total);
-                if (lane_id == 0u && total) atomicAdd(&s_count[full_class], total);
-            }
-        }
-        __syncthreads();
-        // exclusive scan of the class counts (one class per thread)
-        const uint32_t mine = s_count[tid];
-        uint32_t incl = mine;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
-            if (lane_id >= (uint32_t)off) incl += up;
-        }
-        if (lane_id == 63u) s_scan[tid >> 6] = incl;
-        __syncthreads();
-        uint32_t before = 0u;
-        total_units = 0u;
-        for (uint32_t k = 0; k < (uint32_t)(kOrderThreads / 64); k++) {
-            const uint32_t c = s_scan[k];
-            if (k < (tid >> 6)) before += c;
-            total_units += c;
-        }
-        __syncthreads();
-        const bool fits = walk == 0u || total_units <= fit;   // the same for every thread
-        s_count[tid] = fits ? before + incl - mine : 0u;       // first slot of the class, then its cursor / cleared for the retry
-        if (tid == 0) s_max = 0u;
-        __syncthreads();
-        if (fits) break;
-        walk = walk + 1u < seg_log2 + (uint32_t)kWalks ? walk + 1u : 0u;   // longer segments; none fits: whole tiles
-    }
-    if (tid == 0) {
-        trailer[0] = total_units;   // the units of this list (<= cap by the choice of `walk`; whole tiles: <= list_tiles_max)
-        trailer[1] = walk;          // log2 of the segment length they walk (0: whole tiles)
-    }
-    auto klass = [&](uint32_t wt) {
-        return (uint32_t)(kOrderClasses - 1) - min((uint32_t)((float)wt * scale), (uint32_t)(kOrderClasses - 1));
-    };
-    auto place = [&](uint32_t tile, const uint4& d, uint32_t n, uint32_t f, uint32_t base, uint32_t classes, bool cached) {
-        const uint32_t word = tile | (n << (kUnitTileBits + 6u));
-        for (uint32_t k = 0; k < f; k++) order[base + k] = word | (k << kUnitTileBits);
-        for (uint32_t k = f; k < n; k++) {
-            const uint32_t c = (cached && k - f < kCached) ? (classes >> (10u * (k - f))) & 1023u
-                                                           : klass(unit_weight(d, k, n, walk));
-            order[atomicAdd(&s_count[c], 1u)] = word | (k << kUnitTileBits);
-        }
-    };
-    auto full_base = [&](uint32_t f) {   // where this lane's full segments go: one atomic per wave
-        uint32_t total;
-        const uint32_t ahead = wave_prefix(f, &total);
-        uint32_t base = 0u;
-        if (lane_id == 0u && total) base = atomicAdd(&s_count[full_class], total);
-        return (uint32_t)__shfl((int)base, 0) + ahead;
-    };
-    if (keep) {
-        uint32_t fsum = 0u;
-#pragma unroll
-        for (int k = 0; k < KEEP; k++) fsum += nf[k] >> 8;
-        uint32_t base = full_base(fsum);
-#pragma unroll
-        for (int k = 0; k < KEEP; k++) {
-            place(tl[k], w[k], nf[k] & 255u, nf[k] >> 8, base, pc[k], true);
-            base += nf[k] >> 8;
-        }
-    } else {
-        for (uint32_t t0 = 0; t0 < n_tiles; t0 += kOrderThreads) {
-            uint4 d;
-            uint32_t l;
-            load(t0 + tid, d, l);
-            const uint32_t n = d.x + d.y + d.z + d.w == 0u ? 0u
-                               : (walk ? unit_segments(l, max(max(d.x, d.y), max(d.z, d.w)), thr, walk) : 1u);
-            uint32_t f = 0u;
-            if (n > 1u) {
-                f = min(min(d.x, d.y), min(d.z, d.w)) >> walk;
-                f = min(f, n == (uint32_t)kBwdSegMax ? n - 1u : n);
-            }
-            place(t0 + tid < n_tiles ? tile_of(t0 + tid) : 0u, d, n, f, full_base(f), 0u, false);
-        }
-    }
-}
-
 template <bool REUSE>
 static void launch_bwd(uint32_t nblocks, uint32_t units_cap, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s)
 {
-    if (v.blend.tile_order) {
+    if (v.blend.unit_order) {
         static const int lds_pad = env_int("R3DGS_BWD_LDS_PAD", 0, 0, 65536);
         // one workgroup per unit the pass MAY have (those beyond its count leave at once)
         hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, false>), dim3(units_cap), dim3(64), lds_pad, s, dst, v);
     } else {
         hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, true>), dim3(nblocks), dim3(64), 0, s, dst, v);
     }
-}
-
-// the launch order of the backward blend's units (and the pass block: this is then the first kernel of the backward)
-void issue_unit_order(const BwdPlan& p, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s)
-{
-    if (!v.blend.tile_order) return;
-    // slots of the longest list decide how many tiles a thread of the order kernel keeps in registers
-    const uint32_t slots = TileGrid{(uint32_t)p.gx, (uint32_t)p.gy}.list_slots(0);
-    if (slots <= (uint32_t)kOrderThreads)
-        hipLaunchKernelGGL(unit_order_kernel<1>, dim3(kOrderLists), dim3(kOrderThreads), 0, s, dst, v);
-    else if (slots <= 2u * (uint32_t)kOrderThreads)
-        hipLaunchKernelGGL(unit_order_kernel<2>, dim3(kOrderLists), dim3(kOrderThreads), 0, s, dst, v);
-    else
-        hipLaunchKernelGGL(unit_order_kernel<8>, dim3(kOrderLists), dim3(kOrderThreads), 0, s, dst, v);
 }
 
 void issue_blend_backward(const BwdPlan& p, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s)

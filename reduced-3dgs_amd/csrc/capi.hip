@@ -40,6 +40,7 @@
 
 #include "common.h"
 #include "quant_math.h"
+#include "unit_order.h"
 
 namespace r3 {
 int env_int(const char* env, int dflt, int lo, int hi)
@@ -106,7 +107,7 @@ struct Toggle {
 Toggle g_tight_rects{"R3DGS_TIGHT_RECT"};
 int tight_rects() { return g_tight_rects.get(); }
 
-// The backward blend starts its tiles heaviest first (blend.hip unit_order_kernel); R3DGS_TILE_ORDER=0 /
+// The backward blend starts its tiles heaviest first (unit_order.hip); R3DGS_TILE_ORDER=0 /
 // r3dgs_set_tile_order(0): row-major bands, one per XCD, as the forward (A/B runs, the bit-identity test).
 Toggle g_tile_order{"R3DGS_TILE_ORDER"};
 int heaviest_tiles_first() { return g_tile_order.get(); }
@@ -1339,7 +1340,7 @@ static int backward_any(int P, const int* D, int M, int R, const float* backgrou
         bb.quad_masks = binning_buffer && keep_quad_masks() ? bin.quad_masks : nullptr;
         // the unit order lives in the binning blob: a pass without one (no pair was reserved) has nothing to order; a unit
         // word holds kUnitTileBits of tile index (an image of more than 2^20 tiles -- 268 Mpix -- is walked row-major)
-        bb.tile_order = (heaviest_tiles_first() && plan.has_pairs && (size_t)plan.gx * plan.gy <= ((size_t)1 << kUnitTileBits))
+        bb.unit_order = (heaviest_tiles_first() && plan.has_pairs && (size_t)plan.gx * plan.gy <= ((size_t)1 << kUnitTileBits))
                             ? bin.unit_order : nullptr;
         bb.units_cap = plan.units_cap;
         bb.quad_depth = img.quad_depth;
@@ -1427,7 +1428,7 @@ static int backward_any(int P, const int* D, int M, int R, const float* backgrou
             issue_backward(plan, d_args, a, s, hooks);
         } else {
             const uint32_t flags = (uint32_t)plan.bwd_ppl | ((uint32_t)plan.has_pairs << 3) | ((uint32_t)plan.layout.wide << 4) |
-                                   ((uint32_t)(a.blend.tile_order != nullptr) << 6) |   // one more kernel in the chain
+                                   ((uint32_t)(a.blend.unit_order != nullptr) << 6) |   // one more kernel in the chain
                                    ((uint32_t)plan.f64_chain << 7) | ((uint32_t)plan.raw_params << 8);
             const CtxKey key{dev, 1, s, P, M, width, height, plan.reserve, flags};
             launch_graph(key, plan, a, s, [](const BwdPlan& p, BwdPassArgs* d, const BwdPassArgs& v, hipStream_t cs) {
@@ -1756,7 +1757,7 @@ int r3dgs_export_tile_order(int P, int R, int width, int height, char* binning_b
         if (unit_order) {
             if (!binning_buffer || R <= 0) throw Error("the unit order lives in the binning buffer");
             BinState bin = BinState::carve(binning_buffer, (size_t)R, pair_layout(P, Tn).wide, TileGrid{(uint32_t)gx, (uint32_t)gy});
-            R3_HIP(hipMemcpyAsync(unit_order, bin.unit_order, sizeof(uint32_t) * ((size_t)bwd_units_cap((uint32_t)R, TileGrid{(uint32_t)gx, (uint32_t)gy}) + 2 * kOrderLists),
+            R3_HIP(hipMemcpyAsync(unit_order, bin.unit_order, sizeof(uint32_t) * unit_order_words(bwd_units_cap((uint32_t)R, TileGrid{(uint32_t)gx, (uint32_t)gy})),
                                   hipMemcpyDeviceToDevice, s));
         }
         check_launch("export", s, false);

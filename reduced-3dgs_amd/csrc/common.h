@@ -270,7 +270,7 @@ constexpr int kBwdSegMinLog2 = 7;      // smallest segment: 128 entries (two 64-
 constexpr int kBwdSegMaxLog2 = 8;
 constexpr int kBwdSegMax = 32;         // segments per tile at most: the last one takes whatever is left
 constexpr int kFwdCkptMax = 256;       // checkpoints per tile at most (a pass may walk segments of up to 8 S: 31 x 8 < 256)
-constexpr uint32_t kUnitTileBits = 20; // a unit word of the backward's launch order: tile | segment << 20 | segments << 26
+constexpr uint32_t kUnitTileBits = 20; // tile bits of a unit word of the backward's launch order (unit_order.h)
 R3_HD size_t ckpt_slot(uint32_t first, uint32_t k, uint32_t tile, uint32_t seg_log2) { return (size_t)(first >> seg_log2) + tile + k; }
 inline size_t ckpt_slots(size_t R, size_t Tn) { return (R >> kBwdSegMinLog2) + Tn + 2; }
 // The unit order of the backward blend is kept as kOrderLists lists, each made by a workgroup of its own; workgroup b of the
@@ -312,6 +312,9 @@ R3_HD uint32_t bwd_list_fit(uint32_t pairs, const TileGrid& g)   // units a list
     return g.list_tiles_max() + (uint32_t)((extra < most ? extra : most) / kOrderLists);
 }
 inline uint32_t bwd_units_cap(uint32_t reserve, const TileGrid& g) { return (bwd_list_fit(reserve, g) + 1u) * kOrderLists; }
+// words of the order array: the lists' slots, then per list a trailer of two words (addressed by unit_order.h)
+constexpr uint32_t kUnitTrailerWords = 2;
+R3_HD uint32_t unit_order_words(uint32_t units_cap) { return units_cap + kUnitTrailerWords * kOrderLists; }
 int bwd_segment_log2();         // R3DGS_BWD_SEG_LEN = 128 (default) | 256 -> 7 | 8; capi.hip
 int bwd_segment_factor_pct();   // R3DGS_BWD_SEG_FACTOR: lists >= this percentage of the pass's mean length are split (75)
 
@@ -333,10 +336,9 @@ struct BinState {
     unsigned long long* quad_masks;  // [R/64 + Tn + 2][4] region pre-test of the forward blend, kept for the backward:
                                      // bit j of [slot][q] = entry j of a 64-entry chunk of a tile's list may reach 8x8
                                      // quadrant q; slot = quad_mask_slot(first pair of the tile, chunk, tile)
-    uint32_t* unit_order;            // [bwd_units_cap + 2 * kOrderLists] launch order of the backward blend's (tile, segment)
-                                     // units: kOrderLists lists of cap / kOrderLists slots, each heaviest first; behind
-                                     // them per list how many units it has and log2 of the segment length they walk
-                                     // (blend.hip unit_order_kernel)
+    uint32_t* unit_order;            // [unit_order_words(bwd_units_cap)] launch order of the backward blend's (tile, segment)
+                                     // units: kOrderLists lists, each heaviest first, and their trailers (unit_order.h;
+                                     // written by unit_order.hip)
     float4* ckpt;                    // [ckpt_slots][256] forward checkpoints of the segmented tiles: (T, C0, C1, C2) per pixel
     char* end;
     static BinState carve(char* base, size_t R, int wide, const TileGrid& grid)
@@ -369,7 +371,7 @@ struct BinState {
         b.radix_total = c.take<uint32_t>(kMaxRadixPasses * kMaxRadixBins);
         b.quad_masks = c.take<unsigned long long>((R / 64 + Tn + 2) * 4);
         b.block_first = c.take<uint32_t>(R / kRadixBlock + 2);
-        b.unit_order = c.take<uint32_t>((size_t)bwd_units_cap((uint32_t)R, grid) + 2 * kOrderLists);
+        b.unit_order = c.take<uint32_t>(unit_order_words(bwd_units_cap((uint32_t)R, grid)));
         // LAST: only touched for the tiles a pass segments (32 B per pair + 4 KB per tile of address space)
         b.ckpt = c.take<float4>(ckpt_slots(R, Tn) * 256);
         b.end = c.p;
@@ -673,7 +675,7 @@ struct BlendBwdArgs {     // blend.hip
     float* pair_grad;  // [R][kPairGrad]: mx, my, cA, cB, cC, op, r, g, b per (tile, Gaussian) pair, emission order
     unsigned char* pair_flag;  // [R] set for rows written in this pass
     const unsigned long long* quad_masks;   // BinState::quad_masks as the forward left them (null: recompute)
-    uint32_t* tile_order;                   // BinState::unit_order: launch order of the (tile, segment) units, heaviest
+    uint32_t* unit_order;                   // BinState::unit_order: launch order of the (tile, segment) units, heaviest
                                             // first (null: one workgroup per tile, row-major bands, one per XCD)
     uint32_t units_cap;                     // slots of the kOrderLists lists together (= workgroups launched)
     const uint32_t* quad_depth;             // ImageState::quad_depth, what the order is built from
@@ -828,3 +830,4 @@ __device__ __forceinline__ void install_block_from_kernarg(Block* dst, int tid, 
 #endif
 
 }  // namespace r3
+

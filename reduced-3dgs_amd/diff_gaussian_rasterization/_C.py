@@ -1162,7 +1162,8 @@ def bwd_segments():
 def export_tile_order(H, W, imageBuffer, P=0, num_rendered=0, binningBuffer=None):
     """Debug accessor (not in the reference): quad_depth int32[tiles, 4] (deepest contributor of each 8x8 quadrant, left by
     the forward) and -- given the binning buffer, P and num_rendered of the pass -- the launch order of the last backward
-    over this state: `lists`, eight dicts (tile, segment, segments int64 arrays, each list heaviest first, and `walk`, the
+    over this state: `lists`, eight dicts (tile, segment, segments int64 arrays and the unit `words` they were read from, each
+    list heaviest first, and `walk`, the
     entries per list segment its units walk, 0 = whole tiles), and `units`, their concatenation."""
     n = ((W + 15) // 16) * ((H + 15) // 16)
     qd = torch.empty((n, 4), dtype=torch.int32, device=imageBuffer.device)
@@ -1185,13 +1186,18 @@ def export_tile_order(H, W, imageBuffer, P=0, num_rendered=0, binningBuffer=None
         for g in range(_ORDER_LISTS):   # list g: made from the 4 x 4 tile blocks g, g + 8, ...; consumed as entries b // 8 of list b % 8
             cnt, walk_log2 = int(o[cap + 2 * g]), int(o[cap + 2 * g + 1])
             u = o[g * per:g * per + cnt]
-            lists.append(dict(tile=u & 0xFFFFF, segment=(u >> 20) & 63, segments=u >> 26, walk=(1 << walk_log2) if walk_log2 else 0))
+            lists.append(dict(unit_fields(u), words=u, walk=(1 << walk_log2) if walk_log2 else 0))
         out["lists"] = lists
         out["units"] = {k: np.concatenate([l[k] for l in lists]) for k in ("tile", "segment", "segments")}
     return out
 
 
 _ORDER_LISTS = 8
+
+
+def unit_fields(u):
+    """The fields of unit words (csrc/unit_order.h unit_unpack; tests/test_unit_order_cpu.py holds the masks to the header)."""
+    return dict(tile=u & 0xFFFFF, segment=(u >> 20) & 63, segments=u >> 26)
 
 
 def rasterize_gaussians_counters(*args):
