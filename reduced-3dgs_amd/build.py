@@ -39,6 +39,9 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "blend.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # the backward blend's unit order (split out of blend.hip): compiled as it was there
     "unit_order.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # depth / alpha / median-depth maps: the forward blend's step replayed, so the forward blend's flags (the same
+    # contraction: its recomputed T and last contributor are held to the forward's bit for bit)
+    "aux_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's
@@ -110,7 +113,7 @@ def build_torch_binding(force=False, verbose=True):
 
     import torch
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h",
-                                                               "r3dgs_trainstats.h", "r3dgs_quantised.h")]
+                                                               "r3dgs_trainstats.h", "r3dgs_quantised.h", "r3dgs_aux.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
             [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT

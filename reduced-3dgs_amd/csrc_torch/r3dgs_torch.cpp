@@ -34,6 +34,7 @@
 #include <utility>
 #include <vector>
 
+#include "r3dgs_aux.h"
 #include "r3dgs_loss.h"
 #include "r3dgs_optim.h"
 #include "r3dgs_quantised.h"
@@ -59,6 +60,7 @@ using at::Tensor;
     X(r3dgs_pass_query, true)                                 \
     X(r3dgs_backward, true)                                   \
     X(r3dgs_mark_visible, true)                               \
+    X(r3dgs_aux_maps, true)                                   \
     X(r3dgs_l1_ssim_workspace_bytes, false)                   \
     X(r3dgs_l1_ssim_forward, false)                           \
     X(r3dgs_l1_ssim_backward, false)                          \
@@ -448,6 +450,40 @@ std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz,
     return {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation};
 }
 
+// r3dgs_aux_maps over the three buffers a forward returned -> (depth, alpha, median_depth [1,H,W], T_check [H,W],
+// n_check int32 [H,W]); a map that was not asked for is an undefined tensor.  `capacity`: as backward's.
+std::vector<Tensor> aux_maps(int64_t P, int64_t capacity, int64_t image_height, int64_t image_width, const Tensor& geomBuffer,
+                             const Tensor& binningBuffer, const Tensor& imageBuffer, bool want_depth, bool want_alpha,
+                             bool want_median, bool want_checks)
+{
+    need_bound();
+    c10::Device dev = imageBuffer.defined() && imageBuffer.numel() ? imageBuffer.device() : geomBuffer.device();
+    if (P != 0) {
+        if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
+        if (geomBuffer.device() != dev || binningBuffer.device() != dev || imageBuffer.device() != dev)
+            throw std::runtime_error("aux_maps: the three state buffers must live on one device");
+    } else if (!dev.is_cuda()) {   // nothing says where: the current device, as the forward's empty result
+        dev = c10::Device(c10::DeviceType::CUDA, c10::hip::current_device());
+    }
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    const int H = (int)image_height, W = (int)image_width;
+    Tensor depth, alpha, median, T_check, n_check;
+    if (want_depth) depth = at::empty({1, H, W}, f32);
+    if (want_alpha) alpha = at::empty({1, H, W}, f32);
+    if (want_median) median = at::empty({1, H, W}, f32);
+    if (want_checks) {
+        T_check = at::empty({H, W}, f32);
+        n_check = at::empty({H, W}, f32.dtype(at::kInt));
+    }
+    auto fp = [](const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+    if (api.r3dgs_aux_maps((int)P, (int)capacity, W, H, blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer),
+                           fp(depth), fp(alpha), fp(median), fp(T_check),
+                           n_check.defined() ? reinterpret_cast<unsigned*>(n_check.data_ptr<int>()) : nullptr, cur_stream(dev)) < 0)
+        fail("aux_maps");
+    return {depth, alpha, median, T_check, n_check};
+}
+
 // -> (scales [P,3], rotations [P,4]) by csrc/param_math.h, the values the raw-parameter kernels use
 std::tuple<Tensor, Tensor> activate_params(const Tensor& scaling, const Tensor& rotation)
 {
@@ -779,6 +815,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("forward_reserved", &forward_reserved);
     m.def("backward", &backward);
     m.def("mark_visible", &mark_visible);
+    m.def("aux_maps", &aux_maps);
     m.def("forward_params", &forward_params);
     m.def("forward_params_reserved", &forward_params_reserved);
     m.def("backward_params", &backward_params);

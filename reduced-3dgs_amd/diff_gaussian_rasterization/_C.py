@@ -97,6 +97,8 @@ _ABI = {
         "r3dgs_profile_stage_count": (_i, []),
         "r3dgs_profile_stage_name": (_str, [_i]),
         "r3dgs_profile_read": (_i, [_vp, _vp]),
+        # include/r3dgs_aux.h
+        "r3dgs_aux_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         # include/r3dgs_reduction.h
         "r3dgs_min_pixel_size": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_sphere_ellipsoid_intersection": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -556,6 +558,14 @@ def _pair_capacity(R, P, W, H, binningBuffer):
     return _lib.r3dgs_binning_capacity(P, W, H, int(binningBuffer.numel())) if binningBuffer.numel() else 0
 
 
+def _seen(*result):
+    """A non-empty forward's six-tuple on its way out: kept for the thread's forward_state recorder, if one is open."""
+    rec = getattr(_tls, "forward_recorder", None)
+    if rec is not None:
+        rec.result = result
+    return result
+
+
 def _reserved_result(strict, ticket, reserve, rendered, flags, out_color, radii, geom, binning, img):
     """A pass issued on a reservation (either binding; rendered < 0: not fetched yet) -> the forward's six-tuple, or None:
     strict mode found the pass truncated and the caller redoes it on the exact-size path."""
@@ -564,9 +574,9 @@ def _reserved_result(strict, ticket, reserve, rendered, flags, out_color, radii,
     _stats["reserved_passes"] += 1
     if not strict:
         _watch_overflow()
-        return nr, out_color, radii, geom, binning, img
+        return _seen(nr, out_color, radii, geom, binning, img)
     if not nr.truncated:   # waits for the pass's header (not for the pass)
-        return nr, out_color, radii, geom, binning, img
+        return _seen(nr, out_color, radii, geom, binning, img)
     _stats["redone_passes"] += 1
     return None
 
@@ -575,7 +585,7 @@ def _exact_result(rendered, out_color, radii, geom, binning, img):
     """An exact-size pass -> the forward's six-tuple."""
     _stats["exact_passes"] += 1
     pairs = int(_lib.r3dgs_forward_pairs())   # pairs actually binned (<= num_rendered, what the blob was carved for)
-    return NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom, binning, img
+    return _seen(NumRendered(0, max(int(rendered), 1), rendered, pairs), out_color, radii, geom, binning, img)
 
 
 def _drive_forward(fn_exact, fn_reserved, args, what, dev, P, W, H, vm_ptr, lean, counters, out_color, radii, exact, debug,
@@ -1112,6 +1122,65 @@ def hint_next_forward(will_backward):
     no backward will follow (rendering under no_grad) skips what it would only do for the backward's sake (the SH direction
     derivatives, 36 B per visible Gaussian).  One-shot: the call after the next forward trains again."""
     _tls.next_forward_trains = bool(will_backward)
+
+
+class forward_state:
+    """`with forward_state() as st:` -- st.result is the six-tuple (num_rendered, out_color, radii, geomBuffer,
+    binningBuffer, imgBuffer) of the last non-empty forward this thread issued inside the block, through whichever
+    wrapper or autograd function (None: there was none, e.g. P == 0).  How r3dgs_render.render(aux=...) gets at the state
+    blobs of the forward it has just run; nothing is kept outside such a block."""
+
+    def __init__(self):
+        self.result = None
+
+    def __enter__(self):
+        self._outer = getattr(_tls, "forward_recorder", None)
+        _tls.forward_recorder = self
+        return self
+
+    def __exit__(self, *a):
+        _tls.forward_recorder = self._outer
+
+
+AUX_MAPS = ("depth", "alpha", "median_depth")
+
+
+def aux_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, maps=AUX_MAPS, checks=False):
+    """r3dgs_aux_maps (include/r3dgs_aux.h) over the three buffers a forward returned -> {name: float [1,H,W]} for the names
+    in `maps` (any subset of AUX_MAPS): "depth" = sum z alpha T over the blended entries (not normalised), "alpha" = 1 - final
+    T, "median_depth" = z of the first entry that leaves T < 0.5 (0: none).  R: the forward's num_rendered (a NumRendered) or
+    the pair capacity of its binning buffer.  checks=True adds "T_check" (float [H,W]) and "n_check" (int32 [H,W]): the pass's
+    own final T and last contributor.  The buffers are only read; the maps carry no gradient."""
+    maps = tuple(maps)
+    for name in maps:
+        if name not in AUX_MAPS:
+            raise ValueError(f"aux_maps: unknown map {name!r} (expected a subset of {AUX_MAPS})")
+    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    P, H, W = int(P), int(H), int(W)
+    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
+        raise RuntimeError("aux_maps: the three state buffers must live on one device")
+    if _ext is not None:
+        cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
+        got = _ext.aux_maps(P, int(cap), H, W, geomBuffer, binningBuffer, imageBuffer, "depth" in maps, "alpha" in maps,
+                            "median_depth" in maps, bool(checks))
+        out = {name: t for name, t in zip(AUX_MAPS, got[:3]) if name in maps}
+        if checks:
+            out["T_check"], out["n_check"] = got[3], got[4]
+        return out
+    if dev.type != "cuda":   # P == 0 and nothing says where: the current device, as the forward's empty result
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out = {name: torch.empty((1, H, W), dtype=torch.float32, device=dev) for name in maps}
+    if checks:
+        out["T_check"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+        out["n_check"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
+    with _on_device(dev):
+        _check(_lib.r3dgs_aux_maps(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                                   _ptr(out.get("depth")), _ptr(out.get("alpha")), _ptr(out.get("median_depth")),
+                                   _ptr(out.get("T_check")), _ptr(out.get("n_check")), _stream()), "aux_maps")
+    return out
 
 
 def set_sh_cache(on):

@@ -156,6 +156,20 @@ def rasterize_gaussian_params(xyz, means2D, features_dc, features_rest, degrees,
                                           raster_settings, lambda_sh_sparsity)
 
 
+def aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer,
+             maps=("depth", "alpha", "median_depth")):
+    """Per-pixel maps replayed from the three buffers a forward returned (`_C.rasterize_gaussians*` hand them out; P is the
+    model's size, num_rendered the forward's first result) -> {name: float [1,H,W]} for the names in `maps`:
+      "depth"         sum over the blended Gaussians of z * alpha * T (view depth z; fp32, list order).  Not normalised, no
+                      background term: divide by "alpha" for a mean depth
+      "alpha"         1 - final transmittance
+      "median_depth"  z of the first blended Gaussian after which T < 0.5; 0 where none brings T below 0.5
+    and 0 in all three where nothing contributed.  One kernel launch, no host wait; the buffers are only read, so a backward
+    over them afterwards is unaffected.  The maps carry NO gradient."""
+    with torch.no_grad():
+        return _C.aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, maps=maps)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

@@ -16,12 +16,20 @@ the fallback routes) -- or a r3dgs_quantised.QuantisedModel, which is rendered f
 (the three Python-side options, override_color and lambda_sh_sparsity are refused).  A QuantisedModel on which gradients
 were asked for (`requires_grad_`) trains, with grad enabled, through the same raw-parameter route on tensors decoded for the
 step, and the result then carries "viewspace_points" like any model's; otherwise "viewspace_points" is None.
+
+`aux=("depth", "alpha", "median_depth")` (or any subset) adds those keys to the result: float [1,H,W] maps replayed from the
+state the forward left (diff_gaussian_rasterization.aux_maps, include/r3dgs_aux.h) -- "depth" is the blend-weighted sum of
+the view depths (NOT normalised: divide by "alpha" for a mean), "alpha" = 1 - final transmittance, "median_depth" the depth of
+the first Gaussian that brings the transmittance below 0.5 (0 where none does).  One extra kernel launch per call; the maps
+carry no gradient (detached tensors), and the backward of "render" is what it is without them.  aux=None (the default): no
+extra launch, the same keys as before.
 """
+import functools
 import math
 
 import torch
 
-from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C,
+from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps,
                                          rasterize_gaussian_params)
 from r3dgs_quantised import QuantisedModel
 
@@ -83,10 +91,26 @@ def _render_quantised(camera, qm, pipe, bg_color, scaling_modifier, override_col
     return {"render": image, "viewspace_points": None, "visibility_filter": radii > 0, "radii": radii, "FPS": fps}
 
 
+def _with_aux(aux, camera, out, state):
+    """`out` with the maps named in `aux` added, from the six-tuple `state` of the forward that produced it (None: an empty
+    model, nothing was rendered -- zero maps)."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    if state is None:
+        dev = out["render"].device
+        out.update({name: torch.zeros((1, H, W), dtype=torch.float32, device=dev) for name in aux})
+        return out
+    num_rendered, _, radii, geom, binning, img = state
+    with torch.no_grad():
+        out.update(aux_maps(int(radii.numel()), num_rendered, H, W, geom, binning, img, maps=aux))
+    return out
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, lambda_sh_sparsity=0.,
            measure_fps=False, variable_sh_bands=False):
     """Render the scene seen by `viewpoint_camera`.  bg_color must be a device tensor.
-    -> {"render", "viewspace_points", "visibility_filter", "radii", "FPS"}"""
+    -> {"render", "viewspace_points", "visibility_filter", "radii", "FPS"}
+    Keyword-only extension (not a parameter of the reference's render, so not part of this signature): aux=("depth", "alpha",
+    "median_depth") or any subset adds those maps, each float [1,H,W] without gradient; see the module's docstring."""
     if isinstance(pc, QuantisedModel):
         return _render_quantised(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, lambda_sh_sparsity,
                                  measure_fps)
@@ -150,3 +174,20 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # culled Gaussians (radius 0) take no part in the densification statistics
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
             "FPS": fps}
+
+
+_render = render   # the reference's signature, parameter for parameter (tests/test_params_cpu.py holds it to the reference's source)
+
+
+@functools.wraps(_render)
+def render(*args, aux=None, **kwargs):
+    if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
+        return _render(*args, **kwargs)
+    aux = tuple(aux)
+    for name in aux:
+        if name not in _C.AUX_MAPS:
+            raise ValueError(f"render: unknown aux map {name!r} (expected a subset of {_C.AUX_MAPS})")
+    with _C.forward_state() as st:
+        out = _render(*args, **kwargs)
+    camera = args[0] if args else kwargs["viewpoint_camera"]
+    return _with_aux(aux, camera, out, st.result)
