@@ -1,5 +1,6 @@
 /* r3dgs_quantised.h -- C ABI of the codebook-indexed (quantised) model: the inference forward that reads the compressed
- * representation in place, its decoder, and its size (reduced-3dgs_amd/csrc/quant_math.h, preprocess.hip, capi.hip).
+ * representation in place, its decoder, and its size (reduced-3dgs_amd/csrc/quant_math.h, preprocess.hip, capi.hip,
+ * pass_driver.hip).
  * The Python surface is r3dgs_quantised.QuantisedModel.
  * Same conventions as r3dgs_rasterizer.h: device pointers; `void* stream` is a hipStream_t; return >= 0 on success, < 0
  * with the message in r3dgs_last_error().  The forwards are inference only; what training needs beside them is the adjoint of

@@ -177,8 +177,8 @@ int r3dgs_aux_maps(int P, int R, int width, int height, char* geom_buffer, char*
         if (width < 1 || height < 1 || P < 0 || R < 0)
             throw Error("aux_maps: need width, height >= 1 and P, R >= 0, got P = " + std::to_string(P) + ", R = " +
                         std::to_string(R) + ", " + std::to_string(width) + "x" + std::to_string(height));
-        const int gx = (width + kTile - 1) / kTile, gy = (height + kTile - 1) / kTile;
-        const size_t N = (size_t)width * height, Tn = (size_t)gx * gy;
+        const TileGrid grid = grid_of(width, height);
+        const size_t N = (size_t)width * height, Tn = grid.n();
         if (Tn * 4 > 0x7fffffffull) throw Error("aux_maps: the image has too many tiles for one launch");
         if (P == 0 || R == 0) {   // nothing was binned: nothing to walk
             float* const maps[4] = {depth, alpha, median_depth, T_check};
@@ -191,20 +191,18 @@ int r3dgs_aux_maps(int P, int R, int width, int height, char* geom_buffer, char*
         if (!depth && !alpha && !median_depth && !T_check && !n_check) return 0;
         // (the arrays read here lie in front of the geometry blob's temp storage and of its optional tail: their offsets
         // are those of every forward's carve, lean or full)
-        const GeomState geom = GeomState::carve(geom_buffer, (size_t)P, 0);
-        const BinState bin = BinState::carve(binning_buffer, (size_t)R, pair_layout(P, Tn).wide, TileGrid{(uint32_t)gx, (uint32_t)gy});
-        const ImageState img = ImageState::carve(image_buffer, N, Tn);
+        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
         AuxArgs a;
-        a.ranges = img.ranges;
-        a.point_list = bin.point_list;
-        a.rec = geom.rec;
-        a.depth_key = geom.depth_key;
-        a.final_T = img.final_T;
-        a.n_contrib = img.n_contrib;
-        a.quad_depth = img.quad_depth;
+        a.ranges = st.img.ranges;
+        a.point_list = st.bin.point_list;
+        a.rec = st.geom.rec;
+        a.depth_key = st.geom.depth_key;
+        a.final_T = st.img.final_T;
+        a.n_contrib = st.img.n_contrib;
+        a.quad_depth = st.img.quad_depth;
         a.W = width;
         a.H = height;
-        a.gx = gx;
+        a.gx = (int)grid.gx;
         a.nblocks = (uint32_t)(Tn * 4);
         a.P = (uint32_t)P;
         a.R = (uint32_t)R;

@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void radix_digit_scan_kernel(const RadixArgs* 
     const uint32_t* row = a.rows + (size_t)blockIdx.x * a.row_stride;
     uint32_t* out = a.base + (size_t)blockIdx.x * a.row_stride;
     // 1024 counts per trip, four consecutive ones per thread as one 16-byte access (rows are padded to a multiple of
-    // four counts and 16-byte aligned, capi.hip); counts of workgroups that do not exist read as zero
+    // four counts and 16-byte aligned, common.h radix_row_stride); counts of workgroups that do not exist read as zero
     uint32_t run = 0;
     for (uint32_t c0 = 0; c0 < nb; c0 += 1024u) {
         const uint32_t i = c0 + threadIdx.x * 4u;
@@ -599,7 +599,7 @@ void launch_export_point_list(int count, const uint32_t* point_list, const GeomH
 }
 
 // which buffer of the blob holds the sorted words (split layout: their keys) after the passes (see the fill of RadixArgs
-// in capi.hip)
+// in pass_driver.hip fill_fwd_args)
 const char* sorted_words(const BinState& b, const PairLayout& l)
 {
     if (l.wide) return (l.passes & 1) ? b.words_b : b.words_a;   // a -> b -> a (-> b)

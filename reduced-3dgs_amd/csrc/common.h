@@ -11,7 +11,7 @@
 // The parts the backward needs sit at the FRONT of each blob so that their offsets do not depend on
 // library temp-storage sizes.
 //
-// How a pass is issued (capi.hip): every kernel of a pass reads its pointers and scalars from ONE device-resident
+// How a pass is issued (pass_driver.hip): every kernel of a pass reads its pointers and scalars from ONE device-resident
 // argument block (FwdPassArgs / BwdPassArgs) instead of from its kernel arguments.  The block is (re)written by a
 // one-workgroup kernel whose by-value argument IS the block, so a whole pass is "write the block, run a fixed chain
 // of kernels whose launch parameters never change": that chain is captured once per shape into a hipGraph and
@@ -106,7 +106,7 @@ inline size_t depth_hist_per_block(size_t P)
     const size_t per = ((want + kHistBatch - 1) / kHistBatch) * kHistBatch;
     return per < (size_t)kHistBatch ? (size_t)kHistBatch : per;
 }
-int depth_bucket_load();   // mean Gaussians per bucket aimed for up to 1 M Gaussians (R3DGS_DEPTH_BUCKET_LOAD; default 128); capi.hip
+int depth_bucket_load();   // mean Gaussians per bucket aimed for up to 1 M Gaussians (R3DGS_DEPTH_BUCKET_LOAD; default 128); pass_driver.hip
 inline int depth_bucket_count(size_t P)
 {
     int nb = kMinDepthBuckets;
@@ -303,6 +303,10 @@ struct TileGrid {
         return (uint32_t)(m < n() ? m : n());
     }
 };
+inline TileGrid grid_of(int width, int height)   // the kTile x kTile tiles that cover a width x height image
+{
+    return TileGrid{(uint32_t)((width + kTile - 1) / kTile), (uint32_t)((height + kTile - 1) / kTile)};
+}
 // workgroups of the backward blend = capacity of its unit order: per list its tiles once, plus its share of the extra
 // segments a pass may have (bounded by the lists: sum over tiles of len / S <= R / S; capped -- a list that wants more
 // walks longer segments)
@@ -315,7 +319,7 @@ inline uint32_t bwd_units_cap(uint32_t reserve, const TileGrid& g) { return (bwd
 // words of the order array: the lists' slots, then per list a trailer of two words (addressed by unit_order.h)
 constexpr uint32_t kUnitTrailerWords = 2;
 R3_HD uint32_t unit_order_words(uint32_t units_cap) { return units_cap + kUnitTrailerWords * kOrderLists; }
-int bwd_segment_log2();         // R3DGS_BWD_SEG_LEN = 128 (default) | 256 -> 7 | 8; capi.hip
+int bwd_segment_log2();         // R3DGS_BWD_SEG_LEN = 128 (default) | 256 -> 7 | 8; pass_driver.hip
 int bwd_segment_factor_pct();   // R3DGS_BWD_SEG_FACTOR: lists >= this percentage of the pass's mean length are split (75)
 
 struct BinState {
@@ -409,6 +413,23 @@ struct ImageState {
     }
 };
 
+// The three states of a pass of P Gaussians and a pair capacity of R in its caller's blobs (depth_temp: the generic depth
+// sort's temp storage -- behind everything a backward or an export reads, so those may pass 0).
+struct PassBlobs {
+    char *geom, *binning, *image;
+};
+struct PassStates {
+    GeomState geom;
+    BinState bin;
+    ImageState img;
+};
+inline PassStates carve_pass(int P, uint32_t R, int width, int height, const PassBlobs& b, size_t depth_temp)
+{
+    const TileGrid grid = grid_of(width, height);
+    return {GeomState::carve(b.geom, (size_t)P, depth_temp), BinState::carve(b.binning, (size_t)R, pair_layout(P, grid.n()).wide, grid),
+            ImageState::carve(b.image, (size_t)width * height, grid.n())};
+}
+
 template <class S, class... A>
 size_t required_bytes(A... a)
 {
@@ -420,7 +441,7 @@ size_t required_bytes(A... a)
 size_t depth_sort_temp_bytes(size_t P);
 
 // Launch size of the pair-sized kernels for a binning blob of `reserve` pairs: the reservation is ~1.5x the largest
-// recent pair count plus a constant (capi.hip reserve_hint), the grids cover that count with a little headroom and
+// recent pair count plus a constant (reserve_advice.h Advisor::hint), the grids cover that count with a little headroom and
 // their blocks stride over whatever lies beyond.  A function of `reserve` alone, so forward, backward and the graph
 // cache agree on it.
 inline uint32_t grid_pairs_for(uint32_t reserve)
@@ -758,13 +779,12 @@ struct BwdPlan {
     uint32_t reserve, grid_pairs;
     uint32_t units_cap;    // workgroups of the backward blend when it runs in unit order (bwd_units_cap)
     PairLayout layout;
-    int bwd_ppl;
     int has_pairs;         // 0: the forward ran with an empty reservation (P > 0, no binning blob)
     int f64_chain;         // the per-Gaussian backward evaluates the covariance chain in double (gauss_math.h; default)
     int raw_params;        // raw-parameter backward (BwdOutputs::dL_dsh_dc / dL_dsh_rest; activation backward applied)
 };
 
-// stage ids of the optional per-stage timers (capi.hip)
+// stage ids of the optional per-stage timers (pass_driver.hip)
 // kBlendBwdKernel: the backward blend kernel ALONE, inside kBlendBwd's events (which also cover the unit order and the pair
 // reduction): the duration bench.py's roofline.kernel_frac divides by
 enum Stage { kPre = 0, kDepthSort, kBinning, kBlendFwd, kBlendBwd, kPreBwd, kColor, kBlendBwdKernel, kNumStages };
@@ -810,7 +830,7 @@ void launch_colour_variance_accumulate(int P, const int* D, int M, int max_sh_de
                                        const float* transmittance, float* wSum, float* wSumSq, float* mean,
                                        float* variance, float* accum, hipStream_t s);
 
-int env_int(const char* env, int dflt, int lo, int hi);   // capi.hip
+int env_int(const char* env, int dflt, int lo, int hi);   // pass_driver.hip
 
 #if defined(__HIPCC__)
 // Copies the pass block, which the calling kernel received as its SECOND by-value argument after a `Block* dst`, word by

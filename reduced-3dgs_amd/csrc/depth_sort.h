@@ -378,7 +378,7 @@ __device__ __forceinline__ uint32_t rect_tiles(uint2 rc)
 // that live elsewhere and are pinned here:
 //   * key span of a bucket < 2^24: keys are the bit patterns of positive floats (< 2^31) cut into >= kMinDepthBuckets
 //     equal-width buckets (common.h depth_bucket_count) -- and a sub-bucket only narrows its range;
-//   * id < 2^24: P >= 2^24 is routed to the generic sort (capi.hip plan_forward: generic_depth_sort);
+//   * id < 2^24: P >= 2^24 is routed to the generic sort (pass_driver.hip make_fwd_plan: generic_depth_sort);
 //   * position < 2^16: a word-sorted bucket holds at most kBucketCap records; a bigger one is first split in global memory
 //     into pieces of ~2048 (kGlobalSplitCap / kGlobalSplitMax) and a piece above kBucketCap takes the radix path.
 static_assert((1u << 31) / (unsigned)kMinDepthBuckets <= (1u << 24), "a depth bucket's key span must fit the sort word's 24 key bits");

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_geom_kernel(FwdPassArgs*
     }
     // per-workgroup totals, stored (not accumulated): visible count (SH-sparsity normaliser of the backward),
     // num_rendered, and the depth range of the visible Gaussians (bucketed depth sort, binning.hip).  R does not depend
-    // on the depth order, so the host can fetch it while the GPU is busy with the depth sort (capi.hip).
+    // on the depth order, so the host can fetch it while the GPU is busy with the depth sort (pass_driver.hip forward_exact).
     const unsigned long long vmask = __ballot(o.radius > 0);
     const bool binned = o.tiles > 0;
     const unsigned long long bmask = __ballot(binned);

@@ -3,9 +3,9 @@
 //
 // A UNIT is what one workgroup of the backward blend walks: a tile, or -- for a tile whose list the pass splits (common.h) --
 // one segment of its list.  The order is kOrderLists lists (common.h TileGrid), each sorted by decreasing weight class.
-// Three parties read this header and nothing else about the order: unit_order.hip (the counting sort that writes it),
-// blend.hip (blend_bwd_kernel decodes its unit) and capi.hip (sizes and exports the array); tests/hostcheck_unit_order replays
-// the same functions serially on the CPU.  Integer arithmetic, and the one fp32 multiply of the class.
+// Four parties read this header and nothing else about the order: unit_order.hip (the counting sort that writes it),
+// blend.hip (blend_bwd_kernel decodes its unit), pass_driver.hip (sizes the array) and capi.hip (exports it);
+// tests/hostcheck_unit_order replays the same functions serially on the CPU.  Integer arithmetic, and the one fp32 multiply of the class.
 #pragma once
 #include "common.h"
 
