@@ -61,6 +61,8 @@ using at::Tensor;
     X(r3dgs_backward, true)                                   \
     X(r3dgs_mark_visible, true)                               \
     X(r3dgs_aux_maps, true)                                   \
+    X(r3dgs_aux_maps_backward_workspace_bytes, true)          \
+    X(r3dgs_aux_maps_backward, true)                          \
     X(r3dgs_l1_ssim_workspace_bytes, false)                   \
     X(r3dgs_l1_ssim_forward, false)                           \
     X(r3dgs_l1_ssim_backward, false)                          \

@@ -99,6 +99,9 @@ _ABI = {
         "r3dgs_profile_read": (_i, [_vp, _vp]),
         # include/r3dgs_aux.h
         "r3dgs_aux_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_aux_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_aux_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # 3 upstream, 6 outputs
         # include/r3dgs_reduction.h
         "r3dgs_min_pixel_size": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_sphere_ellipsoid_intersection": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1180,6 +1183,55 @@ def aux_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, maps=AUX_MAPS, 
         _check(_lib.r3dgs_aux_maps(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                                    _ptr(out.get("depth")), _ptr(out.get("alpha")), _ptr(out.get("median_depth")),
                                    _ptr(out.get("T_check")), _ptr(out.get("n_check")), _stream()), "aux_maps")
+    return out
+
+
+AUX_GRADS = ("means2D", "means3D", "opacity", "scales", "rotations", "cov3D")
+_AUX_GRAD_COLS = dict(means2D=3, means3D=3, opacity=1, scales=3, rotations=4, cov3D=6)
+
+
+def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
+                      scales, scale_modifier, rotations, cov3D_precomp, radii, dL_ddepth=None, dL_dalpha=None, dL_dmedian=None,
+                      want=AUX_GRADS):
+    """r3dgs_aux_maps_backward (include/r3dgs_aux.h): the gradients of the maps of `aux_maps` over the same three buffers.
+    dL_ddepth / dL_dalpha / dL_dmedian: float tensors of H*W elements (any shape), None = zero.  scales / rotations are the
+    ACTIVATED values (or cov3D_precomp is given and they are empty).  -> {name: float [P, cols]} for the names in `want` (a
+    subset of AUX_GRADS); "opacity" is the gradient of the raw opacity, "means2D" what densification reads.  The buffers are
+    only read; the workspace is allocated here, per call, from torch's caching allocator."""
+    want = tuple(want)
+    for name in want:
+        if name not in AUX_GRADS:
+            raise ValueError(f"aux_maps_backward: unknown gradient {name!r} (expected a subset of {AUX_GRADS})")
+    P, H, W = int(P), int(H), int(W)
+    dev = means3D.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if dev.type != "cuda":
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ups = []
+    for name, g in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha), ("dL_dmedian", dL_dmedian)):
+        g = _dev(g, dev)
+        if g is not None and g.numel() != H * W:
+            raise RuntimeError(f"aux_maps_backward: {name} has {g.numel()} elements, the image {H * W}")
+        ups.append(g)
+    out = {name: torch.empty((P, _AUX_GRAD_COLS[name]), dtype=torch.float32, device=dev) for name in want}
+    if P == 0:
+        return out
+    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
+        raise RuntimeError("aux_maps_backward: the state buffers and the model must live on one device")
+    m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
+    rad = _dev(radii, dev, torch.int32)
+    vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
+    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
+    with _on_device(dev):
+        nbytes = _lib.r3dgs_aux_maps_backward_workspace_bytes(P, cap, W, H)
+        if nbytes == 0 and cap:
+            _check(-1, "aux_maps_backward_workspace_bytes")
+        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_aux_maps_backward(
+            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
+            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(ups[0]), _ptr(ups[1]),
+            _ptr(ups[2]), *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "aux_maps_backward")
     return out
 
 

@@ -170,6 +170,57 @@ def aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuff
         return _C.aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, maps=maps)
 
 
+def aux_maps_backward(*args, **kwargs):
+    """Thin wrapper of `_C.aux_maps_backward` (include/r3dgs_aux.h r3dgs_aux_maps_backward): the gradients of the maps of
+    `aux_maps` with respect to the Gaussians, from upstream gradients of the maps, over the same three buffers."""
+    with torch.no_grad():
+        return _C.aux_maps_backward(*args, **kwargs)
+
+
+class _AuxMaps(torch.autograd.Function):
+    """`aux_maps` with gradients.  Inputs: means3D, means2D, opacities (raw), scales (activated), rotations (unit),
+    cov3D_precomp (or an empty tensor), then without gradient: the forward's six-tuple `state` (num_rendered, color, radii,
+    geomBuffer, binningBuffer, imgBuffer), raster_settings and the names of the maps  ->  one [1,H,W] tensor per name.
+    The forward is `aux_maps`; the backward is `aux_maps_backward` over the saved buffers."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, maps):
+        rs = raster_settings
+        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
+        got = _C.aux_maps(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer,
+                          imgBuffer, maps=maps)
+        ctx.raster_settings, ctx.num_rendered, ctx.maps = rs, num_rendered, tuple(maps)
+        ctx.save_for_backward(means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
+        ctx.set_materialize_grads(False)
+        return tuple(got[name] for name in maps)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        rs = ctx.raster_settings
+        means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors
+        up = dict(zip(ctx.maps, grads))
+        names = ("means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
+        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:6]) if need)
+        got = _C.aux_maps_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
+                                   binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D,
+                                   scales, rs.scale_modifier, rotations, cov3D_precomp, radii, up.get("depth"), up.get("alpha"),
+                                   up.get("median_depth"), want=want)
+        return tuple(got.get(n) for n in names) + (None, None, None)
+
+
+def aux_maps_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
+                       maps=("depth", "alpha", "median_depth")):
+    """The maps of `aux_maps` ATTACHED to the model's tensors -> {name: float [1,H,W]}.  `state`: the six-tuple the forward
+    returned (what `_C.forward_state()` records); scales / rotations: the activated values the forward saw (or cov3D_precomp);
+    means2D: the screen-space tensor whose .grad densification reads -- it receives the maps' share as well."""
+    empty = torch.Tensor([])
+    maps = tuple(maps)
+    got = _AuxMaps.apply(means3D, means2D, opacities, empty if scales is None else scales,
+                         empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
+                         state, raster_settings, maps)
+    return dict(zip(maps, got))
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

@@ -20,18 +20,40 @@ step, and the result then carries "viewspace_points" like any model's; otherwise
 `aux=("depth", "alpha", "median_depth")` (or any subset) adds those keys to the result: float [1,H,W] maps replayed from the
 state the forward left (diff_gaussian_rasterization.aux_maps, include/r3dgs_aux.h) -- "depth" is the blend-weighted sum of
 the view depths (NOT normalised: divide by "alpha" for a mean), "alpha" = 1 - final transmittance, "median_depth" the depth of
-the first Gaussian that brings the transmittance below 0.5 (0 where none does).  One extra kernel launch per call; the maps
-carry no gradient (detached tensors), and the backward of "render" is what it is without them.  aux=None (the default): no
+the first Gaussian that brings the transmittance below 0.5 (0 where none does).  One extra kernel launch per call; by default the
+maps carry no gradient (detached tensors), and the backward of "render" is what it is without them.  aux=None (the default): no
 extra launch, the same keys as before.
+
+`aux_grad=True` (with `aux`, under grad mode, for a model with something trainable -- a ValueError otherwise) returns the maps
+ATTACHED to the model's tensors instead: a loss on "depth" / "alpha" / "median_depth" reaches xyz, opacity, scaling and rotation
+(and the codebooks of a trainable QuantisedModel) through diff_gaussian_rasterization._AuxMaps, whose backward is one
+r3dgs_aux_maps_backward over the forward's state; its gradients add to those of "render" through autograd, and
+"viewspace_points".grad receives both.  On the raw-parameter route and for a QuantisedModel the activated scales and rotations
+the function takes are built in torch (pc.get_scaling / pc.get_rotation) only in this case, so torch carries the gradient
+through exp / normalize and the decode.  "median_depth" hands its gradient to the depth of the Gaussian it selected.
 """
 import functools
+import inspect
 import math
+import threading
 
 import torch
 
-from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps,
+from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps, aux_maps_with_grad,
                                          rasterize_gaussian_params)
 from r3dgs_quantised import QuantisedModel
+
+# render(aux_grad=True) asks the call it wraps for the tensors its forward was fed: a dictionary here, for the duration of that
+# call, receives "inputs" = (means3D, opacities, scales, rotations, cov3D_precomp) -- what _AuxMaps differentiates with respect
+# to.  Routes that built the activated values anyway hand those over; the others build them only when asked.
+_tls = threading.local()
+
+
+def _hand_over(means3D, opacities, scales, rotations, cov3D_precomp):
+    want = getattr(_tls, "inputs", None)
+    if want is not None:
+        want["inputs"] = (means3D, opacities, scales() if callable(scales) else scales,
+                          rotations() if callable(rotations) else rotations, cov3D_precomp)
 
 
 def _settings(camera, pc, pipe, bg_color, scaling_modifier):
@@ -72,6 +94,7 @@ def _render_quantised(camera, qm, pipe, bg_color, scaling_modifier, override_col
         t0.record()
     if qm.trainable and torch.is_grad_enabled():
         xyz, dc, rest, opacity, scaling, rotation, degrees = qm.decode_for_training()
+        _hand_over(xyz, opacity, lambda: torch.exp(scaling), lambda: torch.nn.functional.normalize(rotation), None)
         screenspace_points = torch.zeros_like(xyz, requires_grad=True) + 0
         screenspace_points.retain_grad()
         image, radii = rasterize_gaussian_params(xyz, screenspace_points, dc, rest, degrees, opacity, scaling, rotation, rs, 0.)
@@ -170,6 +193,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         t1.record()
         torch.cuda.synchronize()
         fps = 1 / t0.elapsed_time(t1)
+    if fused:   # the kernels activated the raw parameters: torch's own activations, only if somebody asks
+        _hand_over(xyz, pc._opacity, lambda: pc.get_scaling if hasattr(pc, "get_scaling") else torch.exp(pc._scaling),
+                   lambda: pc.get_rotation if hasattr(pc, "get_rotation") else torch.nn.functional.normalize(pc._rotation), None)
+    else:
+        _hand_over(pc.get_xyz, pc._opacity, scales, rotations, cov3D_precomp)
 
     # culled Gaussians (radius 0) take no part in the densification statistics
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
@@ -181,13 +209,42 @@ _render = render   # the reference's signature, parameter for parameter (tests/t
 
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
+    aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
+        if aux_grad:
+            raise ValueError("render: aux_grad=True without aux: name the maps the loss is put on")
         return _render(*args, **kwargs)
     aux = tuple(aux)
     for name in aux:
         if name not in _C.AUX_MAPS:
             raise ValueError(f"render: unknown aux map {name!r} (expected a subset of {_C.AUX_MAPS})")
-    with _C.forward_state() as st:
-        out = _render(*args, **kwargs)
+    if aux_grad and not torch.is_grad_enabled():
+        raise ValueError("render: aux_grad=True under no_grad: there is no graph to attach the maps to")
     camera = args[0] if args else kwargs["viewpoint_camera"]
-    return _with_aux(aux, camera, out, st.result)
+    if not aux_grad:
+        with _C.forward_state() as st:
+            out = _render(*args, **kwargs)
+        return _with_aux(aux, camera, out, st.result)
+    a = inspect.signature(_render).bind(*args, **kwargs)
+    a.apply_defaults()
+    a = a.arguments
+    pc, pipe = a["pc"], a["pipe"]
+    if isinstance(pc, QuantisedModel) and not pc.trainable:   # (before anything is launched)
+        raise ValueError("render: aux_grad=True needs a trainable model (requires_grad_ the QuantisedModel first)")
+    _tls.inputs = got = {}
+    try:
+        with _C.forward_state() as st:
+            out = _render(*args, **kwargs)
+    finally:
+        _tls.inputs = None
+    means3D, opacities, scales, rotations, cov3D = got["inputs"]
+    if not any(t is not None and t.requires_grad for t in got["inputs"]):
+        raise ValueError("render: aux_grad=True for a model with nothing trainable")
+    if st.result is None:   # an empty model: nothing was rendered -- zero maps, attached all the same (a backward through
+        out = _with_aux(aux, camera, out, None)   # them is valid and leaves zero gradients)
+        anchor = 0.0 * sum(t.sum() for t in got["inputs"] if t is not None and t.requires_grad)
+        out.update({name: out[name] + anchor for name in aux})
+        return out
+    rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
+    out.update(aux_maps_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, st.result, rs, maps=aux))
+    return out
