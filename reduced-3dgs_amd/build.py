@@ -57,6 +57,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "quant_grad.hip": EXACT,
     # densification: the decisions and the children's rows with the roundings densify_math.h names and no others
     "densify.hip": EXACT,
+    # camera gradients: the per-Gaussian backward's chain continued to the camera, so the per-Gaussian backward's flags
+    "camera_bwd.hip": EXACT,
     "capi.hip": [],
     # the pass driver behind the C ABI (split out of capi.hip): compiled as it was there
     "pass_driver.hip": [],

@@ -102,6 +102,10 @@ _ABI = {
         "r3dgs_aux_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_aux_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # 3 upstream, 6 outputs
+        # include/r3dgs_camera.h
+        "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
+        "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # radii, blob, 3 sums, 3 outputs
         # include/r3dgs_reduction.h
         "r3dgs_min_pixel_size": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_sphere_ellipsoid_intersection": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -853,18 +857,20 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
 
 def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation,
                                        scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, campos,
-                                       geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug):
+                                       geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug, _want_2d=False):
     """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dxyz[P,3], dL_dfeatures_dc[P,1,3], dL_dfeatures_rest[P,M-1,3],
-    dL_dscaling[P,3], dL_drotation[P,4]): gradients of the tensors passed in (raw scaling / rotation included)."""
+    dL_dscaling[P,3], dL_drotation[P,4]): gradients of the tensors passed in (raw scaling / rotation included).
+    _want_2d: + (dL_dcolors[P,3], dL_dconic[P,2,2]), the per-Gaussian sums camera_backward reads (the ctypes marshalling)."""
     _need("params")
     P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     opts = dict(dtype=torch.float32, device=dev)
     if P == 0:
-        return _zero_grads(dev, (0, 3), (0, 1), (0, 3), (0, 1, 3), (0, M - 1, 3), (0, 3), (0, 4))
+        return _zero_grads(dev, (0, 3), (0, 1), (0, 3), (0, 1, 3), (0, M - 1, 3), (0, 3), (0, 4)) + (
+            _zero_grads(dev, (0, 3), (0, 2, 2)) if _want_2d else ())
     rest = _NO_TENSOR if M == 1 else features_rest
     cap = _pair_capacity(R, P, W, H, binningBuffer)
-    if _ext is not None:
+    if _ext is not None and not _want_2d:
         return tuple(_ext.backward_params(_t(background), xyz, _t(radii), features_dc, rest, degrees, opacity, scaling, rotation,
                                           float(scale_modifier), _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy),
                                           dL_dout_color, _t(campos), geomBuffer, int(cap), binningBuffer, imageBuffer,
@@ -873,18 +879,20 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
     dL_dmeans3D, dL_dmeans2D, dL_dopacity = e(P, 3), e(P, 3), e(P, 1)
     dL_ddc, dL_drest, dL_dscaling, dL_drotation = e(P, 1, 3), e(P, M - 1, 3), e(P, 3), e(P, 4)
     scratch = e(P, 9)   # dL_dcolor [P,3] + dL_dcov3D [P,6]: written by the C ABI, no leaf on this path
+    dL_dconic = e(P, 2, 2) if _want_2d else None
     bg, vm, pm, cp = (_dev(t, dev) for t in (background, viewmatrix, projmatrix, campos))
     g, deg, rad = _dev(dL_dout_color, dev), _dev(degrees, dev, torch.int32), _dev(radii, dev, torch.int32)
     with _on_device(dev):
         st = _lib.r3dgs_backward_params(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest),
                                         _ptr(scaling), float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp),
                                         float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
-                                        _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), None, _ptr(dL_dopacity),
+                                        _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
                                         scratch.data_ptr(), _ptr(dL_dmeans3D), scratch.data_ptr() + 12 * P, _ptr(dL_ddc),
                                         _ptr(dL_drest), _ptr(dL_dscaling), _ptr(dL_drotation), float(lambda_sh_sparsity),
                                         int(bool(debug)), _stream())
     _check(st, "rasterize_gaussian_params_backward")
-    return dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation
+    out = (dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation)
+    return out + (scratch.view(-1)[:3 * P].view(P, 3), dL_dconic) if _want_2d else out
 
 
 def activate_params(scaling, rotation):
@@ -1232,6 +1240,84 @@ def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewma
             P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
             float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(ups[0]), _ptr(ups[1]),
             _ptr(ups[2]), *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "aux_maps_backward")
+    return out
+
+
+CAMERA_GRADS = ("viewmatrix", "projmatrix", "campos")
+_CAMERA_GRAD_SHAPES = dict(viewmatrix=(4, 4), projmatrix=(4, 4), campos=(3,))
+
+
+def _cam_tensor(t, dev, name, numel=None, dtype=torch.float32):
+    """An input of camera_backward as the library reads it, in place: refused instead of converted.  None / empty -> None."""
+    if t is None or t.numel() == 0:
+        return None
+    if t.device.type != "cuda":
+        raise RuntimeError(f"camera_backward: {name}: the MI355X rasterizer needs device tensors (no CPU path)")
+    if t.device != dev:
+        raise RuntimeError(f"camera_backward: {name}: expected a tensor on {dev}, got {t.device}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"camera_backward: {name}: expected {str(dtype)[6:]}, got {str(t.dtype)[6:]}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"camera_backward: {name}: expected a contiguous tensor")
+    if numel is not None and t.numel() != numel:
+        raise RuntimeError(f"camera_backward: {name}: expected {numel} elements, got {t.numel()}")
+    return t.detach()
+
+
+def camera_backward(means3D, degrees, sh, sh_rest, scales, rotations, scale_modifier, cov3D_precomp, raw_params, viewmatrix,
+                    projmatrix, campos, tanfovx, tanfovy, image_height, image_width, radii, geomBuffer, dL_dmeans2D, dL_dconic,
+                    dL_dcolors, want=CAMERA_GRADS):
+    """r3dgs_camera_backward (include/r3dgs_camera.h): the partial derivatives of the loss with respect to viewmatrix [4,4],
+    projmatrix [4,4] and campos [3] -- taken as independent inputs, in their own (transposed, row-vector) layout -- from the
+    per-Gaussian sums a backward has just written: dL_dmeans2D [P,3], dL_dconic [P,2,2] (rasterize_gaussians_backward's
+    `_want_conic`) and dL_dcolors [P,3].  raw_params False: sh [P,M,3] (None / empty: precomputed colours, campos gets zeros),
+    scales / rotations activated or cov3D_precomp; True: sh = features_dc, sh_rest = features_rest, scales / rotations the
+    model's raw tensors.  geomBuffer: the forward's.  -> {name: tensor} for the names in `want` (a subset of CAMERA_GRADS).
+    Two launches, no host wait; the workspace comes from torch's caching allocator per call.  Tensors are read in place: a
+    host tensor, a wrong dtype or a non-contiguous tensor is refused."""
+    want = tuple(want)
+    for name in want:
+        if name not in CAMERA_GRADS:
+            raise ValueError(f"camera_backward: unknown gradient {name!r} (expected a subset of {CAMERA_GRADS})")
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("camera_backward: means3D must have dimensions (num_points, 3)")
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("camera_backward: means3D: the MI355X rasterizer needs device tensors (no CPU path)")
+    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    raw = bool(raw_params)
+    m3 = _cam_tensor(means3D, dev, "means3D")
+    vm, pm = _cam_tensor(viewmatrix, dev, "viewmatrix", 16), _cam_tensor(projmatrix, dev, "projmatrix", 16)
+    cp = _cam_tensor(campos, dev, "campos", 3)
+    shc, rest = _cam_tensor(sh, dev, "sh"), _cam_tensor(sh_rest, dev, "sh_rest")
+    sc, rot = _cam_tensor(scales, dev, "scales", 3 * P), _cam_tensor(rotations, dev, "rotations", 4 * P)
+    cov = _cam_tensor(cov3D_precomp, dev, "cov3D_precomp", 6 * P)
+    deg, rad = _cam_tensor(degrees, dev, "degrees", P, torch.int32), _cam_tensor(radii, dev, "radii", P, torch.int32)
+    g2 = _cam_tensor(dL_dmeans2D, dev, "dL_dmeans2D", 3 * P)
+    gcon, gcol = _cam_tensor(dL_dconic, dev, "dL_dconic", 4 * P), _cam_tensor(dL_dcolors, dev, "dL_dcolors", 3 * P)
+    geom = _cam_tensor(geomBuffer, dev, "geomBuffer", dtype=torch.uint8)
+    if P and (vm is None or pm is None or cp is None):
+        raise RuntimeError("camera_backward: viewmatrix, projmatrix and campos are needed")
+    if shc is None:
+        M = 0
+    elif raw:
+        if tuple(shc.shape) != (P, 1, 3):
+            raise RuntimeError("camera_backward: features_dc must have dimensions (num_points, 1, 3)")
+        M = 1 if rest is None else 1 + int(rest.size(1))
+        if rest is not None and (rest.dim() != 3 or rest.size(0) != P or rest.size(2) != 3):
+            raise RuntimeError("camera_backward: features_rest must have dimensions (num_points, M-1, 3)")
+    else:
+        if shc.dim() != 3 or shc.size(0) != P or shc.size(2) != 3:
+            raise RuntimeError("camera_backward: sh must have dimensions (num_points, M, 3)")
+        M = int(shc.size(1))
+    out = {name: torch.empty(_CAMERA_GRAD_SHAPES[name], dtype=torch.float32, device=dev) for name in want}
+    with _on_device(dev):
+        nbytes = int(_lib.r3dgs_camera_backward_workspace_bytes(P))
+        work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_camera_backward(
+            P, _ptr(deg), M, W, H, _ptr(m3), _ptr(shc), _ptr(rest), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), int(raw),
+            _ptr(vm), _ptr(pm), _ptr(cp), float(tanfovx), float(tanfovy), _ptr(rad), _ptr(geom), _ptr(g2), _ptr(gcon), _ptr(gcol),
+            *[_ptr(out.get(name)) for name in CAMERA_GRADS], work.data_ptr(), _stream()), "camera_backward")
     return out
 
 

@@ -152,8 +152,141 @@ def rasterize_gaussian_params(xyz, means2D, features_dc, features_rest, degrees,
     _rotation) -> (color, radii); gradients flow to exactly those tensors."""
     if features_rest is None:
         features_rest = torch.Tensor([])
+    rs = raster_settings
+    if _camera_requires_grad(rs):   # a camera tensor asks for a gradient: the camera-differentiable function
+        return _RasterizeGaussianParamsCam.apply(xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation,
+                                                 rs, lambda_sh_sparsity, rs.viewmatrix, rs.projmatrix, rs.campos)
     return _RasterizeGaussianParams.apply(xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation,
                                           raster_settings, lambda_sh_sparsity)
+
+
+def _camera_requires_grad(rs):
+    """True if one of the settings' three camera tensors asks for a gradient (under grad mode)."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+
+
+# ---- the camera-differentiable pair.  Each is its existing counterpart plus three inputs (viewmatrix, projmatrix, campos) and
+# one more call in the backward; what the two share lives in the helpers below, the originals are not touched. ----------------
+
+def _cam_settings(raster_settings, model_device, viewmatrix, projmatrix, campos):
+    """raster_settings with the three camera tensors as the native calls read them -- detached, contiguous -- checked HERE,
+    before the forward is issued: the camera pass reads them in place and would refuse them only in the backward."""
+    for name, t, numel in (("viewmatrix", viewmatrix, 16), ("projmatrix", projmatrix, 16), ("campos", campos, 3)):
+        if not isinstance(t, torch.Tensor) or t.numel() != numel:
+            raise RuntimeError(f"camera gradients: {name} must be a tensor of {numel} elements")
+        if t.device != model_device:
+            raise RuntimeError(f"camera gradients: {name}: expected a tensor on {model_device}, got {t.device}")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"camera gradients: {name}: expected float32, got {str(t.dtype)[6:]}")
+    return raster_settings._replace(viewmatrix=viewmatrix.detach().contiguous(), projmatrix=projmatrix.detach().contiguous(),
+                                    campos=campos.detach().contiguous())
+
+
+def _cam_forward(ctx, native, args, rs, lambda_sh_sparsity, saved):
+    """The forward body of both functions: the native call `native(*args)`, the context, `saved(radii, geomBuffer,
+    binningBuffer, imgBuffer)` -> the tensors to keep."""
+    _C.hint_next_forward(any(ctx.needs_input_grad))
+    num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_native(native, args, rs.debug, "snapshot_fw.dump")
+    ctx.raster_settings, ctx.num_rendered, ctx.lambda_sh_sparsity = rs, num_rendered, lambda_sh_sparsity
+    ctx.save_for_backward(*saved(radii, geomBuffer, binningBuffer, imgBuffer))
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)
+    return color, radii
+
+
+def _cam_upstream(rs, grad_out_color, like):
+    if grad_out_color is None:  # the image did not take part in the loss
+        return torch.zeros((3, rs.image_height, rs.image_width), dtype=like.dtype, device=like.device)
+    return grad_out_color
+
+
+def _cam_backward(ctx, first_camera_slot, native, args, raw, **model):
+    """The native backward `native(*args)`, asked for its per-Gaussian sums as well -- its result starts with dL_dmeans2D and
+    ends with (dL_dcolors, dL_dconic) -- then the camera pass for the camera inputs that need a gradient (they are the inputs
+    first_camera_slot .. + 2 of the function) -> (native's result, the three camera slots).  **model: camera_backward's
+    model arguments."""
+    rs = ctx.raster_settings
+    got = tuple(_call_native(native, args, rs.debug, "snapshot_bw.dump"))
+    needs = ctx.needs_input_grad[first_camera_slot:first_camera_slot + 3]
+    want = tuple(n for n, need in zip(_C.CAMERA_GRADS, needs) if need)
+    cam = {}
+    if want:
+        cam = _C.camera_backward(scale_modifier=rs.scale_modifier, raw_params=raw, viewmatrix=rs.viewmatrix, projmatrix=rs.projmatrix,
+                                 campos=rs.campos, tanfovx=rs.tanfovx, tanfovy=rs.tanfovy, image_height=rs.image_height,
+                                 image_width=rs.image_width, dL_dmeans2D=got[0], dL_dcolors=got[-2], dL_dconic=got[-1], want=want,
+                                 **model)
+    return got, tuple(cam.get(n) for n in _C.CAMERA_GRADS)
+
+
+class _RasterizeGaussiansCam(torch.autograd.Function):
+    """_RasterizeGaussians with the camera differentiable.  Inputs: those of _RasterizeGaussians, then viewmatrix [4,4],
+    projmatrix [4,4], campos [3] -- the tensors of raster_settings, handed in as arguments so that autograd sees them.
+    The forward is the same native call; the backward is the same native backward, asked for its per-Gaussian dL_dconic as
+    well, followed by `_C.camera_backward` for the camera tensors that need a gradient.  The three are independent inputs:
+    what ties them together (a pose) is chained by autograd outside (r3dgs_camera.RefinedCamera)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, degrees, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, lambda_sh_sparsity, viewmatrix, projmatrix, campos):
+        rs = _cam_settings(raster_settings, means3D.device, viewmatrix, projmatrix, campos)
+        args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, degrees,
+                rs.campos, rs.prefiltered, rs.debug)
+        return _cam_forward(ctx, _C.rasterize_gaussians, args, rs, lambda_sh_sparsity,
+                            lambda radii, geom, binning, img: (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii,
+                                                               sh, geom, binning, img, degrees))
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii):
+        rs = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
+         degrees) = ctx.saved_tensors
+        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, _cam_upstream(rs, grad_out_color, means3D), sh, degrees,
+                rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
+
+        def native(*a):   # -> the eight gradients, then (dL_dcolors again, dL_dconic); an empty model has no conic rows
+            out = tuple(_C.rasterize_gaussians_backward(*a, _want_conic=True))
+            return out[:8] + (out[1], out[8] if len(out) == 9 else None)
+        got, cam = _cam_backward(ctx, 11, native, args, False, means3D=means3D, degrees=degrees,
+                                 sh=None if colors_precomp.numel() else sh, sh_rest=None, scales=scales, rotations=rotations,
+                                 cov3D_precomp=cov3Ds_precomp, radii=radii, geomBuffer=geomBuffer)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations) = got[:8]
+        return (grad_means3D, grad_means2D, grad_sh, None, grad_colors_precomp, grad_opacities, grad_scales,
+                grad_rotations, grad_cov3Ds_precomp, None, None) + cam
+
+
+class _RasterizeGaussianParamsCam(torch.autograd.Function):
+    """_RasterizeGaussianParams with the camera differentiable: its inputs, then viewmatrix, projmatrix, campos (see
+    _RasterizeGaussiansCam).  The per-Gaussian kernel of the camera pass activates the raw scaling / rotation itself."""
+
+    @staticmethod
+    def forward(ctx, xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation, raster_settings,
+                lambda_sh_sparsity, viewmatrix, projmatrix, campos):
+        rs = _cam_settings(raster_settings, xyz.device, viewmatrix, projmatrix, campos)
+        args = (rs.bg, xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
+                rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.campos, rs.prefiltered, rs.debug)
+        return _cam_forward(ctx, _C.rasterize_gaussian_params, args, rs, lambda_sh_sparsity,
+                            lambda radii, geom, binning, img: (xyz, features_dc, features_rest, degrees, opacity, scaling, rotation,
+                                                               radii, geom, binning, img))
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii):
+        rs = ctx.raster_settings
+        (xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, radii, geomBuffer, binningBuffer,
+         imgBuffer) = ctx.saved_tensors
+        args = (rs.bg, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, _cam_upstream(rs, grad_out_color, xyz), rs.campos, geomBuffer,
+                ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
+        no_rest = features_rest.numel() == 0
+        got, cam = _cam_backward(ctx, 10, lambda *a: _C.rasterize_gaussian_params_backward(*a, _want_2d=True), args, True,
+                                 means3D=xyz, degrees=degrees, sh=features_dc, sh_rest=None if no_rest else features_rest,
+                                 scales=scaling, rotations=rotation, cov3D_precomp=None, radii=radii, geomBuffer=geomBuffer)
+        grad_means2D, grad_opacity, grad_xyz, grad_dc, grad_rest, grad_scaling, grad_rotation = got[:7]
+        return (grad_xyz, grad_means2D, grad_dc, None if no_rest else grad_rest, None, grad_opacity, grad_scaling, grad_rotation,
+                None, None) + cam
 
 
 def aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer,
@@ -246,5 +379,9 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        rs = self.raster_settings
+        if _camera_requires_grad(rs):   # a camera tensor asks for a gradient: the camera-differentiable function
+            return _RasterizeGaussiansCam.apply(means3D, means2D, shs, degrees, colors_precomp, opacities, scales, rotations,
+                                                cov3D_precomp, rs, lambda_sh_sparsity, rs.viewmatrix, rs.projmatrix, rs.campos)
         return rasterize_gaussians(means3D, means2D, shs, degrees, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings, lambda_sh_sparsity)

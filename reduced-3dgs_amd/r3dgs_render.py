@@ -31,6 +31,13 @@ r3dgs_aux_maps_backward over the forward's state; its gradients add to those of 
 "viewspace_points".grad receives both.  On the raw-parameter route and for a QuantisedModel the activated scales and rotations
 the function takes are built in torch (pc.get_scaling / pc.get_rotation) only in this case, so torch carries the gradient
 through exp / normalize and the decode.  "median_depth" hands its gradient to the depth of the Gaussian it selected.
+
+Camera gradients.  A camera whose world_view_transform, full_proj_transform or camera_center is a tensor that requires grad
+(r3dgs_camera.RefinedCamera builds such a camera from a 6-parameter pose correction) makes "render" differentiable with respect
+to those tensors too, on the raw-parameter route and on the activated one: the backward runs one more pass over the Gaussians
+(include/r3dgs_camera.h) and autograd chains the three partial derivatives through whatever ties the tensors together.  Refused
+with a ValueError: a QuantisedModel, and aux_grad=True (the maps' share of a pose gradient is out of scope).  tan_fov / the focal
+length is not differentiated.
 """
 import functools
 import inspect
@@ -62,6 +69,15 @@ def _settings(camera, pc, pipe, bg_color, scaling_modifier):
         tanfovx=math.tan(camera.FoVx * 0.5), tanfovy=math.tan(camera.FoVy * 0.5), bg=bg_color,
         scale_modifier=scaling_modifier, viewmatrix=camera.world_view_transform, projmatrix=camera.full_proj_transform,
         sh_degree=pc.active_sh_degree, campos=camera.camera_center, prefiltered=False, debug=bool(pipe.debug))
+
+
+def camera_requires_grad(camera):
+    """True when, under grad mode, one of the camera's world_view_transform / full_proj_transform / camera_center is a tensor
+    that requires grad: render() then differentiates the image with respect to them as well (the module's docstring)."""
+    if camera is None or not torch.is_grad_enabled():
+        return False
+    return any(isinstance(t, torch.Tensor) and t.requires_grad
+               for t in (getattr(camera, n, None) for n in ("world_view_transform", "full_proj_transform", "camera_center")))
 
 
 def fused_path_applies(pc, pipe, override_color=None, variable_sh_bands=False):
@@ -210,6 +226,22 @@ _render = render   # the reference's signature, parameter for parameter (tests/t
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
     aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
+    camera = args[0] if args else kwargs.get("viewpoint_camera")
+    if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
+        camera = camera.snapshot()                    # built once for this render
+        if args:
+            args = (camera,) + tuple(args[1:])
+        else:
+            kwargs["viewpoint_camera"] = camera
+    if camera_requires_grad(camera):   # (before anything is launched)
+        pc = args[1] if len(args) > 1 else kwargs.get("pc")
+        if isinstance(pc, QuantisedModel):
+            raise ValueError("render: camera gradients are not available for a QuantisedModel (its forward reads ids and "
+                             "codebooks; no backward of it writes the per-Gaussian sums they are formed from); decode() it and "
+                             "render the dense tensors")
+        if aux_grad:
+            raise ValueError("render: aux_grad=True together with a camera that requires grad is not supported: the maps' "
+                             "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera)")
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
         if aux_grad:
             raise ValueError("render: aux_grad=True without aux: name the maps the loss is put on")
