@@ -44,6 +44,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "aux_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # gradients through those maps: the backward blend's step replayed, so the blend's flags again
     "aux_bwd.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # per-Gaussian feature maps and their gradients: both blends' steps replayed over C channels, so the blend's flags
+    "feature_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's

@@ -102,6 +102,11 @@ _ABI = {
         "r3dgs_aux_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_aux_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # 3 upstream, 6 outputs
+        # include/r3dgs_features.h
+        "r3dgs_feature_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+        "r3dgs_feature_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+        "r3dgs_feature_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
+                                             _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # features .. 7 outputs
         # include/r3dgs_camera.h
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
@@ -1240,6 +1245,91 @@ def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewma
             P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
             float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(ups[0]), _ptr(ups[1]),
             _ptr(ups[2]), *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "aux_maps_backward")
+    return out
+
+
+FEATURE_MAX_CHANNELS = 512   # R3DGS_FEATURE_MAX_CHANNELS (include/r3dgs_features.h)
+FEATURE_GRADS = ("features",) + AUX_GRADS
+
+
+def _feature_tensor(features, P, dev, what):
+    """`features` as the library reads it: float32 [P, C] on `dev`, contiguous (copied if it is not); refused otherwise."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != P:
+        shape = tuple(features.shape) if isinstance(features, torch.Tensor) else type(features).__name__
+        raise ValueError(f"{what}: features must be a [P, C] tensor with P = {P}, got {shape}")
+    C_ = int(features.shape[1])
+    if not 1 <= C_ <= FEATURE_MAX_CHANNELS:
+        raise ValueError(f"{what}: need 1 <= C <= {FEATURE_MAX_CHANNELS} feature channels, got C = {C_}")
+    if features.dtype != torch.float32:
+        raise ValueError(f"{what}: features must be float32, got {str(features.dtype)[6:]}")
+    if P and dev is not None and features.device != dev:
+        raise ValueError(f"{what}: features must live on {dev}, got {features.device}")
+    return features.detach().contiguous(), C_
+
+
+def feature_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, features):
+    """r3dgs_feature_maps (include/r3dgs_features.h) over the three buffers a forward returned: features float32 [P, C] ->
+    float [C, H, W], out[c] = sum over the blended Gaussians of features[id, c] * alpha * T (not normalised, no background
+    term).  R: the forward's num_rendered (a NumRendered) or the pair capacity of its binning buffer.  The buffers are only
+    read; the map carries no gradient."""
+    P, H, W = int(P), int(H), int(W)
+    feats, C_ = _feature_tensor(features, P, None, "feature_maps")
+    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if dev.type != "cuda":
+        dev = features.device if features.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    _feature_tensor(features, P, dev, "feature_maps")
+    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
+        raise RuntimeError("feature_maps: the three state buffers must live on one device")
+    out = torch.empty((C_, H, W), dtype=torch.float32, device=dev)
+    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
+    with _on_device(dev):
+        _check(_lib.r3dgs_feature_maps(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(feats),
+                                       C_, out.data_ptr(), _stream()), "feature_maps")
+    return out
+
+
+def feature_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
+                          scales, scale_modifier, rotations, cov3D_precomp, radii, features, dL_dout, want=FEATURE_GRADS):
+    """r3dgs_feature_maps_backward (include/r3dgs_features.h): dL_dout (C*H*W elements, None = zero) -> {name: float [P, cols]}
+    for the names in `want` (a subset of FEATURE_GRADS): "features" [P, C] and the geometry gradients of aux_maps_backward, in
+    its units.  With only "features" wanted the geometry is frozen: the geometric sums and the per-Gaussian chain are skipped and
+    viewmatrix .. cov3D_precomp may be None.  The buffers are only read; the workspace is allocated here, per call, from
+    torch's caching allocator."""
+    want = tuple(want)
+    for name in want:
+        if name not in FEATURE_GRADS:
+            raise ValueError(f"feature_maps_backward: unknown gradient {name!r} (expected a subset of {FEATURE_GRADS})")
+    P, H, W = int(P), int(H), int(W)
+    dev = features.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if dev.type != "cuda":
+        dev = torch.device("cuda", torch.cuda.current_device())
+    feats, C_ = _feature_tensor(features, P, dev, "feature_maps_backward")
+    g = _dev(dL_dout, dev)
+    if g is not None and g.numel() != C_ * H * W:
+        raise RuntimeError(f"feature_maps_backward: dL_dout has {g.numel()} elements, the map {C_ * H * W}")
+    cols = dict(_AUX_GRAD_COLS, features=C_)
+    out = {name: torch.empty((P, cols[name]), dtype=torch.float32, device=dev) for name in want}
+    if P == 0:
+        return out
+    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
+        raise RuntimeError("feature_maps_backward: the state buffers and the features must live on one device")
+    m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
+    rad = _dev(radii, dev, torch.int32)
+    vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
+    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
+    with _on_device(dev):
+        nbytes = _lib.r3dgs_feature_maps_backward_workspace_bytes(P, cap, C_, W, H)
+        if nbytes == 0 and cap:
+            _check(-1, "feature_maps_backward_workspace_bytes")
+        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_feature_maps_backward(
+            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
+            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(feats), C_, _ptr(g),
+            *[_ptr(out.get(name)) for name in FEATURE_GRADS], work.data_ptr(), _stream()), "feature_maps_backward")
     return out
 
 

@@ -354,6 +354,61 @@ def aux_maps_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_pre
     return dict(zip(maps, got))
 
 
+def feature_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, features):
+    """A per-Gaussian feature vector blended into a map, replayed from the three buffers a forward returned: features float32
+    [P, C] -> float [C, H, W], map[c] = sum over the blended Gaussians of features[id, c] * alpha * T (fp32, list order).  Not
+    normalised, no background term: divide by the "alpha" map of `aux_maps` for a mean.  One kernel launch, no host wait; the
+    buffers are only read, so a backward over them afterwards is unaffected.  The map is detached (`feature_maps_with_grad`
+    carries gradients)."""
+    with torch.no_grad():
+        return _C.feature_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, features)
+
+
+def feature_maps_backward(*args, **kwargs):
+    """Thin wrapper of `_C.feature_maps_backward` (include/r3dgs_features.h r3dgs_feature_maps_backward)."""
+    with torch.no_grad():
+        return _C.feature_maps_backward(*args, **kwargs)
+
+
+class _FeatureMaps(torch.autograd.Function):
+    """`feature_maps` with gradients.  Inputs: features [P, C], then the model's tensors as `_AuxMaps` takes them -- means3D,
+    means2D, opacities (raw), scales (activated), rotations (unit), cov3D_precomp (or an empty tensor); pass tensors that do
+    not require grad (detached) for a frozen geometry -- then without gradient: the forward's six-tuple `state` and
+    raster_settings  ->  the [C, H, W] map.  The backward is one `feature_maps_backward` over the saved buffers, asked only
+    for the gradients autograd wants."""
+
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings):
+        rs = raster_settings
+        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
+        out = _C.feature_maps(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer,
+                              imgBuffer, features)
+        ctx.raster_settings, ctx.num_rendered = rs, num_rendered
+        ctx.save_for_backward(features, means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rs = ctx.raster_settings
+        features, means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors
+        names = ("features", "means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
+        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:7]) if need)
+        got = _C.feature_maps_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
+                                       binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D,
+                                       scales, rs.scale_modifier, rotations, cov3D_precomp, radii, features, grad_out, want=want)
+        return tuple(got.get(n) for n in names) + (None, None)
+
+
+def feature_maps_with_grad(features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings):
+    """The map of `feature_maps` ATTACHED to `features` and to whichever of the model's tensors require grad -> float
+    [C, H, W].  `state`: the six-tuple the forward returned (what `_C.forward_state()` records); scales / rotations: the
+    activated values the forward saw (or cov3D_precomp); means2D: the screen-space tensor whose .grad densification reads."""
+    empty = torch.Tensor([])
+    return _FeatureMaps.apply(features, means3D, means2D, opacities, empty if scales is None else scales,
+                              empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
+                              state, raster_settings)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

@@ -38,6 +38,16 @@ to those tensors too, on the raw-parameter route and on the activated one: the b
 (include/r3dgs_camera.h) and autograd chains the three partial derivatives through whatever ties the tensors together.  Refused
 with a ValueError: a QuantisedModel, and aux_grad=True (the maps' share of a pose gradient is out of scope).  tan_fov / the focal
 length is not differentiated.
+
+`features=F` (float32 [P, C] on the model's device, 1 <= C <= _C.FEATURE_MAX_CHANNELS; a non-contiguous F is made contiguous)
+adds the key "features": the [C,H,W] map sum F[id] alpha T over the blended Gaussians (include/r3dgs_features.h) -- not
+normalised and without a background term, like "depth".  One extra launch on the forward's state instead of ceil(C / 3) renders
+with colors_precomp = F[:, c:c+3].  If F requires grad the map is attached to F (diff_gaussian_rasterization._FeatureMaps; the
+geometry stays frozen and the backward skips its sums); `features_geom_grad=True` attaches it to the model's geometry as well,
+and those gradients add to the colour backward's through autograd ("viewspace_points".grad receives both).  `pc` may be a
+QuantisedModel.  Refused with a ValueError: features_geom_grad=True for a QuantisedModel, together with a camera that requires
+grad, or under no_grad; an F of the wrong shape, dtype, device or channel count.  `features` combines freely with `aux` /
+`aux_grad`; features=None (the default): the same dictionary, no extra launch, no recorder.
 """
 import functools
 import inspect
@@ -47,7 +57,7 @@ import threading
 import torch
 
 from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps, aux_maps_with_grad,
-                                         rasterize_gaussian_params)
+                                         feature_maps, feature_maps_with_grad, rasterize_gaussian_params)
 from r3dgs_quantised import QuantisedModel
 
 # render(aux_grad=True) asks the call it wraps for the tensors its forward was fed: a dictionary here, for the duration of that
@@ -223,9 +233,54 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
 _render = render   # the reference's signature, parameter for parameter (tests/test_params_cpu.py holds it to the reference's source)
 
 
+def _checked_features(features, pc, features_geom_grad, camera):
+    """The refusals of render(features=...), before anything is launched."""
+    P = int(pc.P) if isinstance(pc, QuantisedModel) else int(pc._xyz.shape[0])
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != P:
+        shape = tuple(features.shape) if isinstance(features, torch.Tensor) else type(features).__name__
+        raise ValueError(f"render: features must be a [P, C] tensor with P = {P} rows (one per Gaussian), got {shape}")
+    if not 1 <= features.shape[1] <= _C.FEATURE_MAX_CHANNELS:
+        raise ValueError(f"render: features needs 1 <= C <= {_C.FEATURE_MAX_CHANNELS} channels, got C = {features.shape[1]}")
+    if features.dtype != torch.float32:
+        raise ValueError(f"render: features must be float32, got {str(features.dtype)[6:]}")
+    where = pc.xyz.device if isinstance(pc, QuantisedModel) else pc._xyz.device
+    if features.device.type != "cuda" or features.device != where:
+        raise ValueError(f"render: features must live on the model's device ({where}), got {features.device}")
+    if features_geom_grad:
+        if isinstance(pc, QuantisedModel):
+            raise ValueError("render: features_geom_grad=True is not available for a QuantisedModel (geometry gradients of its "
+                             "codebooks through the feature map are out of scope); its features alone can be trained")
+        if camera_requires_grad(camera):
+            raise ValueError("render: features_geom_grad=True together with a camera that requires grad is not supported: the "
+                             "feature map's share of a pose gradient is out of scope")
+        if not torch.is_grad_enabled():
+            raise ValueError("render: features_geom_grad=True under no_grad: there is no graph to attach the map to")
+
+
+def _feature_map(features, camera, out, state, rs, inputs=None):
+    """The "features" entry of the result: [C,H,W] from the six-tuple `state` of the forward that produced `out` (None: an empty
+    model -- a zero map), attached to `features` when it requires grad and, with `inputs` (means3D, opacities, scales,
+    rotations, cov3D_precomp), to the model's geometry as well."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    attach = torch.is_grad_enabled() and (features.requires_grad or inputs is not None)
+    if state is None:
+        zero = torch.zeros((features.shape[1], H, W), dtype=torch.float32, device=out["render"].device)
+        return zero + 0.0 * features.sum() if attach and features.requires_grad else zero
+    if not attach:
+        num_rendered, _, radii, geom, binning, img = state
+        return feature_maps(int(radii.numel()), num_rendered, H, W, geom, binning, img, features)
+    if inputs is None:   # frozen geometry: the backward skips the geometric sums and reads none of the model's tensors
+        empty = torch.Tensor([])
+        return feature_maps_with_grad(features, empty, empty, empty, None, None, None, state, rs)
+    means3D, opacities, scales, rotations, cov3D = inputs
+    return feature_maps_with_grad(features, means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs)
+
+
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
     aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
+    features = kwargs.pop("features", None)          # likewise: the [P, C] tensor of the "features" map; default: no such key
+    features_geom_grad = bool(kwargs.pop("features_geom_grad", False))
     camera = args[0] if args else kwargs.get("viewpoint_camera")
     if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
         camera = camera.snapshot()                    # built once for this render
@@ -242,10 +297,14 @@ def render(*args, aux=None, **kwargs):
         if aux_grad:
             raise ValueError("render: aux_grad=True together with a camera that requires grad is not supported: the maps' "
                              "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera)")
+    if features is None and features_geom_grad:
+        raise ValueError("render: features_geom_grad=True without features: pass the [P, C] tensor the map is blended from")
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
         if aux_grad:
             raise ValueError("render: aux_grad=True without aux: name the maps the loss is put on")
-        return _render(*args, **kwargs)
+        if features is None:
+            return _render(*args, **kwargs)
+        aux = ()
     aux = tuple(aux)
     for name in aux:
         if name not in _C.AUX_MAPS:
@@ -253,15 +312,21 @@ def render(*args, aux=None, **kwargs):
     if aux_grad and not torch.is_grad_enabled():
         raise ValueError("render: aux_grad=True under no_grad: there is no graph to attach the maps to")
     camera = args[0] if args else kwargs["viewpoint_camera"]
-    if not aux_grad:
-        with _C.forward_state() as st:
-            out = _render(*args, **kwargs)
-        return _with_aux(aux, camera, out, st.result)
     a = inspect.signature(_render).bind(*args, **kwargs)
     a.apply_defaults()
     a = a.arguments
     pc, pipe = a["pc"], a["pipe"]
-    if isinstance(pc, QuantisedModel) and not pc.trainable:   # (before anything is launched)
+    if features is not None:   # (before anything is launched)
+        _checked_features(features, pc, features_geom_grad, camera)
+    if not aux_grad and not features_geom_grad:
+        with _C.forward_state() as st:
+            out = _render(*args, **kwargs)
+        out = _with_aux(aux, camera, out, st.result)
+        if features is not None:
+            out["features"] = _feature_map(features, camera, out, st.result,
+                                           _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"]))
+        return out
+    if aux_grad and isinstance(pc, QuantisedModel) and not pc.trainable:   # (before anything is launched)
         raise ValueError("render: aux_grad=True needs a trainable model (requires_grad_ the QuantisedModel first)")
     _tls.inputs = got = {}
     try:
@@ -271,12 +336,16 @@ def render(*args, aux=None, **kwargs):
         _tls.inputs = None
     means3D, opacities, scales, rotations, cov3D = got["inputs"]
     if not any(t is not None and t.requires_grad for t in got["inputs"]):
-        raise ValueError("render: aux_grad=True for a model with nothing trainable")
+        raise ValueError(f"render: {'aux_grad' if aux_grad else 'features_geom_grad'}=True for a model with nothing trainable")
+    rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
+    if features is not None:
+        out["features"] = _feature_map(features, camera, out, st.result, rs, got["inputs"] if features_geom_grad else None)
+    if not aux_grad:
+        return _with_aux(aux, camera, out, st.result)
     if st.result is None:   # an empty model: nothing was rendered -- zero maps, attached all the same (a backward through
         out = _with_aux(aux, camera, out, None)   # them is valid and leaves zero gradients)
         anchor = 0.0 * sum(t.sum() for t in got["inputs"] if t is not None and t.requires_grad)
         out.update({name: out[name] + anchor for name in aux})
         return out
-    rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
     out.update(aux_maps_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, st.result, rs, maps=aux))
     return out
