@@ -46,6 +46,9 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "aux_bwd.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # per-Gaussian feature maps and their gradients: both blends' steps replayed over C channels, so the blend's flags
     "feature_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # per-Gaussian blend-contribution scores: the forward blend's step replayed (its T and last contributor are held to the
+    # forward's bit for bit), so the blend's flags
+    "importance.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's
@@ -121,7 +124,8 @@ def build_torch_binding(force=False, verbose=True):
 
     import torch
     hdrs = [os.path.join(HERE, "..", "include", h) for h in ("r3dgs_rasterizer.h", "r3dgs_loss.h", "r3dgs_optim.h",
-                                                               "r3dgs_trainstats.h", "r3dgs_quantised.h", "r3dgs_aux.h")]
+                                                               "r3dgs_trainstats.h", "r3dgs_quantised.h", "r3dgs_aux.h",
+                                                               "r3dgs_importance.h")]
     if not force and os.path.exists(TORCH_EXT_OUT) and os.path.getmtime(TORCH_EXT_OUT) >= max(
             [os.path.getmtime(TORCH_EXT_SRC), os.path.getmtime(torch.__file__)] + [os.path.getmtime(h) for h in hdrs]):
         return TORCH_EXT_OUT

@@ -25,6 +25,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include <limits>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "r3dgs_aux.h"
+#include "r3dgs_importance.h"
 #include "r3dgs_loss.h"
 #include "r3dgs_optim.h"
 #include "r3dgs_quantised.h"
@@ -63,6 +65,8 @@ using at::Tensor;
     X(r3dgs_aux_maps, true)                                   \
     X(r3dgs_aux_maps_backward_workspace_bytes, true)          \
     X(r3dgs_aux_maps_backward, true)                          \
+    X(r3dgs_contribution_scores_workspace_bytes, true)        \
+    X(r3dgs_contribution_scores, true)                        \
     X(r3dgs_l1_ssim_workspace_bytes, false)                   \
     X(r3dgs_l1_ssim_forward, false)                           \
     X(r3dgs_l1_ssim_backward, false)                          \
@@ -486,6 +490,43 @@ std::vector<Tensor> aux_maps(int64_t P, int64_t capacity, int64_t image_height, 
     return {depth, alpha, median, T_check, n_check};
 }
 
+// r3dgs_contribution_scores over the three buffers a forward returned, into the caller's [P] tensors in place (an empty
+// tensor: not computed; _C.py has checked devices, dtypes, sizes and contiguity: nothing is copied) -> (T_check [H,W],
+// n_check int32 [H,W]), undefined unless asked for.  `capacity`: as backward's.
+std::vector<Tensor> contribution_scores(int64_t P, int64_t capacity, int64_t image_height, int64_t image_width,
+                                        const Tensor& geomBuffer, const Tensor& binningBuffer, const Tensor& imageBuffer,
+                                        const Tensor& pixel_weight, const Tensor& score_sum, const Tensor& score_max,
+                                        const Tensor& score_count, const Tensor& score_views, bool accumulate, bool want_checks)
+{
+    need_bound();
+    c10::Device dev = imageBuffer.defined() && imageBuffer.numel() ? imageBuffer.device() : geomBuffer.device();
+    if (P != 0) {
+        if (!dev.is_cuda()) throw std::runtime_error("the MI355X rasterizer needs device tensors (no CPU path)");
+    } else if (!dev.is_cuda()) {   // nothing says where: the current device, as the forward's empty result
+        dev = c10::Device(c10::DeviceType::CUDA, c10::hip::current_device());
+    }
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    const int H = (int)image_height, W = (int)image_width;
+    Tensor T_check, n_check;
+    if (want_checks) {
+        T_check = at::empty({H, W}, f32);
+        n_check = at::empty({H, W}, f32.dtype(at::kInt));
+    }
+    const size_t nbytes = api.r3dgs_contribution_scores_workspace_bytes((int)P, (int)capacity, W, H);
+    if (nbytes == 0 && P != 0 && capacity != 0) fail("contribution_scores_workspace_bytes");
+    const Tensor work = at::empty({(int64_t)std::max<size_t>(nbytes, 1)}, f32.dtype(at::kByte));
+    auto ptr = [](const Tensor& t) { return t.defined() && t.numel() != 0 ? t.data_ptr() : nullptr; };
+    if (api.r3dgs_contribution_scores((int)P, (int)capacity, W, H, blob_ptr(geomBuffer), blob_ptr(binningBuffer),
+                                      blob_ptr(imageBuffer), static_cast<const float*>(ptr(pixel_weight)),
+                                      static_cast<double*>(ptr(score_sum)), static_cast<float*>(ptr(score_max)),
+                                      static_cast<long long*>(ptr(score_count)), static_cast<int*>(ptr(score_views)),
+                                      accumulate ? 1 : 0, static_cast<float*>(ptr(T_check)), static_cast<unsigned*>(ptr(n_check)),
+                                      blob_ptr(work), cur_stream(dev)) < 0)
+        fail("contribution_scores");
+    return {T_check, n_check};
+}
+
 // -> (scales [P,3], rotations [P,4]) by csrc/param_math.h, the values the raw-parameter kernels use
 std::tuple<Tensor, Tensor> activate_params(const Tensor& scaling, const Tensor& rotation)
 {
@@ -818,6 +859,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("backward", &backward);
     m.def("mark_visible", &mark_visible);
     m.def("aux_maps", &aux_maps);
+    m.def("contribution_scores", &contribution_scores);
     m.def("forward_params", &forward_params);
     m.def("forward_params_reserved", &forward_params_reserved);
     m.def("backward_params", &backward_params);

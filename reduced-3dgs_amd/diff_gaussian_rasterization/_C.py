@@ -107,6 +107,9 @@ _ABI = {
         "r3dgs_feature_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
         "r3dgs_feature_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                              _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # features .. 7 outputs
+        # include/r3dgs_importance.h
+        "r3dgs_contribution_scores_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_contribution_scores": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
         # include/r3dgs_camera.h
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
@@ -1331,6 +1334,86 @@ def feature_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, vi
             float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(feats), C_, _ptr(g),
             *[_ptr(out.get(name)) for name in FEATURE_GRADS], work.data_ptr(), _stream()), "feature_maps_backward")
     return out
+
+
+SCORES = ("sum", "max", "count", "views")
+_SCORE_DTYPES = dict(sum=torch.float64, max=torch.float32, count=torch.int64, views=torch.int32)
+
+
+def _score_tensor(t, dev, name, numel, dtype):
+    """An input or output of contribution_scores as the library takes it, in place: refused instead of converted or copied."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"contribution_scores: {name} must be a tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"contribution_scores: {name} must be a device tensor (no CPU path), got {t.device}")
+    if dev is not None and t.device != dev:
+        raise RuntimeError(f"contribution_scores: {name} must live on {dev}, got {t.device}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"contribution_scores: {name} must be {str(dtype)[6:]}, got {str(t.dtype)[6:]}")
+    if t.numel() != numel:
+        raise RuntimeError(f"contribution_scores: {name} has {t.numel()} elements, expected {numel}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"contribution_scores: {name} must be contiguous (it is written and read in place, never copied)")
+    return t
+
+
+def contribution_scores(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, pixel_weight=None, out=None, accumulate=False,
+                        checks=False):
+    """r3dgs_contribution_scores (include/r3dgs_importance.h) over the three buffers a forward returned -> {name: tensor [P]}:
+    "sum" (float64) of pixel_weight * alpha * T over the pixels that blend a Gaussian, "max" (float32) of alpha * T, "count"
+    (int64) of those pixels, "views" (int32) = count > 0.  pixel_weight: float32 of H*W elements or None (ones); a pixel of
+    weight 0 is left out of all four.  out: None (all four, allocated here) or a dict of any of the four names to [P] tensors
+    that are written in place -- the names it lacks are not computed.  accumulate: fold the view into what `out` holds instead
+    of overwriting it.  R: the forward's num_rendered (a NumRendered) or the pair capacity of its binning buffer.
+    checks=True adds "T_check" (float [H,W]) and "n_check" (int32 [H,W]): the walk's own final T and last contributor.
+    Host, non-contiguous and wrong-dtype tensors are refused, nothing is copied; the buffers are only read; the workspace is
+    allocated here, per call, from torch's caching allocator."""
+    P, H, W = int(P), int(H), int(W)
+    if P < 0 or H < 1 or W < 1:
+        raise ValueError(f"contribution_scores: need P >= 0 and H, W >= 1, got P = {P}, {W}x{H}")
+    dev = None
+    for t in (imageBuffer, geomBuffer, pixel_weight, *(out.values() if isinstance(out, dict) else ())):
+        if isinstance(t, torch.Tensor) and t.numel() and t.device.type == "cuda":
+            dev = t.device
+            break
+    if P and (dev is None or imageBuffer.device.type != "cuda"):
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if out is not None:
+        if not isinstance(out, dict) or any(name not in SCORES for name in out):
+            raise ValueError(f"contribution_scores: out must be a dict with names among {SCORES}")
+        for name, t in out.items():
+            _score_tensor(t, dev, name, P, _SCORE_DTYPES[name])
+    elif accumulate:
+        raise ValueError("contribution_scores: accumulate needs the buffers to fold into (out=...)")
+    if pixel_weight is not None:
+        _score_tensor(pixel_weight, dev, "pixel_weight", H * W, torch.float32)
+    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
+        raise RuntimeError("contribution_scores: the state buffers, the weights and the outputs must live on one device")
+    if dev is None:   # P == 0 and nothing says where: the current device, as the forward's empty result
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = {name: torch.empty(P, dtype=_SCORE_DTYPES[name], device=dev) for name in SCORES}
+    cap = int(_pair_capacity(R, P, W, H, binningBuffer)) if P else 0
+    res = dict(out)
+    if _ext is not None:
+        got = _ext.contribution_scores(P, cap, H, W, geomBuffer, binningBuffer, imageBuffer, _t(pixel_weight),
+                                       *[_t(out.get(name)) for name in SCORES], bool(accumulate), bool(checks))
+        if checks:
+            res["T_check"], res["n_check"] = got
+        return res
+    if checks:
+        res["T_check"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+        res["n_check"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        nbytes = _lib.r3dgs_contribution_scores_workspace_bytes(P, cap, W, H)
+        if nbytes == 0 and P and cap:
+            _check(-1, "contribution_scores_workspace_bytes")
+        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_contribution_scores(
+            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(pixel_weight),
+            *[_ptr(out.get(name)) for name in SCORES], int(bool(accumulate)), _ptr(res.get("T_check")), _ptr(res.get("n_check")),
+            work.data_ptr(), _stream()), "contribution_scores")
+    return res
 
 
 CAMERA_GRADS = ("viewmatrix", "projmatrix", "campos")

@@ -303,6 +303,37 @@ def aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuff
         return _C.aux_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, maps=maps)
 
 
+class Scores(NamedTuple):
+    """Per-Gaussian blend-contribution scores, each [P]: `sum` (float64) of pixel_weight * alpha * T over the pixels that blend
+    the Gaussian, `max` (float32) of alpha * T, `count` (int64) of those pixels, `views` (int32) of the views with count > 0."""
+    sum: torch.Tensor
+    max: torch.Tensor
+    count: torch.Tensor
+    views: torch.Tensor
+
+
+def new_scores(P, device):
+    """Zeroed buffers for `contribution_scores(..., out=..., accumulate=True)`."""
+    return Scores(*(torch.zeros(int(P), dtype=_C._SCORE_DTYPES[name], device=device) for name in _C.SCORES))
+
+
+def contribution_scores(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, pixel_weight=None,
+                        out=None, accumulate=False):
+    """How much each Gaussian contributed to the pixels of the view whose forward left the three buffers (include/
+    r3dgs_importance.h) -> Scores.  pixel_weight: float32 [H, W] on the device or None (ones); a pixel of weight 0 is left out
+    of every score, so a 0/1 map is a region of interest and an error map weights the sum.  out: a Scores to write in place
+    (None: a new one); accumulate=True folds the view into it (sum and count add, max is the maximum, views counts the views
+    that saw the Gaussian) instead of overwriting it.  No host wait, no float atomics, the same bits from run to run; the
+    buffers are only read, so a backward over them afterwards is unaffected."""
+    if out is not None and not isinstance(out, Scores):
+        raise ValueError(f"contribution_scores: out must be a Scores, got {type(out).__name__}")
+    with torch.no_grad():
+        got = _C.contribution_scores(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer,
+                                     pixel_weight=pixel_weight, out=None if out is None else out._asdict(),
+                                     accumulate=accumulate)
+    return out if out is not None else Scores(*(got[name] for name in _C.SCORES))
+
+
 def aux_maps_backward(*args, **kwargs):
     """Thin wrapper of `_C.aux_maps_backward` (include/r3dgs_aux.h r3dgs_aux_maps_backward): the gradients of the maps of
     `aux_maps` with respect to the Gaussians, from upstream gradients of the maps, over the same three buffers."""
