@@ -62,6 +62,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "quant_grad.hip": EXACT,
     # densification: the decisions and the children's rows with the roundings densify_math.h names and no others
     "densify.hip": EXACT,
+    # 3DGS-MCMC relocation, growth and noise: the roundings mcmc_math.h names and no others
+    "mcmc.hip": EXACT,
     # camera gradients: the per-Gaussian backward's chain continued to the camera, so the per-Gaussian backward's flags
     "camera_bwd.hip": EXACT,
     "capi.hip": [],

@@ -43,6 +43,10 @@ class _DensifyTensor(C.Structure):   # r3dgs_densify_tensor (include/r3dgs_densi
     _fields_ = [("src", _vp), ("dst", _vp), ("row_words", _i), ("kind", _i)]
 
 
+class _McmcTensor(C.Structure):   # r3dgs_mcmc_tensor (include/r3dgs_mcmc.h), the same shape; filled by r3dgs_mcmc.py
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_words", _i), ("kind", _i)]
+
+
 # ---- the C ABI of libr3dgs_hip.so, once: {group: (sentence, {name: (restype, [argtypes])})}, a row for every prototype under
 # include/ (tests/test_abi_table.py holds names, arity and the kind of every parameter to the headers; the package itself never
 # reads them).  "required" is what every build of the library exports; each other group is a family an older A/B build loaded
@@ -110,6 +114,11 @@ _ABI = {
         # include/r3dgs_importance.h
         "r3dgs_contribution_scores_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_contribution_scores": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+        # include/r3dgs_mcmc.h; called by r3dgs_mcmc.py
+        "r3dgs_mcmc_workspace_bytes": (_sz, [_i, _i]),
+        "r3dgs_mcmc_noise": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
+        "r3dgs_mcmc_plan": (_i, [_i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_mcmc_move": (_i, [_i, _i, _i, _i, _f, _i, C.POINTER(_McmcTensor), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         # include/r3dgs_camera.h
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
