@@ -64,6 +64,9 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "densify.hip": EXACT,
     # 3DGS-MCMC relocation, growth and noise: the roundings mcmc_math.h names and no others
     "mcmc.hip": EXACT,
+    # anti-aliasing (2D opacity compensation, 3D filter): double chains rounded to fp32 once, decisions on the forward's own
+    # fp32 expressions -- so the forward's flags (no contraction, correctly rounded divide and sqrt)
+    "mip.hip": EXACT,
     # camera gradients: the per-Gaussian backward's chain continued to the camera, so the per-Gaussian backward's flags
     "camera_bwd.hip": EXACT,
     "capi.hip": [],

@@ -119,6 +119,14 @@ _ABI = {
         "r3dgs_mcmc_noise": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
         "r3dgs_mcmc_plan": (_i, [_i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_mcmc_move": (_i, [_i, _i, _i, _i, _f, _i, C.POINTER(_McmcTensor), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        # include/r3dgs_mip.h; called by r3dgs_mip.py
+        "r3dgs_mip_opacity": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _i, _f, _vp, _vp, _vp]),
+        "r3dgs_mip_opacity_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _i, _f, _vp,   # .. dL_draw_eff
+                                            _vp, _vp, _vp, _vp, _vp, _vp]),                                  # 5 outputs, stream
+        "r3dgs_mip_filter3d_workspace_bytes": (_sz, [_i, _i]),
+        "r3dgs_mip_filter3d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_mip_filtered": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_mip_filtered_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         # include/r3dgs_camera.h
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy

@@ -48,6 +48,16 @@ and those gradients add to the colour backward's through autograd ("viewspace_po
 QuantisedModel.  Refused with a ValueError: features_geom_grad=True for a QuantisedModel, together with a camera that requires
 grad, or under no_grad; an F of the wrong shape, dtype, device or channel count.  `features` combines freely with `aux` /
 `aux_grad`; features=None (the default): the same dictionary, no extra launch, no recorder.
+
+Anti-aliasing.  `antialiasing=True` multiplies every Gaussian's opacity by rho = sqrt(det C / det(C + 0.3 I)) of its projected
+covariance in this view (the official rasterizer's `antialiasing`, gsplat's "antialiased" mode with eps2d = 0.3 -- not
+Mip-Splatting's 0.1 kernel); `filter_3d=f` (float32 [P,1] from r3dgs_mip.filter_3d) applies Mip-Splatting's 3D smoothing filter
+to the scales and opacities.  Both are differentiable maps from raw parameters to raw parameters (r3dgs_mip,
+include/r3dgs_mip.h) placed in front of the unchanged rasterizer: the model is rendered through a thin view whose _scaling /
+_opacity are the filtered tensors -- the 3D filter first, the 2D compensation on its result -- and autograd composes the maps'
+backward with the rasterizer's.  Every route, `aux`, `aux_grad`, `features` and `features_geom_grad` work unchanged.  With both
+off (the default) nothing new is launched.  Refused with a ValueError: a QuantisedModel; filter_3d with
+pipe.compute_cov3D_python; antialiasing=True with a camera that requires grad; an f of the wrong shape, dtype or device.
 """
 import functools
 import inspect
@@ -276,11 +286,74 @@ def _feature_map(features, camera, out, state, rs, inputs=None):
     return feature_maps_with_grad(features, means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs)
 
 
+_SIGNATURE = inspect.signature(_render)
+
+
+class _FilteredModel:
+    """A thin view of a model whose _scaling / _opacity are the anti-aliased tensors: everything else is the model's own.
+    The activated getters follow the two tensors, so every route of render() -- all of them read RAW opacity -- sees them."""
+
+    def __init__(self, pc, scaling, opacity):
+        self.__dict__.update(_pc=pc, _scaling=scaling, _opacity=opacity)
+
+    def __getattr__(self, name):   # only reached for what the view does not hold itself
+        return getattr(self._pc, name)
+
+    @property
+    def get_scaling(self):
+        return torch.exp(self._scaling)
+
+    @property
+    def get_opacity(self):
+        return torch.sigmoid(self._opacity)
+
+
+def _checked_filter_3d(filter_3d, pc):
+    """The refusals of render(filter_3d=...): shape, dtype, device."""
+    P = int(pc._xyz.shape[0])
+    if not isinstance(filter_3d, torch.Tensor) or tuple(filter_3d.shape) != (P, 1):
+        shape = tuple(filter_3d.shape) if isinstance(filter_3d, torch.Tensor) else type(filter_3d).__name__
+        raise ValueError(f"render: filter_3d must be a [P, 1] tensor with P = {P} (r3dgs_mip.filter_3d), got {shape}")
+    if filter_3d.dtype != torch.float32:
+        raise ValueError(f"render: filter_3d must be float32, got {str(filter_3d.dtype)[6:]}")
+    if filter_3d.device.type != "cuda" or filter_3d.device != pc._xyz.device:
+        raise ValueError(f"render: filter_3d must live on the model's device ({pc._xyz.device}), got {filter_3d.device}")
+
+
+def _antialiased_model(camera, pc, pipe, bg_color, scaling_modifier, antialiasing, filter_3d):
+    """The model render(antialiasing=..., filter_3d=...) rasterizes: the refusals first (before anything is launched), then
+    the 3D filter on the raw parameters and the per-view 2D compensation on its result (r3dgs_mip)."""
+    import r3dgs_mip
+    if isinstance(pc, QuantisedModel):
+        raise ValueError("render: antialiasing / filter_3d are not available for a QuantisedModel (its opacity and scaling live "
+                         "in codebooks); decode() it and render the dense tensors")
+    if filter_3d is not None and pipe.compute_cov3D_python:
+        raise ValueError("render: filter_3d together with pipe.compute_cov3D_python is not supported (the model's own "
+                         "get_covariance would not see the filtered scaling)")
+    if antialiasing and camera_requires_grad(camera):
+        raise ValueError("render: antialiasing=True together with a camera that requires grad is not supported: rho depends on "
+                         "the view and its share of a pose gradient is out of scope")
+    if filter_3d is not None:
+        _checked_filter_3d(filter_3d, pc)
+    scaling, opacity = pc._scaling, pc._opacity
+    if filter_3d is not None:
+        scaling, opacity = r3dgs_mip.filtered_parameters(scaling, opacity, filter_3d)
+    if antialiasing:
+        rs = _settings(camera, pc, pipe, bg_color, scaling_modifier)
+        if pipe.compute_cov3D_python:
+            opacity = r3dgs_mip.antialias_opacity(pc.get_xyz, opacity, None, None, pc.get_covariance(scaling_modifier), rs)
+        else:
+            opacity = r3dgs_mip.antialias_opacity(pc._xyz, opacity, scaling, pc._rotation, None, rs, raw=True)
+    return _FilteredModel(pc, scaling, opacity)
+
+
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
     aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
     features = kwargs.pop("features", None)          # likewise: the [P, C] tensor of the "features" map; default: no such key
     features_geom_grad = bool(kwargs.pop("features_geom_grad", False))
+    antialiasing = bool(kwargs.pop("antialiasing", False))   # likewise: the two anti-aliasing filters (the module's docstring);
+    filter_3d = kwargs.pop("filter_3d", None)                # both off: today's path, nothing new is launched
     camera = args[0] if args else kwargs.get("viewpoint_camera")
     if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
         camera = camera.snapshot()                    # built once for this render
@@ -288,6 +361,12 @@ def render(*args, aux=None, **kwargs):
             args = (camera,) + tuple(args[1:])
         else:
             kwargs["viewpoint_camera"] = camera
+    if antialiasing or filter_3d is not None:
+        b = _SIGNATURE.bind(*args, **kwargs)
+        b.apply_defaults()
+        b.arguments["pc"] = _antialiased_model(camera, b.arguments["pc"], b.arguments["pipe"], b.arguments["bg_color"],
+                                               b.arguments["scaling_modifier"], antialiasing, filter_3d)
+        args, kwargs = b.args, b.kwargs
     if camera_requires_grad(camera):   # (before anything is launched)
         pc = args[1] if len(args) > 1 else kwargs.get("pc")
         if isinstance(pc, QuantisedModel):
