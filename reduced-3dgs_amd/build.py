@@ -67,6 +67,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     # anti-aliasing (2D opacity compensation, 3D filter): double chains rounded to fp32 once, decisions on the forward's own
     # fp32 expressions -- so the forward's flags (no contraction, correctly rounded divide and sqrt)
     "mip.hip": EXACT,
+    # surface normals (per-Gaussian normals, depth normals, consistency loss): double chains rounded to fp32 once, like mip.hip
+    "normals.hip": EXACT,
     # camera gradients: the per-Gaussian backward's chain continued to the camera, so the per-Gaussian backward's flags
     "camera_bwd.hip": EXACT,
     "capi.hip": [],

@@ -127,6 +127,12 @@ _ABI = {
         "r3dgs_mip_filter3d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_mip_filtered": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_mip_filtered_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        # include/r3dgs_normals.h; called by r3dgs_normals.py
+        "r3dgs_gaussian_normals": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+        "r3dgs_gaussian_normals_backward": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+        "r3dgs_depth_normal_workspace_bytes": (_sz, [_i, _i]),
+        "r3dgs_depth_normal": (_i, [_i, _i, _f, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+        "r3dgs_depth_normal_backward": (_i, [_i, _i, _f, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
         # include/r3dgs_camera.h
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy

@@ -58,6 +58,17 @@ _opacity are the filtered tensors -- the 3D filter first, the 2D compensation on
 backward with the rasterizer's.  Every route, `aux`, `aux_grad`, `features` and `features_geom_grad` work unchanged.  With both
 off (the default) nothing new is launched.  Refused with a ValueError: a QuantisedModel; filter_3d with
 pipe.compute_cov3D_python; antialiasing=True with a camera that requires grad; an f of the wrong shape, dtype or device.
+
+Surface normals.  `normals=True` adds the key "normal": the [3,H,W] map sum n_i alpha T of the Gaussians' view-space normals
+(r3dgs_normals.gaussian_normals: the axis of the smallest scale, turned towards the camera), blended by the feature-map launch
+over the forward's state -- together with `features=F` the three channels ride the same launch (C + 3 <=
+_C.FEATURE_MAX_CHANNELS).  Not normalised, like "depth" and "features".  Under grad mode the map is attached to the model's
+rotation through the normals' own backward, and with `features_geom_grad=True` to the geometry through the blend weights, as a
+user-supplied F would be; on the raw-parameter route the raw tensors go in.  `antialiasing` / `filter_3d` combine unchanged
+(the 3D filter adds the same term to all three squared scales: the smallest stays the smallest).  r3dgs_normals.
+normal_consistency(out["normal"], out["depth"], rs, alpha=out["alpha"]) is the depth-normal consistency loss.  normals=False
+(the default): the same dictionary, nothing new is launched, no recorder.  Refused with a ValueError before anything is
+launched: a QuantisedModel, pipe.compute_cov3D_python (no axis to pick), a camera that requires grad.
 """
 import functools
 import inspect
@@ -257,14 +268,19 @@ def _checked_features(features, pc, features_geom_grad, camera):
     if features.device.type != "cuda" or features.device != where:
         raise ValueError(f"render: features must live on the model's device ({where}), got {features.device}")
     if features_geom_grad:
-        if isinstance(pc, QuantisedModel):
-            raise ValueError("render: features_geom_grad=True is not available for a QuantisedModel (geometry gradients of its "
-                             "codebooks through the feature map are out of scope); its features alone can be trained")
-        if camera_requires_grad(camera):
-            raise ValueError("render: features_geom_grad=True together with a camera that requires grad is not supported: the "
-                             "feature map's share of a pose gradient is out of scope")
-        if not torch.is_grad_enabled():
-            raise ValueError("render: features_geom_grad=True under no_grad: there is no graph to attach the map to")
+        _checked_geom_grad(pc, camera)
+
+
+def _checked_geom_grad(pc, camera):
+    """The refusals of render(features_geom_grad=True)."""
+    if isinstance(pc, QuantisedModel):
+        raise ValueError("render: features_geom_grad=True is not available for a QuantisedModel (geometry gradients of its "
+                         "codebooks through the feature map are out of scope); its features alone can be trained")
+    if camera_requires_grad(camera):
+        raise ValueError("render: features_geom_grad=True together with a camera that requires grad is not supported: the "
+                         "feature map's share of a pose gradient is out of scope")
+    if not torch.is_grad_enabled():
+        raise ValueError("render: features_geom_grad=True under no_grad: there is no graph to attach the map to")
 
 
 def _feature_map(features, camera, out, state, rs, inputs=None):
@@ -347,6 +363,30 @@ def _antialiased_model(camera, pc, pipe, bg_color, scaling_modifier, antialiasin
     return _FilteredModel(pc, scaling, opacity)
 
 
+def _checked_normals(camera, pc, pipe, features):
+    """The refusals of render(normals=True), before anything is launched."""
+    if isinstance(pc, QuantisedModel):
+        raise ValueError("render: normals=True is not available for a QuantisedModel (its scales and rotations live in "
+                         "codebooks); decode() it and render the dense tensors")
+    if pipe.compute_cov3D_python:
+        raise ValueError("render: normals=True together with pipe.compute_cov3D_python is not supported (a precomputed "
+                         "covariance has no axis to pick)")
+    if camera_requires_grad(camera):
+        raise ValueError("render: normals=True together with a camera that requires grad is not supported: the normals' share "
+                         "of a pose gradient is out of scope")
+    if isinstance(features, torch.Tensor) and features.dim() == 2 and features.shape[1] + 3 > _C.FEATURE_MAX_CHANNELS:
+        raise ValueError(f"render: normals=True rides the feature launch: C + 3 <= {_C.FEATURE_MAX_CHANNELS} channels, got "
+                         f"C = {features.shape[1]}")
+
+
+def _model_normals(pc, pipe, rs, override_color, variable_sh_bands):
+    """The [P,3] view-space normals render(normals=True) blends: from the raw tensors where render() rasterizes from them."""
+    import r3dgs_normals
+    if fused_path_applies(pc, pipe, override_color, variable_sh_bands):
+        return r3dgs_normals.gaussian_normals(pc._xyz.detach(), pc._scaling.detach(), pc._rotation, rs, raw=True)
+    return r3dgs_normals.gaussian_normals(pc.get_xyz.detach(), pc.get_scaling.detach(), pc.get_rotation, rs, raw=False)
+
+
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
     aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
@@ -354,6 +394,7 @@ def render(*args, aux=None, **kwargs):
     features_geom_grad = bool(kwargs.pop("features_geom_grad", False))
     antialiasing = bool(kwargs.pop("antialiasing", False))   # likewise: the two anti-aliasing filters (the module's docstring);
     filter_3d = kwargs.pop("filter_3d", None)                # both off: today's path, nothing new is launched
+    normals = bool(kwargs.pop("normals", False))             # likewise: the "normal" map (the module's docstring)
     camera = args[0] if args else kwargs.get("viewpoint_camera")
     if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
         camera = camera.snapshot()                    # built once for this render
@@ -376,12 +417,12 @@ def render(*args, aux=None, **kwargs):
         if aux_grad:
             raise ValueError("render: aux_grad=True together with a camera that requires grad is not supported: the maps' "
                              "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera)")
-    if features is None and features_geom_grad:
+    if features is None and features_geom_grad and not normals:
         raise ValueError("render: features_geom_grad=True without features: pass the [P, C] tensor the map is blended from")
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
         if aux_grad:
             raise ValueError("render: aux_grad=True without aux: name the maps the loss is put on")
-        if features is None:
+        if features is None and not normals:
             return _render(*args, **kwargs)
         aux = ()
     aux = tuple(aux)
@@ -391,12 +432,29 @@ def render(*args, aux=None, **kwargs):
     if aux_grad and not torch.is_grad_enabled():
         raise ValueError("render: aux_grad=True under no_grad: there is no graph to attach the maps to")
     camera = args[0] if args else kwargs["viewpoint_camera"]
-    a = inspect.signature(_render).bind(*args, **kwargs)
+    a = _SIGNATURE.bind(*args, **kwargs)
     a.apply_defaults()
     a = a.arguments
     pc, pipe = a["pc"], a["pipe"]
+    if normals:                # (before anything is launched)
+        _checked_normals(camera, pc, pipe, features)
+        if features is None and features_geom_grad:
+            _checked_geom_grad(pc, camera)
     if features is not None:   # (before anything is launched)
         _checked_features(features, pc, features_geom_grad, camera)
+    user_channels = None if features is None else int(features.shape[1])
+    if normals:   # the three channels ride the feature launch, behind the user's
+        n = _model_normals(pc, pipe, _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"]), a["override_color"],
+                           a["variable_sh_bands"])
+        features = n if features is None else torch.cat((features, n), dim=1)
+
+    def blended(out):   # "features" as the launch left it -> the user's channels and the "normal" map
+        if normals:
+            both = out.pop("features")
+            out["normal"] = both[user_channels or 0:]
+            if user_channels is not None:
+                out["features"] = both[:user_channels]
+        return out
     if not aux_grad and not features_geom_grad:
         with _C.forward_state() as st:
             out = _render(*args, **kwargs)
@@ -404,7 +462,7 @@ def render(*args, aux=None, **kwargs):
         if features is not None:
             out["features"] = _feature_map(features, camera, out, st.result,
                                            _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"]))
-        return out
+        return blended(out)
     if aux_grad and isinstance(pc, QuantisedModel) and not pc.trainable:   # (before anything is launched)
         raise ValueError("render: aux_grad=True needs a trainable model (requires_grad_ the QuantisedModel first)")
     _tls.inputs = got = {}
@@ -419,6 +477,7 @@ def render(*args, aux=None, **kwargs):
     rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
     if features is not None:
         out["features"] = _feature_map(features, camera, out, st.result, rs, got["inputs"] if features_geom_grad else None)
+    out = blended(out)
     if not aux_grad:
         return _with_aux(aux, camera, out, st.result)
     if st.result is None:   # an empty model: nothing was rendered -- zero maps, attached all the same (a backward through
