@@ -44,6 +44,9 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "aux_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # gradients through those maps: the backward blend's step replayed, so the blend's flags again
     "aux_bwd.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # depth-distortion map and the pixel pass of its gradients: both blends' steps replayed (the weights are the forward's), so
+    # the blend's flags; its second stage is aux_bwd.hip's
+    "distortion.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # per-Gaussian feature maps and their gradients: both blends' steps replayed over C channels, so the blend's flags
     "feature_maps.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     # per-Gaussian blend-contribution scores: the forward blend's step replayed (its T and last contributor are held to the

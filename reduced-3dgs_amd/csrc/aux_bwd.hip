@@ -30,6 +30,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/r3dgs_aux.h"
+#include "aux_bwd_stage.h"
 #include "aux_math.h"
 #include "common.h"
 #include "pass_driver.h"
@@ -379,6 +380,78 @@ void check_dims(const char* what, int P, int R, int width, int height)
 
 }  // namespace
 
+// ---- the second stage, shared with the units that write the same slab (aux_bwd_stage.h) ---------------------------------
+size_t aux_bwd_workspace_bytes(size_t R)
+{
+    return (size_t)reinterpret_cast<uintptr_t>(AuxBwdWork::carve(nullptr, R, sort_temp_bytes(R)).end) + kAlign;
+}
+
+float* aux_bwd_slab(char* workspace, size_t R) { return AuxBwdWork::carve(workspace, R, 0).slab; }
+
+void aux_bwd_zero_outputs(int P, const AuxBwdGeom& g, hipStream_t s)
+{
+    const size_t n = (size_t)P;
+    if (g.dL_dmeans2D) R3_HIP(hipMemsetAsync(g.dL_dmeans2D, 0, sizeof(float) * 3 * n, s));
+    if (g.dL_dmeans3D) R3_HIP(hipMemsetAsync(g.dL_dmeans3D, 0, sizeof(float) * 3 * n, s));
+    if (g.dL_dopacity) R3_HIP(hipMemsetAsync(g.dL_dopacity, 0, sizeof(float) * n, s));
+    if (g.dL_dscales) R3_HIP(hipMemsetAsync(g.dL_dscales, 0, sizeof(float) * 3 * n, s));
+    if (g.dL_drotations) R3_HIP(hipMemsetAsync(g.dL_drotations, 0, sizeof(float) * 4 * n, s));
+    if (g.dL_dcov3D) R3_HIP(hipMemsetAsync(g.dL_dcov3D, 0, sizeof(float) * 6 * n, s));
+}
+
+void aux_bwd_check_geom(const char* what, const AuxBwdGeom& g)
+{
+    if (!g.viewmatrix || !g.projmatrix || !g.means3D || !g.radii)
+        throw Error(std::string(what) + ": viewmatrix, projmatrix, means3D and radii must not be NULL");
+    if (!g.cov3D_precomp && (!g.scales || !g.rotations))
+        throw Error(std::string(what) + ": need scales and rotations, or cov3D_precomp");
+}
+
+void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int height, const AuxBwdGeom& in, char* workspace,
+                          hipStream_t s)
+{
+    size_t temp = sort_temp_bytes((size_t)R);
+    const AuxBwdWork w = AuxBwdWork::carve(workspace, (size_t)R, temp);
+    const uint32_t key_blocks = (uint32_t)std::min<size_t>(((size_t)R + 255) / 256, 4096);
+    hipLaunchKernelGGL(aux_bwd_keys_kernel, dim3(key_blocks), dim3(256), 0, s, st.geom.header, st.bin.point_list, (uint32_t)P,
+                       (uint32_t)R, w.keys_in, w.slots_in);
+    check_launch("aux maps backward, keys", s, false);
+    R3_HIP(rocprim::radix_sort_pairs(w.temp, temp, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)R, 0, 32, s));
+
+    AuxGaussArgs g;
+    g.rec = st.geom.rec;
+    g.radii = in.radii;
+    g.tiles = st.geom.tiles;
+    g.keys = w.keys_out;
+    g.slots = w.slots_out;
+    g.slab = w.slab;
+    g.view = in.viewmatrix;
+    g.proj = in.projmatrix;
+    g.means3D = in.means3D;
+    g.scales = in.scales;
+    g.rotations = in.rotations;
+    g.cov3D_precomp = in.cov3D_precomp;
+    g.tan_fovx = in.tan_fovx;
+    g.tan_fovy = in.tan_fovy;
+    g.scale_modifier = in.scale_modifier;
+    g.W = width;
+    g.H = height;
+    g.P = (uint32_t)P;
+    g.R = (uint32_t)R;
+    g.dL_dmeans2D = in.dL_dmeans2D;
+    g.dL_dmeans3D = in.dL_dmeans3D;
+    g.dL_dopacity = in.dL_dopacity;
+    g.dL_dscales = in.dL_dscales;
+    g.dL_drotations = in.dL_drotations;
+    g.dL_dcov3D = in.dL_dcov3D;
+    const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
+    if (g_f64_chain.get())
+        hipLaunchKernelGGL(aux_bwd_gauss_kernel<true>, dim3(gblocks), dim3(64), 0, s, g);
+    else
+        hipLaunchKernelGGL(aux_bwd_gauss_kernel<false>, dim3(gblocks), dim3(64), 0, s, g);
+    check_launch("aux maps backward, per-Gaussian chain", s, false);
+}
+
 }  // namespace r3
 
 extern "C" {
@@ -390,7 +463,7 @@ size_t r3dgs_aux_maps_backward_workspace_bytes(int P, int R, int width, int heig
         using namespace r3;
         check_dims("aux_maps_backward_workspace_bytes", P, R, width, height);
         if (P == 0 || R == 0) return 0;
-        out = (size_t)reinterpret_cast<uintptr_t>(AuxBwdWork::carve(nullptr, (size_t)R, sort_temp_bytes((size_t)R)).end) + kAlign;
+        out = aux_bwd_workspace_bytes((size_t)R);
         return 0;
     });
     return out;
@@ -408,30 +481,21 @@ int r3dgs_aux_maps_backward(int P, int R, int width, int height, char* geom_buff
         hipStream_t s = static_cast<hipStream_t>(stream);
         check_dims("aux_maps_backward", P, R, width, height);
         if (P == 0) return 0;   // every output has P rows
+        const AuxBwdGeom geom = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
+                                 cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
         const bool no_upstream = !dL_ddepth && !dL_dalpha && !dL_dmedian;
         if (R == 0 || no_upstream) {   // nothing to walk: zeros, the blobs are not read
-            const size_t n = (size_t)P;
-            if (dL_dmeans2D) R3_HIP(hipMemsetAsync(dL_dmeans2D, 0, sizeof(float) * 3 * n, s));
-            if (dL_dmeans3D) R3_HIP(hipMemsetAsync(dL_dmeans3D, 0, sizeof(float) * 3 * n, s));
-            if (dL_dopacity) R3_HIP(hipMemsetAsync(dL_dopacity, 0, sizeof(float) * n, s));
-            if (dL_dscales) R3_HIP(hipMemsetAsync(dL_dscales, 0, sizeof(float) * 3 * n, s));
-            if (dL_drotations) R3_HIP(hipMemsetAsync(dL_drotations, 0, sizeof(float) * 4 * n, s));
-            if (dL_dcov3D) R3_HIP(hipMemsetAsync(dL_dcov3D, 0, sizeof(float) * 6 * n, s));
+            aux_bwd_zero_outputs(P, geom, s);
             return 0;
         }
-        if (!dL_dmeans2D && !dL_dmeans3D && !dL_dopacity && !dL_dscales && !dL_drotations && !dL_dcov3D) return 0;
+        if (!geom.any_output()) return 0;
         if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("aux_maps_backward: state buffers must not be NULL");
         if (!workspace) throw Error("aux_maps_backward: the workspace must not be NULL");
-        if (!viewmatrix || !projmatrix || !means3D || !radii)
-            throw Error("aux_maps_backward: viewmatrix, projmatrix, means3D and radii must not be NULL");
-        if (!cov3D_precomp && (!scales || !rotations))
-            throw Error("aux_maps_backward: need scales and rotations, or cov3D_precomp");
+        aux_bwd_check_geom("aux_maps_backward", geom);
         const TileGrid grid = grid_of(width, height);
         const size_t Tn = grid.n();
         if (Tn * 4 > 0x7fffffffull) throw Error("aux_maps_backward: the image has too many tiles for one launch");
         const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
-        size_t temp = sort_temp_bytes((size_t)R);
-        const AuxBwdWork w = AuxBwdWork::carve(workspace, (size_t)R, temp);
 
         AuxBwdArgs a;
         a.ranges = st.img.ranges;
@@ -450,48 +514,10 @@ int r3dgs_aux_maps_backward(int P, int R, int width, int height, char* geom_buff
         a.nblocks = (uint32_t)(Tn * 4);
         a.P = (uint32_t)P;
         a.R = (uint32_t)R;
-        a.slab = w.slab;
+        a.slab = aux_bwd_slab(workspace, (size_t)R);
         hipLaunchKernelGGL(aux_bwd_pixel_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
         check_launch("aux maps backward, pixel pass", s, false);
-
-        const uint32_t key_blocks = (uint32_t)std::min<size_t>(((size_t)R + 255) / 256, 4096);
-        hipLaunchKernelGGL(aux_bwd_keys_kernel, dim3(key_blocks), dim3(256), 0, s, st.geom.header, st.bin.point_list, (uint32_t)P,
-                           (uint32_t)R, w.keys_in, w.slots_in);
-        check_launch("aux maps backward, keys", s, false);
-        R3_HIP(rocprim::radix_sort_pairs(w.temp, temp, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)R, 0, 32, s));
-
-        AuxGaussArgs g;
-        g.rec = st.geom.rec;
-        g.radii = radii;
-        g.tiles = st.geom.tiles;
-        g.keys = w.keys_out;
-        g.slots = w.slots_out;
-        g.slab = w.slab;
-        g.view = viewmatrix;
-        g.proj = projmatrix;
-        g.means3D = means3D;
-        g.scales = scales;
-        g.rotations = rotations;
-        g.cov3D_precomp = cov3D_precomp;
-        g.tan_fovx = tan_fovx;
-        g.tan_fovy = tan_fovy;
-        g.scale_modifier = scale_modifier;
-        g.W = width;
-        g.H = height;
-        g.P = (uint32_t)P;
-        g.R = (uint32_t)R;
-        g.dL_dmeans2D = dL_dmeans2D;
-        g.dL_dmeans3D = dL_dmeans3D;
-        g.dL_dopacity = dL_dopacity;
-        g.dL_dscales = dL_dscales;
-        g.dL_drotations = dL_drotations;
-        g.dL_dcov3D = dL_dcov3D;
-        const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
-        if (g_f64_chain.get())
-            hipLaunchKernelGGL(aux_bwd_gauss_kernel<true>, dim3(gblocks), dim3(64), 0, s, g);
-        else
-            hipLaunchKernelGGL(aux_bwd_gauss_kernel<false>, dim3(gblocks), dim3(64), 0, s, g);
-        check_launch("aux maps backward, per-Gaussian chain", s, false);
+        aux_bwd_second_stage(st, P, R, width, height, geom, workspace, s);
         return 0;
     });
 }

@@ -106,6 +106,12 @@ _ABI = {
         "r3dgs_aux_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_aux_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # 3 upstream, 6 outputs
+        # include/r3dgs_distortion.h
+        "r3dgs_distortion_map": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+        "r3dgs_distortion_map_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_distortion_map_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp,
+                                               _vp,                                             # .. radii
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # upstream, moments, 6 outputs
         # include/r3dgs_features.h
         "r3dgs_feature_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
         "r3dgs_feature_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -1271,6 +1277,87 @@ def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewma
             P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
             float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(ups[0]), _ptr(ups[1]),
             _ptr(ups[2]), *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "aux_maps_backward")
+    return out
+
+
+def depth_mapping(mapping):
+    """The (near, far) pair the distortion calls take: True / None / (0, 0) = the linear mapping m = z; (near, far) with
+    0 < near < far = 2DGS's m = far / (far - near) (1 - near / z).  Anything else raises ValueError."""
+    if mapping is True or mapping is None:
+        return 0.0, 0.0
+    try:
+        near, far = (float(v) for v in mapping)
+    except (TypeError, ValueError):
+        raise ValueError(f"distortion: expected True or a (near, far) pair, got {mapping!r}") from None
+    if not ((near == 0.0 and far == 0.0) or 0.0 < near < far):
+        raise ValueError(f"distortion: need near = far = 0 (the linear mapping) or 0 < near < far, got ({near}, {far})")
+    return near, far
+
+
+def distortion_map(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, near=0.0, far=0.0, want_moments=False):
+    """r3dgs_distortion_map (include/r3dgs_distortion.h) over the three buffers a forward returned -> float [1,H,W]: per pixel
+    sum_{j<k} w_j w_k (m_k - m_j)^2 over the Gaussians the forward blended (w = alpha T, m the mapped depth: linear for
+    near = far = 0, 2DGS's for 0 < near < far).  want_moments=True -> (map, moments float [2,H,W]): what distortion_map_backward
+    reads.  R as in aux_maps.  One launch, no host wait; the buffers are only read; the map carries no gradient."""
+    near, far = depth_mapping((near, far))
+    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    P, H, W = int(P), int(H), int(W)
+    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
+        raise RuntimeError("distortion_map: the three state buffers must live on one device")
+    if dev.type != "cuda":   # P == 0 and nothing says where: the current device, as the forward's empty result
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    moments = torch.empty((2, H, W), dtype=torch.float32, device=dev) if want_moments else None
+    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
+    with _on_device(dev):
+        _check(_lib.r3dgs_distortion_map(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), near, far,
+                                         _ptr(out), _ptr(moments), _stream()), "distortion_map")
+    return (out, moments) if want_moments else out
+
+
+def distortion_map_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
+                            scales, scale_modifier, rotations, cov3D_precomp, radii, dL_ddistortion, moments, near=0.0, far=0.0,
+                            want=AUX_GRADS):
+    """r3dgs_distortion_map_backward (include/r3dgs_distortion.h): the gradients of the map of `distortion_map` over the same
+    three buffers, from dL_ddistortion (float, H*W elements, any shape; None = zero) and the `moments` that call returned for
+    the same (near, far).  Everything else as aux_maps_backward: activated scales / rotations or cov3D_precomp -> {name: float
+    [P, cols]} for the names in `want` (a subset of AUX_GRADS).  The workspace is allocated here, per call."""
+    near, far = depth_mapping((near, far))
+    want = tuple(want)
+    for name in want:
+        if name not in AUX_GRADS:
+            raise ValueError(f"distortion_map_backward: unknown gradient {name!r} (expected a subset of {AUX_GRADS})")
+    P, H, W = int(P), int(H), int(W)
+    dev = means3D.device
+    if P and dev.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+    if dev.type != "cuda":
+        dev = torch.device("cuda", torch.cuda.current_device())
+    g, mom = _dev(dL_ddistortion, dev), _dev(moments, dev)
+    if g is not None and g.numel() != H * W:
+        raise RuntimeError(f"distortion_map_backward: dL_ddistortion has {g.numel()} elements, the image {H * W}")
+    if g is not None and P and (mom is None or mom.numel() != 2 * H * W):
+        raise RuntimeError(f"distortion_map_backward: moments must have {2 * H * W} elements (distortion_map(want_moments=True))")
+    out = {name: torch.empty((P, _AUX_GRAD_COLS[name]), dtype=torch.float32, device=dev) for name in want}
+    if P == 0:
+        return out
+    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
+        raise RuntimeError("distortion_map_backward: the state buffers and the model must live on one device")
+    m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
+    rad = _dev(radii, dev, torch.int32)
+    vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
+    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
+    with _on_device(dev):
+        nbytes = _lib.r3dgs_distortion_map_backward_workspace_bytes(P, cap, W, H)
+        if nbytes == 0 and cap:
+            _check(-1, "distortion_map_backward_workspace_bytes")
+        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_distortion_map_backward(
+            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), near, far, _ptr(vm), _ptr(pm), float(tanfovx),
+            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(g), _ptr(mom),
+            *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "distortion_map_backward")
     return out
 
 

@@ -385,6 +385,56 @@ def aux_maps_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_pre
     return dict(zip(maps, got))
 
 
+def distortion_map(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, near=0.0, far=0.0):
+    """The depth-distortion map (the squared form of the 2DGS regulariser) replayed from the three buffers a forward returned
+    -> float [1,H,W]: per pixel sum_{j<k} w_j w_k (m_k - m_j)^2 over the Gaussians the forward blended, w = alpha T, m the
+    mapped depth -- m = z for near = far = 0, 2DGS's m = far / (far - near) (1 - near / z) for 0 < near < far.  No background
+    term, 0 where nothing contributed.  One kernel launch, no host wait; the buffers are only read.  The map carries NO
+    gradient (`distortion_map_with_grad` attaches it)."""
+    with torch.no_grad():
+        return _C.distortion_map(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, near, far)
+
+
+class _DistortionMap(torch.autograd.Function):
+    """`distortion_map` with gradients.  Inputs as `_AuxMaps`: means3D, means2D, opacities (raw), scales (activated), rotations
+    (unit), cov3D_precomp (or an empty tensor), then without gradient: the forward's six-tuple `state`, raster_settings and the
+    (near, far) pair  ->  the [1,H,W] map.  The backward is `_C.distortion_map_backward` over the saved buffers and moments."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, mapping):
+        rs = raster_settings
+        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
+        near, far = _C.depth_mapping(mapping)
+        out, moments = _C.distortion_map(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer,
+                                         binningBuffer, imgBuffer, near, far, want_moments=True)
+        ctx.raster_settings, ctx.num_rendered, ctx.mapping = rs, num_rendered, (near, far)
+        ctx.save_for_backward(means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer, moments)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        rs = ctx.raster_settings
+        means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer, moments = ctx.saved_tensors
+        names = ("means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
+        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:6]) if need)
+        got = _C.distortion_map_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
+                                         binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+                                         means3D, scales, rs.scale_modifier, rotations, cov3D_precomp, radii, grad, moments,
+                                         *ctx.mapping, want=want)
+        return tuple(got.get(n) for n in names) + (None, None, None)
+
+
+def distortion_map_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
+                             near=0.0, far=0.0):
+    """The map of `distortion_map` ATTACHED to the model's tensors -> float [1,H,W].  Arguments as `aux_maps_with_grad`;
+    means2D receives the map's share of the screen-space gradient as well."""
+    empty = torch.Tensor([])
+    return _DistortionMap.apply(means3D, means2D, opacities, empty if scales is None else scales,
+                                empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
+                                state, raster_settings, (near, far))
+
+
 def feature_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, features):
     """A per-Gaussian feature vector blended into a map, replayed from the three buffers a forward returned: features float32
     [P, C] -> float [C, H, W], map[c] = sum over the blended Gaussians of features[id, c] * alpha * T (fp32, list order).  Not

@@ -69,6 +69,18 @@ user-supplied F would be; on the raw-parameter route the raw tensors go in.  `an
 normal_consistency(out["normal"], out["depth"], rs, alpha=out["alpha"]) is the depth-normal consistency loss.  normals=False
 (the default): the same dictionary, nothing new is launched, no recorder.  Refused with a ValueError before anything is
 launched: a QuantisedModel, pipe.compute_cov3D_python (no axis to pick), a camera that requires grad.
+
+Depth distortion.  `distortion=True` or `distortion=(near, far)` adds the key "distortion": the [1,H,W] map sum_{j<k} w_j w_k
+(m_k - m_j)^2 over the Gaussians the forward blended, w = alpha T (include/r3dgs_distortion.h: the squared form 2DGS's
+rasterizer computes; the linear-order form of Mip-NeRF 360 / gsplat is not offered).  True: the mapped depth m is the view depth
+z; (near, far) with 0 < near < far: 2DGS's m = far / (far - near) (1 - near / z).  One extra launch on the forward's state.
+Under grad mode, for a model with something trainable, the map is attached to the model's tensors
+(diff_gaussian_rasterization._DistortionMap) and "viewspace_points".grad receives its share, as with `aux_grad`; otherwise --
+no_grad, nothing trainable, a QuantisedModel -- it is detached.  The 2DGS recipe: lambda_dist * out["distortion"].mean() next
+to r3dgs_normals.normal_consistency.  It combines with `aux`, `aux_grad`, `features`, `normals`, `antialiasing` and `filter_3d`
+on every route; distortion=None / False (the default): the same dictionary, nothing new is launched.  Refused with a
+ValueError before anything is launched: a trainable QuantisedModel under grad mode, a camera that requires grad, a (near, far)
+that is neither (0, 0) nor 0 < near < far.
 """
 import functools
 import inspect
@@ -78,7 +90,8 @@ import threading
 import torch
 
 from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps, aux_maps_with_grad,
-                                         feature_maps, feature_maps_with_grad, rasterize_gaussian_params)
+                                         distortion_map, distortion_map_with_grad, feature_maps, feature_maps_with_grad,
+                                         rasterize_gaussian_params)
 from r3dgs_quantised import QuantisedModel
 
 # render(aux_grad=True) asks the call it wraps for the tensors its forward was fed: a dictionary here, for the duration of that
@@ -302,6 +315,23 @@ def _feature_map(features, camera, out, state, rs, inputs=None):
     return feature_maps_with_grad(features, means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs)
 
 
+def _distortion_map(mapping, camera, out, state, rs, inputs):
+    """The "distortion" entry of the result: [1,H,W] from the six-tuple `state` of the forward that produced `out` (None: an
+    empty model -- a zero map); with `inputs` (means3D, opacities, scales, rotations, cov3D_precomp) attached to them."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    near, far = mapping
+    if state is None:
+        zero = torch.zeros((1, H, W), dtype=torch.float32, device=out["render"].device)
+        if inputs is None:
+            return zero
+        return zero + 0.0 * sum(t.sum() for t in inputs if t is not None and t.requires_grad)
+    if inputs is None:
+        num_rendered, _, radii, geom, binning, img = state
+        return distortion_map(int(radii.numel()), num_rendered, H, W, geom, binning, img, near, far)
+    means3D, opacities, scales, rotations, cov3D = inputs
+    return distortion_map_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs, near, far)
+
+
 _SIGNATURE = inspect.signature(_render)
 
 
@@ -395,6 +425,8 @@ def render(*args, aux=None, **kwargs):
     antialiasing = bool(kwargs.pop("antialiasing", False))   # likewise: the two anti-aliasing filters (the module's docstring);
     filter_3d = kwargs.pop("filter_3d", None)                # both off: today's path, nothing new is launched
     normals = bool(kwargs.pop("normals", False))             # likewise: the "normal" map (the module's docstring)
+    distortion = kwargs.pop("distortion", None)              # likewise: the "distortion" map; None / False: no such key
+    mapping = None if distortion is None or distortion is False else _C.depth_mapping(distortion)
     camera = args[0] if args else kwargs.get("viewpoint_camera")
     if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
         camera = camera.snapshot()                    # built once for this render
@@ -417,12 +449,15 @@ def render(*args, aux=None, **kwargs):
         if aux_grad:
             raise ValueError("render: aux_grad=True together with a camera that requires grad is not supported: the maps' "
                              "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera)")
+        if mapping is not None:
+            raise ValueError("render: distortion together with a camera that requires grad is not supported: the map's "
+                             "share of a pose gradient is out of scope (detach the camera)")
     if features is None and features_geom_grad and not normals:
         raise ValueError("render: features_geom_grad=True without features: pass the [P, C] tensor the map is blended from")
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
         if aux_grad:
             raise ValueError("render: aux_grad=True without aux: name the maps the loss is put on")
-        if features is None and not normals:
+        if features is None and not normals and mapping is None:
             return _render(*args, **kwargs)
         aux = ()
     aux = tuple(aux)
@@ -442,6 +477,11 @@ def render(*args, aux=None, **kwargs):
             _checked_geom_grad(pc, camera)
     if features is not None:   # (before anything is launched)
         _checked_features(features, pc, features_geom_grad, camera)
+    # the distortion map is attached whenever there is a graph to attach it to; a QuantisedModel gets the detached map
+    dist_attach = mapping is not None and torch.is_grad_enabled() and not isinstance(pc, QuantisedModel)
+    if mapping is not None and isinstance(pc, QuantisedModel) and pc.trainable and torch.is_grad_enabled():
+        raise ValueError("render: distortion for a trainable QuantisedModel is not supported (gradients of its codebooks "
+                         "through the distortion map are out of scope); render it under no_grad for the detached map")
     user_channels = None if features is None else int(features.shape[1])
     if normals:   # the three channels ride the feature launch, behind the user's
         n = _model_normals(pc, pipe, _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"]), a["override_color"],
@@ -455,10 +495,12 @@ def render(*args, aux=None, **kwargs):
             if user_channels is not None:
                 out["features"] = both[:user_channels]
         return out
-    if not aux_grad and not features_geom_grad:
+    if not aux_grad and not features_geom_grad and not dist_attach:
         with _C.forward_state() as st:
             out = _render(*args, **kwargs)
         out = _with_aux(aux, camera, out, st.result)
+        if mapping is not None:
+            out["distortion"] = _distortion_map(mapping, camera, out, st.result, None, None)
         if features is not None:
             out["features"] = _feature_map(features, camera, out, st.result,
                                            _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"]))
@@ -472,9 +514,12 @@ def render(*args, aux=None, **kwargs):
     finally:
         _tls.inputs = None
     means3D, opacities, scales, rotations, cov3D = got["inputs"]
-    if not any(t is not None and t.requires_grad for t in got["inputs"]):
+    trainable = any(t is not None and t.requires_grad for t in got["inputs"])
+    if not trainable and (aux_grad or features_geom_grad):
         raise ValueError(f"render: {'aux_grad' if aux_grad else 'features_geom_grad'}=True for a model with nothing trainable")
     rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
+    if mapping is not None:   # (nothing trainable: the detached map)
+        out["distortion"] = _distortion_map(mapping, camera, out, st.result, rs, got["inputs"] if trainable else None)
     if features is not None:
         out["features"] = _feature_map(features, camera, out, st.result, rs, got["inputs"] if features_geom_grad else None)
     out = blended(out)
