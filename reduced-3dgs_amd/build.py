@@ -52,6 +52,8 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     # per-Gaussian blend-contribution scores: the forward blend's step replayed (its T and last contributor are held to the
     # forward's bit for bit), so the blend's flags
     "importance.hip": ["-ffp-contract=fast", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # the replay passes' (Gaussian id, list slot) keys and their rocPRIM sort: integer code, no rounding depends on flags
+    "pair_sort.hip": [],
     # fused L1 + D-SSIM loss: contraction in the window sums; one correctly rounded divide per pixel (loss_math.h)
     "loss.hip": ["-ffp-contract=fast", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused Adam step: torch's roundings exactly -- no contraction, correctly rounded divide and sqrt, the fmas torch's

@@ -1,10 +1,60 @@
-// aux_bwd_stage.h -- the second stage of aux_bwd.hip, for the units whose pixel pass writes the same slab (distortion.hip):
-// the workspace layout, the zero-fill of a call with nothing to walk, and the three launches behind the pixel pass -- keys, the
-// stable sort by Gaussian id, the per-Gaussian sum in double and chain (aux_math.h aux_bwd_chain).  Defined in aux_bwd.hip.
+// aux_bwd_stage.h -- what the units with an aux-style backward share (aux_bwd.hip, distortion.hip, feature_maps.hip):
+//   * the slab rows a pixel pass writes (aux_bwd_pixel_kernel, dist_bwd_pixel_kernel): 32-byte rows of seven wave sums at
+//     slab[(list slot * 4 + quadrant) * 8], zero rows for an entry nobody blended and for the slots behind the walk;
+//   * the ends of a per-Gaussian kernel: the zero gradient and the six guarded stores;
+//   * the host side of aux_bwd.hip's second stage (defined there): the workspace layout, the zero fill of a call with
+//     nothing to walk, and the three launches behind the pixel pass -- keys, the stable sort (pair_sort.h), the per-Gaussian
+//     sum in double and chain.
 #pragma once
+#include "aux_math.h"
 #include "common.h"
+#include "pair_sort.h"
+#include "replay_walk.h"
 
 namespace r3 {
+
+// ---- slab rows (two float4 per row) -------------------------------------------------------------------------------------
+__device__ __forceinline__ size_t slab_row(const WalkSpan& sp, uint32_t k, int quad)   // of list position k, in float4
+{
+    return ((size_t)(sp.first + k) * kAuxQuads + (size_t)quad) * 2;
+}
+
+// the slots behind the walk: zero rows
+__device__ __forceinline__ void slab_zero_behind(R3_GLOBAL float4* rows, const WalkSpan& sp, int quad, int lane)
+{
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t k = sp.len + (uint32_t)lane; k < sp.list_len; k += kWalkChunk) {
+        const size_t row = slab_row(sp, k, quad);
+        rows[row] = zero4;
+        rows[row + 1] = zero4;
+    }
+}
+
+// the seven sums of entry j over the wave, parked in the slab's order (aux_math.h aux_row_of): sx, sy, sxx, sxy, syy, sm, sz
+__device__ __forceinline__ void slab_park_sums(float4 (*s_out)[2], int j, int lane, const SplatSums& sg)
+{
+    const float r0 = wave_sum_ror(sg.sx), r1 = wave_sum_ror(sg.sy), r2 = wave_sum_ror(sg.sxx);
+    const float r3 = wave_sum_ror(sg.sxy), r4 = wave_sum_ror(sg.syy), r5 = wave_sum_ror(sg.sm);
+    const float r6 = wave_sum_ror(sg.r);
+    if (lane == 0) {
+        s_out[j][0] = make_float4(r0, r1, r2, r3);
+        s_out[j][1] = make_float4(r4, r5, r6, 0.f);
+    }
+}
+
+// lane j stores the row of entry j of the chunk at cbase: the parked sums, or zeros for an entry no lane blended
+__device__ __forceinline__ void slab_store_chunk(R3_GLOBAL float4* rows, const float4 (*s_out)[2], const WalkSpan& sp, int quad,
+                                                 uint32_t cbase, int lane, unsigned long long contributed)
+{
+    if (cbase + (uint32_t)lane < sp.len) {
+        const bool have = (contributed >> lane) & 1ull;
+        const size_t row = slab_row(sp, cbase + (uint32_t)lane, quad);
+        float4 o0 = s_out[lane][0], o1 = s_out[lane][1];
+        if (!have) o0 = o1 = make_float4(0.f, 0.f, 0.f, 0.f);
+        rows[row] = o0;
+        rows[row + 1] = o1;
+    }
+}
 
 // what the per-Gaussian chain reads besides the state blobs, and the six outputs (any of them nullptr: not written)
 struct AuxBwdGeom {
@@ -18,6 +68,49 @@ struct AuxBwdGeom {
     bool any_output() const { return dL_dmeans2D || dL_dmeans3D || dL_dopacity || dL_dscales || dL_drotations || dL_dcov3D; }
 };
 
+// ---- the per-Gaussian kernels' shared ends --------------------------------------------------------------------------------
+// (A: a kernel's argument struct with the six output pointers.  The middle -- camera and parameter loads, aux_math.h
+// aux_bwd_chain -- stays written out in aux_bwd_gauss_kernel and feat_bwd_gauss_kernel: behind a function boundary the
+// compiler orders the operands of the chain's commutative fp32 operations differently, contracts the other product of a
+// sum of two into the FMA, and the gradients' last bits move.)
+__device__ __forceinline__ void gauss_grad_clear(AuxGaussGrad& o)
+{
+    o.mean2D[0] = o.mean2D[1] = o.opacity = 0.f;
+    for (int k = 0; k < 3; k++) o.mean3D[k] = o.scale[k] = 0.f;
+    for (int k = 0; k < 4; k++) o.rot[k] = 0.f;
+    for (int k = 0; k < 6; k++) o.cov6[k] = 0.f;
+}
+
+// row i of every output that is asked for
+template <class A>
+__device__ __forceinline__ void gauss_grad_store(const A& a, uint32_t i, const AuxGaussGrad& o)
+{
+    if (a.dL_dmeans2D) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dmeans2D) + 3 * (size_t)i;
+        d[0] = o.mean2D[0];
+        d[1] = o.mean2D[1];
+        d[2] = 0.f;
+    }
+    if (a.dL_dmeans3D) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dmeans3D) + 3 * (size_t)i;
+        for (int k = 0; k < 3; k++) d[k] = o.mean3D[k];
+    }
+    if (a.dL_dopacity) global_ptr(a.dL_dopacity)[i] = o.opacity;
+    if (a.dL_dscales) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dscales) + 3 * (size_t)i;
+        for (int k = 0; k < 3; k++) d[k] = o.scale[k];
+    }
+    if (a.dL_drotations) {
+        R3_GLOBAL float* d = global_ptr(a.dL_drotations) + 4 * (size_t)i;
+        for (int k = 0; k < 4; k++) d[k] = o.rot[k];
+    }
+    if (a.dL_dcov3D) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dcov3D) + 6 * (size_t)i;
+        for (int k = 0; k < 6; k++) d[k] = o.cov6[k];
+    }
+}
+
+// ---- the host side, defined in aux_bwd.hip ------------------------------------------------------------------------------
 // bytes of the workspace for a pair capacity R > 0 (asks rocPRIM once per R: call it outside a capture first)
 size_t aux_bwd_workspace_bytes(size_t R);
 // the slab inside a workspace: [R][4 quadrants][8 floats], every (slot < num_pairs, quadrant) row written by the pixel pass

@@ -1,19 +1,17 @@
 // feature_maps.hip -- a per-Gaussian feature vector F[P, C] blended into a [C, H, W] map, and the gradients through it
-// (include/r3dgs_features.h; the arithmetic is feature_math.h), gfx950.  Passes of their own behind any forward, like
-// aux_maps.hip / aux_bwd.hip: they read the three state blobs and write only the caller's outputs and workspace.
+// (include/r3dgs_features.h; the arithmetic is feature_math.h), gfx950.  Replay passes (DESIGN.md "Replay passes"; the
+// walk's shared part is replay_walk.h): they read the three state blobs and write only the caller's outputs and workspace.
 //
 // Channels go in register-resident groups of NC = 4, 8 or 16 (the smallest that holds C, 16 beyond); a map of more channels
-// than a group is a further walk per group, over the second grid dimension.
+// than a group is a further walk per group, over the second grid dimension: one wave per (quadrant, channel group).
 //
-// Forward, feat_fwd_kernel<NC> -- aux_maps_kernel's shape: one 64-lane wave per (8x8 quadrant of a tile, channel group), one
-// pixel per lane; the tile's list is fetched 64 entries at a time, one chunk ahead of its use: lane j gathers the first 32
-// bytes of the GRec of entry j and the group's slice of its feature row (16-byte loads when the rows allow it) and parks
-// both in LDS -- a 32-byte record and NC floats beside it, 6 KB per workgroup at NC = 16; the walk ends at the quadrant's
-// deepest contributor (ImageState::quad_depth), lane j runs the forward's region pre-test for entry j, and the step is the
-// forward's own (feature_math.h feat_step).  Plain vector stores; a partial tile writes only the pixels inside the image.
+// Forward, feat_fwd_kernel<NC> -- the walk front to back: lane j gathers, beside the record of entry j, the group's slice of
+// its feature row (16-byte loads when the rows allow it) and parks NC floats beside the record in LDS, 6 KB per workgroup at
+// NC = 16; the step is the forward's own (feature_math.h feat_step).  Plain vector stores; a partial tile writes only the
+// pixels inside the image.
 //
 // Backward, four or five launches on the caller's stream (the route of aux_bwd.hip; no host wait, no allocation, no atomics):
-//   1. feat_bwd_pixel_kernel<NC, GEOM, FEAT> -- the same shape walked back to front with T recovered from final_T by
+//   1. feat_bwd_pixel_kernel<NC, GEOM, FEAT> -- the walk back to front with T recovered from final_T by
 //      division.  Per entry some lane blended, the wave reduces the group's NC channel sums and (GEOM) the six geometric
 //      sums with a TRANSPOSING reduction: at every step a lane hands half of its values to its partner and keeps the sums
 //      of the other half, so N values cost N - 1 + (6 - log2 N) shuffles instead of 6 N, and lane l ends up with the
@@ -21,24 +19,19 @@
 //      entry no lane blended -- at (list slot, quadrant[, group]); the slots behind the walk get zero rows.  Every row of
 //      every slot < num_pairs is written in every call by exactly one wave: the slabs need no clearing.
 //      The backward's recurrence is linear in the channels: each group carries its own and their geometric sums add up.
-//   2. feat_keys_kernel, 3. a stable rocPRIM radix sort of (Gaussian id, list slot) by id.
-//   4. feat_bwd_feature_kernel -- one lane per (Gaussian, four channels): its run of the sorted keys by binary search, its
-//      rows added in sorted order (slot ascending, quadrant 0..3) in double -> dL_dfeatures.
+//   2, 3. the (Gaussian id, list slot) keys and their stable sort by id (pair_sort.h).
+//   4. feat_bwd_feature_kernel -- one lane per (Gaussian, four channels): its run of the sorted keys, its rows added in
+//      sorted order (slot ascending, quadrant 0..3) in double -> dL_dfeatures.
 //   5. feat_bwd_gauss_kernel<F64> (GEOM) -- one lane per Gaussian: the six sums over (slot, quadrant, group) in double, then
-//      aux_math.h aux_bwd_chain with a zero z sum.
+//      aux_bwd.hip's per-Gaussian tail (aux_bwd_stage.h) with a zero z sum.
 // A Gaussian that lost pairs to an overflowed reservation (its run is shorter than its tiles_touched) gets zero rows.
 // The order of every sum is fixed by the data alone: the results are bit-identical run to run.
 // Workspace per pair, G = ceil(C / 16) groups (NC = 16): 4 x G x 64 B feature rows + 4 x G x 32 B geometric rows + 16 B of
 // keys and slots = 384 G + 16 bytes, plus rocPRIM's temp storage.
-#include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
 
-#include <rocprim/rocprim.hpp>
-
 #include "../../include/r3dgs_features.h"
+#include "aux_bwd_stage.h"
 #include "feature_math.h"
 #include "common.h"
 #include "pass_driver.h"
@@ -47,37 +40,15 @@ namespace r3 {
 
 namespace {
 
-constexpr int kChunk = 64;
 constexpr int kGeoRow = 8;   // floats per geometric row: sx, sy, sxx, sxy, syy, sm, 0, 0
 
-struct FeatRec {   // 32 B: a staged list entry
-    float4 a;      // x, y, qa, qb
-    float4 b;      // qc, op, unused, 1-based list position (bits; forward only)
-};
-
-__device__ __forceinline__ QSplat load_splat(const FeatRec& r) { return feat_splat(r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y); }
-
-// consecutive logical ids on one XCD, as the forward blend places its tiles (speed only)
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nblocks)
-{
-    const uint32_t per = nblocks >> 3;
-    if (b >= per * 8) return b;
-    return (b & 7u) * per + (b >> 3);
-}
-
-struct FeatArgs {
-    const uint2* ranges;
-    const uint32_t* point_list;
-    const GRec* rec;
-    const float* final_T;
-    const uint32_t* n_contrib;
-    const uint32_t* quad_depth;
+// (the staged record's own words: b.z unused, b.w the 1-based list position in the forward)
+struct FeatArgs : WalkArgs {
     const float* features;   // [P, C]
     const float* g_out;      // backward: dL_dout [C, H*W]
-    int W, H, gx, C;
+    int C;
     int vec4;                // the feature rows can be read as float4 (C % 4 == 0 and a 16-byte aligned base)
-    uint32_t nblocks, ngroups;
-    uint32_t P, R;           // bounds of rec / features and of point_list / the slabs
+    uint32_t ngroups;
     float* out;              // forward: [C, H*W]
     float* slab_f;           // backward: [R][4][ngroups * NC]
     float* slab_g;           // backward: [R][4][ngroups][8]
@@ -105,14 +76,14 @@ __device__ __forceinline__ void load_slice(const FeatArgs& a, uint32_t id, int c
 }
 
 template <int NC>
-__device__ __forceinline__ void park_slice(float4 (*s_feat)[kChunk], int lane, const float (&f)[NC])
+__device__ __forceinline__ void park_slice(float4 (*s_feat)[kWalkChunk], int lane, const float (&f)[NC])
 {
 #pragma unroll
     for (int q = 0; q < NC / 4; q++) s_feat[q][lane] = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
 }
 
 template <int NC>
-__device__ __forceinline__ void read_slice(const float4 (*s_feat)[kChunk], int j, float (&f)[NC])
+__device__ __forceinline__ void read_slice(const float4 (*s_feat)[kWalkChunk], int j, float (&f)[NC])
 {
 #pragma unroll
     for (int q = 0; q < NC / 4; q++) {
@@ -124,81 +95,46 @@ __device__ __forceinline__ void read_slice(const float4 (*s_feat)[kChunk], int j
     }
 }
 
-__device__ __forceinline__ bool pretest(const float4& a, const float2& b, float qx0, float qy0)
-{
-    Splat mine;
-    mine.x = a.x;
-    mine.y = a.y;
-    mine.cA = a.z;
-    mine.cB = a.w;
-    mine.cC = b.x;
-    mine.op = b.y;
-    mine.r = mine.g = mine.b = 0.f;
-    return region_may_contribute(mine, qx0, qx0 + 7.f, qy0, qy0 + 7.f);
-}
-
 template <int NC>
 __global__ __launch_bounds__(64) void feat_fwd_kernel(const FeatArgs a)
 {
-    __shared__ FeatRec s_rec[kChunk];
-    __shared__ float4 s_feat[NC / 4][kChunk];
+    __shared__ WalkRec s_rec[kWalkChunk];
+    __shared__ float4 s_feat[NC / 4][kWalkChunk];
     const int lane = threadIdx.x;
-    const uint32_t wg = xcd_remap(blockIdx.x, a.nblocks);
+    const QuadLane q = quad_lane(xcd_remap(blockIdx.x, a.nblocks), lane, a.gx, a.W, a.H);
     const int c0 = (int)blockIdx.y * NC;
-    const uint32_t tile = wg >> 2;
-    const int quad = (int)(wg & 3u);
-    const int tile_x = (int)(tile % (uint32_t)a.gx), tile_y = (int)(tile / (uint32_t)a.gx);
-    const float qx0 = (float)(tile_x * kTile + (quad & 1) * 8), qy0 = (float)(tile_y * kTile + (quad >> 1) * 8);
-    const int px = tile_x * kTile + (quad & 1) * 8 + (lane & 7), py = tile_y * kTile + (quad >> 1) * 8 + (lane >> 3);
-    const float pxf = (float)px, pyf = (float)py;
-    const bool inside = px < a.W && py < a.H;
-    const size_t pix = (size_t)a.W * (size_t)py + (size_t)px;
-
-    const uint2 range = global_ptr(a.ranges)[tile];
-    // the walk: from the list's start to the deepest contributor of this quadrant, inside the list and inside the blob
-    uint32_t len = range.y > range.x ? range.y - range.x : 0u;
-    len = min(len, global_ptr(a.quad_depth)[tile * 4u + (uint32_t)quad]);
-    const uint32_t first = min(range.x, a.R);
-    const uint32_t end = first + min(len, a.R - first);
+    const WalkSpan sp = load_walk_span(a, q);
+    const uint32_t first = sp.first, end = sp.first + sp.len;
+    const float pxf = q.pxf, pyf = q.pyf;
+    const bool inside = q.inside;
+    const size_t pix = q.pix;
     const uint32_t n = inside ? global_ptr(a.n_contrib)[pix] : 0u;
     FeatPix<NC> p;
     feat_pix_init<NC>(p, inside);
 
     // software pipeline: the records of chunk k+1 are gathered into registers while chunk k is walked
-    float4 nxa = make_float4(0.f, 0.f, 0.f, 0.f);
-    float2 nxb = make_float2(0.f, 0.f);
     float nxf[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) nxf[c] = 0.f;
-    bool nxhave = false;
     auto gather = [&](uint32_t idx) {
-        nxhave = false;
-        if (idx < end) {
-            const uint32_t id = global_ptr(a.point_list)[idx];
-            if (id < a.P) {
-                const auto* g = (const R3_GLOBAL float4*)global_ptr(a.rec + id);
-                nxa = g[0];
-                nxb = *(const R3_GLOBAL float2*)(g + 1);
-                load_slice<NC>(a, id, c0, nxf);
-                nxhave = true;
-            }
-        }
+        const WalkGather g = gather_rec(a.point_list, a.rec, a.P, idx, end);
+        if (g.have) load_slice<NC>(a, g.id, c0, nxf);
+        return g;
     };
-    gather(first + (uint32_t)lane);
-    for (uint32_t base = first; base < end; base += kChunk) {
+    WalkGather nx = gather(first + (uint32_t)lane);
+    for (uint32_t base = first; base < end; base += kWalkChunk) {
         __syncthreads();
-        s_rec[lane].a = make_float4(nxa.x, nxa.y, (-0.5f * kLog2e) * nxa.z, -kLog2e * nxa.w);
-        s_rec[lane].b = make_float4((-0.5f * kLog2e) * nxb.x, nxb.y, 0.f, __uint_as_float(base - first + (uint32_t)lane + 1u));
+        s_rec[lane] = stage_rec(nx.a, nx.b, 0.f, __uint_as_float(base - first + (uint32_t)lane + 1u));
         park_slice<NC>(s_feat, lane, nxf);
-        unsigned long long mask = __ballot(nxhave && pretest(nxa, nxb, qx0, qy0));
+        unsigned long long mask = __ballot(nx.have && walk_pretest(nx.a, nx.b, q.qx0, q.qy0));
         __syncthreads();
-        gather(base + kChunk + (uint32_t)lane);
+        nx = gather(base + kWalkChunk + (uint32_t)lane);
         while (mask) {
             const int j = __builtin_ctzll(mask);
             mask &= mask - 1ull;
             float f[NC];
             read_slice<NC>(s_feat, j, f);
-            feat_step<NC>(load_splat(s_rec[j]), pxf, pyf, __float_as_uint(s_rec[j].b.w), n, f, p);
+            feat_step<NC>(load_splat(s_rec[j]), pxf, pyf, load_pos1(s_rec[j]), n, f, p);
         }
     }
     if (inside) {
@@ -251,29 +187,20 @@ __device__ __forceinline__ int feat_sum_slot(int lane)   // which of the N value
 template <int NC, bool GEOM, bool FEAT>
 __global__ __launch_bounds__(64) void feat_bwd_pixel_kernel(const FeatArgs a)
 {
-    __shared__ FeatRec s_rec[kChunk];
-    __shared__ float4 s_feat[GEOM ? NC / 4 : 1][kChunk];
-    __shared__ float s_outf[FEAT ? kChunk : 1][NC];
-    __shared__ float s_outg[GEOM ? kChunk : 1][kGeoRow];
+    __shared__ WalkRec s_rec[kWalkChunk];
+    __shared__ float4 s_feat[GEOM ? NC / 4 : 1][kWalkChunk];
+    __shared__ float s_outf[FEAT ? kWalkChunk : 1][NC];
+    __shared__ float s_outg[GEOM ? kWalkChunk : 1][kGeoRow];
     const int lane = threadIdx.x;
-    const uint32_t wg = xcd_remap(blockIdx.x, a.nblocks);
+    const QuadLane q = quad_lane(xcd_remap(blockIdx.x, a.nblocks), lane, a.gx, a.W, a.H);
     const uint32_t grp = blockIdx.y;
     const int c0 = (int)grp * NC;
-    const uint32_t tile = wg >> 2;
-    const int quad = (int)(wg & 3u);
-    const int tile_x = (int)(tile % (uint32_t)a.gx), tile_y = (int)(tile / (uint32_t)a.gx);
-    const float qx0 = (float)(tile_x * kTile + (quad & 1) * 8), qy0 = (float)(tile_y * kTile + (quad >> 1) * 8);
-    const int px = tile_x * kTile + (quad & 1) * 8 + (lane & 7), py = tile_y * kTile + (quad >> 1) * 8 + (lane >> 3);
-    const float pxf = (float)px, pyf = (float)py;
-    const bool inside = px < a.W && py < a.H;
-    const size_t pix = (size_t)a.W * (size_t)py + (size_t)px;
-
-    const uint2 range = global_ptr(a.ranges)[tile];
-    // the list inside the blob, and the part of it this quadrant walks: up to its deepest contributor
-    const uint32_t full = range.y > range.x ? range.y - range.x : 0u;
-    const uint32_t first = min(range.x, a.R);
-    const uint32_t list_len = min(full, a.R - first);
-    const uint32_t len = min(list_len, global_ptr(a.quad_depth)[tile * 4u + (uint32_t)quad]);
+    const WalkSpan sp = load_walk_span(a, q);
+    const uint32_t first = sp.first, list_len = sp.list_len, len = sp.len;
+    const int quad = q.quad;
+    const float pxf = q.pxf, pyf = q.pyf;
+    const bool inside = q.inside;
+    const size_t pix = q.pix;
     const size_t cpad = (size_t)a.ngroups * NC;
     R3_GLOBAL float* const slab_f = global_ptr(a.slab_f);
     R3_GLOBAL float* const slab_g = global_ptr(a.slab_g);
@@ -285,7 +212,7 @@ __global__ __launch_bounds__(64) void feat_bwd_pixel_kernel(const FeatArgs a)
         return reinterpret_cast<R3_GLOBAL float4*>(slab_g + (((size_t)(first + k) * 4 + (size_t)quad) * a.ngroups + grp) * kGeoRow);
     };
     // the slots behind the walk: zero rows
-    for (uint32_t k = len + (uint32_t)lane; k < list_len; k += kChunk) {
+    for (uint32_t k = len + (uint32_t)lane; k < list_len; k += kWalkChunk) {
         if (FEAT) {
             R3_GLOBAL float4* r = frow(k);
 #pragma unroll
@@ -317,38 +244,26 @@ __global__ __launch_bounds__(64) void feat_bwd_pixel_kernel(const FeatArgs a)
     }
 
     // software pipeline: the records of the next (shallower) chunk are gathered into registers while a chunk is walked
-    float4 nxa = zero4;
-    float2 nxb = make_float2(0.f, 0.f);
     float nxf[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) nxf[c] = 0.f;
-    bool nxhave = false;
     auto gather = [&](uint32_t k) {   // k: position in the list
-        nxhave = false;
-        if (k < len) {
-            const uint32_t id = global_ptr(a.point_list)[first + k];
-            if (id < a.P) {
-                const auto* g = (const R3_GLOBAL float4*)global_ptr(a.rec + id);
-                nxa = g[0];
-                nxb = *(const R3_GLOBAL float2*)(g + 1);
-                if (GEOM) load_slice<NC>(a, id, c0, nxf);
-                nxhave = true;
-            }
-        }
+        const WalkGather g = gather_rec(a.point_list + first, a.rec, a.P, k, len);
+        if (GEOM && g.have) load_slice<NC>(a, g.id, c0, nxf);
+        return g;
     };
-    const uint32_t cfirst = ((len - 1u) / kChunk) * kChunk;
-    gather(cfirst + (uint32_t)lane);
+    const uint32_t cfirst = ((len - 1u) / kWalkChunk) * kWalkChunk;
+    WalkGather nx = gather(cfirst + (uint32_t)lane);
     FeatSums<NC> sg;
     feat_sums_clear<NC>(sg);
     const int fslot = feat_sum_slot<NC>(lane), gslot = feat_sum_slot<kGeoRow>(lane);
-    for (uint32_t cbase = cfirst;; cbase -= kChunk) {
+    for (uint32_t cbase = cfirst;; cbase -= kWalkChunk) {
         __syncthreads();
-        s_rec[lane].a = make_float4(nxa.x, nxa.y, (-0.5f * kLog2e) * nxa.z, -kLog2e * nxa.w);
-        s_rec[lane].b = make_float4((-0.5f * kLog2e) * nxb.x, nxb.y, 0.f, 0.f);
+        s_rec[lane] = stage_rec(nx.a, nx.b, 0.f, 0.f);
         if (GEOM) park_slice<NC>(s_feat, lane, nxf);
-        unsigned long long mask = __ballot(nxhave && pretest(nxa, nxb, qx0, qy0));
+        unsigned long long mask = __ballot(nx.have && walk_pretest(nx.a, nx.b, q.qx0, q.qy0));
         __syncthreads();
-        if (cbase >= kChunk) gather(cbase - kChunk + (uint32_t)lane);
+        if (cbase >= kWalkChunk) nx = gather(cbase - kWalkChunk + (uint32_t)lane);
         unsigned long long contributed = 0ull;   // wave-uniform: entries of this chunk some lane blended
         while (mask) {   // back to front: highest set bit first
             const int j = 63 - __builtin_clzll(mask);
@@ -401,39 +316,6 @@ __global__ __launch_bounds__(64) void feat_bwd_pixel_kernel(const FeatArgs a)
         }
         if (cbase == 0u) break;
     }
-}
-
-// (Gaussian id, list slot) per slot of the pair capacity
-__global__ __launch_bounds__(256) void feat_keys_kernel(const GeomHeader* hdr, const uint32_t* point_list, uint32_t P, uint32_t R,
-                                                        uint32_t* keys, uint32_t* slots)
-{
-    const uint32_t num_pairs = min(global_ptr(hdr)->num_pairs, R);
-    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < R; e += gridDim.x * 256u) {
-        uint32_t key = 0xffffffffu;
-        if (e < num_pairs) {
-            const uint32_t id = global_ptr(point_list)[e];
-            if (id < P) key = id;
-        }
-        global_ptr(keys)[e] = key;
-        global_ptr(slots)[e] = e;
-    }
-}
-
-// the run of Gaussian i in the sorted keys: [lo, lo + count)
-__device__ __forceinline__ uint32_t run_of(const uint32_t* keys, uint32_t R, uint32_t i, uint32_t* count)
-{
-    uint32_t lo = 0u, hi = R;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (global_ptr(keys)[mid] < i)
-            lo = mid + 1u;
-        else
-            hi = mid;
-    }
-    uint32_t j = lo;
-    while (j < R && global_ptr(keys)[j] == i) j++;
-    *count = j - lo;
-    return lo;
 }
 
 struct FeatSumArgs {
@@ -502,10 +384,7 @@ __global__ __launch_bounds__(64) void feat_bwd_gauss_kernel(const FeatGaussArgs 
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= a.P) return;
     AuxGaussGrad o;
-    o.mean2D[0] = o.mean2D[1] = o.opacity = 0.f;
-    for (int k = 0; k < 3; k++) o.mean3D[k] = o.scale[k] = 0.f;
-    for (int k = 0; k < 4; k++) o.rot[k] = 0.f;
-    for (int k = 0; k < 6; k++) o.cov6[k] = 0.f;
+    gauss_grad_clear(o);
     if (global_ptr(a.radii)[i] > 0) {
         uint32_t count;
         const uint32_t lo = run_of(a.keys, a.R, i, &count);
@@ -556,38 +435,15 @@ __global__ __launch_bounds__(64) void feat_bwd_gauss_kernel(const FeatGaussArgs 
         }
         aux_bwd_chain<F64>(cam, rec6, sums, m3, sc, q, a.cov3D_precomp ? c6 : nullptr, o);
     }
-    if (a.dL_dmeans2D) {
-        R3_GLOBAL float* d = global_ptr(a.dL_dmeans2D) + 3 * (size_t)i;
-        d[0] = o.mean2D[0];
-        d[1] = o.mean2D[1];
-        d[2] = 0.f;
-    }
-    if (a.dL_dmeans3D) {
-        R3_GLOBAL float* d = global_ptr(a.dL_dmeans3D) + 3 * (size_t)i;
-        for (int k = 0; k < 3; k++) d[k] = o.mean3D[k];
-    }
-    if (a.dL_dopacity) global_ptr(a.dL_dopacity)[i] = o.opacity;
-    if (a.dL_dscales) {
-        R3_GLOBAL float* d = global_ptr(a.dL_dscales) + 3 * (size_t)i;
-        for (int k = 0; k < 3; k++) d[k] = o.scale[k];
-    }
-    if (a.dL_drotations) {
-        R3_GLOBAL float* d = global_ptr(a.dL_drotations) + 4 * (size_t)i;
-        for (int k = 0; k < 4; k++) d[k] = o.rot[k];
-    }
-    if (a.dL_dcov3D) {
-        R3_GLOBAL float* d = global_ptr(a.dL_dcov3D) + 6 * (size_t)i;
-        for (int k = 0; k < 6; k++) d[k] = o.cov6[k];
-    }
+    gauss_grad_store(a, i, o);
 }
 
 int group_width(int C) { return C <= 4 ? 4 : C <= 8 ? 8 : kFeatGroup; }
 
-// the workspace: the two slabs, the (id, slot) arrays before and after the sort, rocPRIM's temp storage
+// the workspace: the two slabs, then the sort's arrays and temp storage
 struct FeatWork {
     float *slab_f, *slab_g;
-    uint32_t *keys_in, *slots_in, *keys_out, *slots_out;
-    char* temp;
+    PairSortWork sort;
     char* end;
     static FeatWork carve(char* base, size_t R, int C, size_t temp_bytes)
     {
@@ -596,35 +452,15 @@ struct FeatWork {
         FeatWork w;
         w.slab_f = c.take<float>(R * 4 * groups * nc);
         w.slab_g = c.take<float>(R * 4 * groups * kGeoRow);
-        w.keys_in = c.take<uint32_t>(R);
-        w.slots_in = c.take<uint32_t>(R);
-        w.keys_out = c.take<uint32_t>(R);
-        w.slots_out = c.take<uint32_t>(R);
-        w.temp = c.take<char>(temp_bytes);
+        w.sort = PairSortWork::carve(c, R, temp_bytes);
         w.end = c.p;
         return w;
     }
 };
 
-size_t sort_temp_bytes(size_t R)   // asked once per R: the query is host work, and a captured call must not repeat it
-{
-    static std::mutex mu;
-    static std::map<size_t, size_t> known;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = known.find(R);
-    if (it != known.end()) return it->second;
-    size_t bytes = 0;
-    R3_HIP(rocprim::radix_sort_pairs(nullptr, bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                     R, 0, 32, (hipStream_t)0));
-    known[R] = bytes;
-    return bytes;
-}
-
 void check_dims(const char* what, int P, int R, int C, int width, int height)
 {
-    if (width < 1 || height < 1 || P < 0 || R < 0)
-        throw Error(std::string(what) + ": need width, height >= 1 and P, R >= 0, got P = " + std::to_string(P) + ", R = " +
-                    std::to_string(R) + ", " + std::to_string(width) + "x" + std::to_string(height));
+    check_replay_dims(what, P, R, width, height);
     if (C < 1 || C > R3DGS_FEATURE_MAX_CHANNELS)
         throw Error(std::string(what) + ": need 1 <= C <= " + std::to_string(R3DGS_FEATURE_MAX_CHANNELS) + " channels, got C = " +
                     std::to_string(C));
@@ -632,26 +468,10 @@ void check_dims(const char* what, int P, int R, int C, int width, int height)
 
 FeatArgs base_args(const PassStates& st, const TileGrid& grid, int P, int R, int width, int height, const float* features, int C)
 {
-    FeatArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.ranges = st.img.ranges;
-    a.point_list = st.bin.point_list;
-    a.rec = st.geom.rec;
-    a.final_T = st.img.final_T;
-    a.n_contrib = st.img.n_contrib;
-    a.quad_depth = st.img.quad_depth;
-    a.features = features;
-    a.W = width;
-    a.H = height;
-    a.gx = (int)grid.gx;
-    a.C = C;
-    a.vec4 = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(features) % 16 == 0);
-    a.nblocks = (uint32_t)(grid.n() * 4);
     const int nc = group_width(C);
-    a.ngroups = (uint32_t)((C + nc - 1) / nc);
-    a.P = (uint32_t)P;
-    a.R = (uint32_t)R;
-    return a;
+    const int vec4 = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(features) % 16 == 0);
+    return {walk_args_of(st, grid, P, R, width, height), features, nullptr, C, vec4, (uint32_t)((C + nc - 1) / nc), nullptr, nullptr,
+            nullptr};
 }
 
 template <bool GEOM, bool FEAT>
@@ -679,9 +499,8 @@ int r3dgs_feature_maps(int P, int R, int width, int height, char* geom_buffer, c
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
         check_dims("feature_maps", P, R, C, width, height);
-        const TileGrid grid = grid_of(width, height);
-        const size_t N = (size_t)width * height, Tn = grid.n();
-        if (Tn * 4 > 0x7fffffffull) throw Error("feature_maps: the image has too many tiles for one launch");
+        const TileGrid grid = replay_grid("feature_maps", width, height);
+        const size_t N = (size_t)width * height;
         if (!out) return 0;
         if (P == 0 || R == 0) {   // nothing was binned: nothing to walk
             R3_HIP(hipMemsetAsync(out, 0, sizeof(float) * N * (size_t)C, s));
@@ -712,7 +531,7 @@ size_t r3dgs_feature_maps_backward_workspace_bytes(int P, int R, int C, int widt
         using namespace r3;
         check_dims("feature_maps_backward_workspace_bytes", P, R, C, width, height);
         if (P == 0 || R == 0) return 0;
-        out = (size_t)reinterpret_cast<uintptr_t>(FeatWork::carve(nullptr, (size_t)R, C, sort_temp_bytes((size_t)R)).end) + kAlign;
+        out = (size_t)reinterpret_cast<uintptr_t>(FeatWork::carve(nullptr, (size_t)R, C, pair_sort_temp_bytes((size_t)R)).end) + kAlign;
         return 0;
     });
     return out;
@@ -730,17 +549,13 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
         hipStream_t s = static_cast<hipStream_t>(stream);
         check_dims("feature_maps_backward", P, R, C, width, height);
         if (P == 0) return 0;   // every output has P rows
-        const bool geom = dL_dmeans2D || dL_dmeans3D || dL_dopacity || dL_dscales || dL_drotations || dL_dcov3D;
+        const AuxBwdGeom in = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
+                               cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
+        const bool geom = in.any_output();
         const bool feat = dL_dfeatures != nullptr;
         if (R == 0 || !dL_dout) {   // nothing to walk: zeros, the blobs are not read
-            const size_t n = (size_t)P;
-            if (dL_dfeatures) R3_HIP(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)C * n, s));
-            if (dL_dmeans2D) R3_HIP(hipMemsetAsync(dL_dmeans2D, 0, sizeof(float) * 3 * n, s));
-            if (dL_dmeans3D) R3_HIP(hipMemsetAsync(dL_dmeans3D, 0, sizeof(float) * 3 * n, s));
-            if (dL_dopacity) R3_HIP(hipMemsetAsync(dL_dopacity, 0, sizeof(float) * n, s));
-            if (dL_dscales) R3_HIP(hipMemsetAsync(dL_dscales, 0, sizeof(float) * 3 * n, s));
-            if (dL_drotations) R3_HIP(hipMemsetAsync(dL_drotations, 0, sizeof(float) * 4 * n, s));
-            if (dL_dcov3D) R3_HIP(hipMemsetAsync(dL_dcov3D, 0, sizeof(float) * 6 * n, s));
+            if (dL_dfeatures) R3_HIP(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)C * (size_t)P, s));
+            aux_bwd_zero_outputs(P, in, s);
             return 0;
         }
         if (!geom && !feat) return 0;
@@ -754,12 +569,9 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
             if (!cov3D_precomp && (!scales || !rotations))
                 throw Error("feature_maps_backward: need scales and rotations, or cov3D_precomp");
         }
-        const TileGrid grid = grid_of(width, height);
-        const size_t Tn = grid.n();
-        if (Tn * 4 > 0x7fffffffull) throw Error("feature_maps_backward: the image has too many tiles for one launch");
+        const TileGrid grid = replay_grid("feature_maps_backward", width, height);
         const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
-        size_t temp = sort_temp_bytes((size_t)R);
-        const FeatWork w = FeatWork::carve(workspace, (size_t)R, C, temp);
+        const FeatWork w = FeatWork::carve(workspace, (size_t)R, C, pair_sort_temp_bytes((size_t)R));
 
         FeatArgs a = base_args(st, grid, P, R, width, height, features, C);
         a.g_out = dL_dout;
@@ -774,18 +586,14 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
             launch_pixel<false, true>(nc, a, s);
         check_launch("feature maps backward, pixel pass", s, false);
 
-        const uint32_t key_blocks = (uint32_t)std::min<size_t>(((size_t)R + 255) / 256, 4096);
-        hipLaunchKernelGGL(feat_keys_kernel, dim3(key_blocks), dim3(256), 0, s, st.geom.header, st.bin.point_list, (uint32_t)P,
-                           (uint32_t)R, w.keys_in, w.slots_in);
-        check_launch("feature maps backward, keys", s, false);
-        R3_HIP(rocprim::radix_sort_pairs(w.temp, temp, w.keys_in, w.keys_out, w.slots_in, w.slots_out, (size_t)R, 0, 32, s));
+        launch_pair_sort("feature maps backward", st, P, R, w.sort, s);
 
         if (feat) {
             FeatSumArgs f;
             f.radii = radii;
             f.tiles = st.geom.tiles;
-            f.keys = w.keys_out;
-            f.slots = w.slots_out;
+            f.keys = w.sort.keys_out;
+            f.slots = w.sort.slots_out;
             f.slab_f = w.slab_f;
             f.P = (uint32_t)P;
             f.R = (uint32_t)R;
@@ -802,8 +610,8 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
             g.rec = st.geom.rec;
             g.radii = radii;
             g.tiles = st.geom.tiles;
-            g.keys = w.keys_out;
-            g.slots = w.slots_out;
+            g.keys = w.sort.keys_out;
+            g.slots = w.sort.slots_out;
             g.slab_g = w.slab_g;
             g.view = viewmatrix;
             g.proj = projmatrix;

@@ -112,6 +112,20 @@ void reserve_forget_view(const float* viewmatrix);
 void reserve_forget_all();
 long long reserve_overflow_events(int* last_num_rendered, int* last_reserve);
 
+// the host preamble of the replay passes (`what`: the entry point's name, for the message)
+inline void check_replay_dims(const char* what, int P, int R, int width, int height)
+{
+    if (width < 1 || height < 1 || P < 0 || R < 0)
+        throw Error(std::string(what) + ": need width, height >= 1 and P, R >= 0, got P = " + std::to_string(P) + ", R = " +
+                    std::to_string(R) + ", " + std::to_string(width) + "x" + std::to_string(height));
+}
+inline TileGrid replay_grid(const char* what, int width, int height)   // a walk launches four workgroups per tile
+{
+    const TileGrid grid = grid_of(width, height);
+    if (grid.n() * 4 > 0x7fffffffull) throw Error(std::string(what) + ": the image has too many tiles for one launch");
+    return grid;
+}
+
 void profile_enable(int on);
 void profile_read(double* total_ms, int* launches);
 
