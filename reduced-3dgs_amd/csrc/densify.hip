@@ -16,22 +16,25 @@
 //         the parent (xyz and scaling of the children).  A unit inside one copied row whose source address is 16-byte aligned
 //         is one 16-byte load; every other unit is assembled from 4-byte loads.
 // The host reads the totals once between scan and move -- it has to size the destination tensors.
+// The workgroup scans, counts and ranks are block_scan.h's; the workspace carver and the tensor table row_table.h's.
 #include "../../include/r3dgs_densify.h"
 
-#include "common.h"
+#include "block_scan.h"
 #include "densify_math.h"
+#include "row_table.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+constexpr int kBlock = r3::kScanBlock;
 constexpr int kCounts = 5;                   // per plan workgroup: rows of A, B, C; clone and split decisions
 constexpr int kSegCounts = 3;                // ... of which the first three are scanned into offsets
-constexpr int kScanSpan = kBlock;            // plan workgroups the scan workgroup takes per round (= 65536 Gaussians)
 constexpr int kUnitWords = 4;                // a thread of the move kernel owns one 16-byte unit
 constexpr int kChunkWords = kBlock * kUnitWords;
 constexpr int kHeaderInts = 16;              // workspace header: the eight totals, then P
 constexpr int kMaxTensors = R3DGS_DENSIFY_MAX_TENSORS;
+constexpr long long kMaxP = r3::kMaxP;
+using r3::plan_blocks;
+static_assert(kBlock == r3::kPlanBlock && R3DGS_DENSIFY_COPY == 0, "row_table.h's grid and kind range");
 
 struct Plan {
     int* header;      // [kHeaderInts] totals (as the caller's copy) and P: the move kernel refuses a plan that is not its own
@@ -40,28 +43,19 @@ struct Plan {
     int* offsets;     // [nb][kSegCounts] exclusive, per segment
     int* map;         // [2 P] source Gaussian of every destination row (a source has at most two rows)
 };
-inline long long plan_blocks(long long P) { return (P + kBlock - 1) / kBlock; }
-inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline Plan carve_plan(char* ws, long long P)
+// The layout of the workspace; with ws == NULL only its size.
+inline size_t carve_plan(char* ws, long long P, Plan* p)
 {
     const size_t nb = (size_t)plan_blocks(P);
-    Plan p;
-    p.header = reinterpret_cast<int*>(ws);
-    ws += kHeaderInts * sizeof(int);
-    p.flags = reinterpret_cast<uint8_t*>(ws);
-    ws += round16((size_t)P);
-    p.counts = reinterpret_cast<int*>(ws);
-    ws += round16(nb * kCounts * sizeof(int));
-    p.offsets = reinterpret_cast<int*>(ws);
-    ws += round16(nb * kSegCounts * sizeof(int));
-    p.map = reinterpret_cast<int*>(ws);
-    return p;
-}
-inline size_t plan_bytes(long long P)
-{
-    const size_t nb = (size_t)plan_blocks(P);
-    return kHeaderInts * sizeof(int) + round16((size_t)P) + round16(nb * kCounts * sizeof(int)) +
-           round16(nb * kSegCounts * sizeof(int)) + round16(2 * (size_t)P * sizeof(int));
+    r3::Carver16 c{ws};
+    Plan q;
+    q.header = c.take<int>(kHeaderInts);
+    q.flags = c.take<uint8_t>((size_t)P);
+    q.counts = c.take<int>(nb * kCounts);
+    q.offsets = c.take<int>(nb * kSegCounts);
+    q.map = c.take<int>(2 * (size_t)P);
+    if (p) *p = q;
+    return c.used();
 }
 
 // Which segments a source Gaussian has a row in.
@@ -78,8 +72,7 @@ __global__ __launch_bounds__(kBlock) void plan_kernel(int P, r3::DensifyThreshol
                                                       const float* __restrict__ opacity, const float* __restrict__ max_radii,
                                                       const uint8_t* __restrict__ mask, Plan out)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * kBlock + tid;
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool in = i < P;
     uint8_t f = 0;
     if (in) {
@@ -95,62 +88,27 @@ __global__ __launch_bounds__(kBlock) void plan_kernel(int P, r3::DensifyThreshol
     }
     bool a, b, c;
     rows_of(f, in, a, b, c);
-    __shared__ int s_count[kWaves][kCounts];
+    __shared__ int s_count[kCounts][r3::kScanWaves];
     const bool flagged[kCounts] = {a, b, c, in && (f & r3::kFlagClone), in && (f & r3::kFlagSplit)};
-    int n[kCounts];
-#pragma unroll
-    for (int k = 0; k < kCounts; k++) n[k] = (int)__popcll(__ballot(flagged[k]));
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kCounts; k++) s_count[wave][k] = n[k];
-    }
-    __syncthreads();
-    if (tid < kCounts) {
-        int sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) sum += s_count[w][tid];
-        out.counts[(long long)blockIdx.x * kCounts + tid] = sum;
-    }
+    r3::block_count(flagged, s_count, out.counts + (long long)blockIdx.x * kCounts);
 }
 
 // One workgroup.  Round r takes the counts of plan workgroups r * kScanSpan + tid; the carry of the rounds before it lives in
 // every thread's registers.
 __global__ __launch_bounds__(kBlock) void scan_kernel(int P, long long nb, Plan p, int* __restrict__ totals)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ int s_wave[kWaves][kCounts];
+    const int tid = threadIdx.x;
+    __shared__ int s_wave[kCounts][r3::kScanWaves];
     int carry[kCounts] = {0, 0, 0, 0, 0};
-    for (long long b0 = 0; b0 < nb; b0 += kScanSpan) {
+    for (long long b0 = 0; b0 < nb; b0 += r3::kScanSpan) {
         const long long b = b0 + tid;
-        int v[kCounts], inc[kCounts];
-#pragma unroll
-        for (int k = 0; k < kCounts; k++) {
-            v[k] = b < nb ? p.counts[b * kCounts + k] : 0;
-            int x = v[k];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int y = __shfl_up(x, off);
-                if (lane >= off) x += y;
-            }
-            inc[k] = x;
-        }
-        if (lane == 63) {
-#pragma unroll
-            for (int k = 0; k < kCounts; k++) s_wave[wave][k] = inc[k];
-        }
+        int v[kCounts], inc[kCounts], excl[kCounts];
+        r3::scan_round_publish(p.counts, b, nb, v, inc, s_wave);
         __syncthreads();
+        r3::scan_round_combine(v, inc, s_wave, carry, excl);
 #pragma unroll
-        for (int k = 0; k < kCounts; k++) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; w++) {
-                const int s = s_wave[w][k];
-                before += w < wave ? s : 0;
-                all += s;
-            }
-            if (k < kSegCounts && b < nb) p.offsets[b * kSegCounts + k] = carry[k] + before + inc[k] - v[k];
-            carry[k] += all;
-        }
+        for (int k = 0; k < kSegCounts; k++)
+            if (b < nb) p.offsets[b * kSegCounts + k] = excl[k];
         __syncthreads();   // s_wave is rewritten by the next round
     }
     if (tid == 0) {
@@ -168,47 +126,31 @@ __global__ __launch_bounds__(kBlock) void scan_kernel(int P, long long nb, Plan 
     }
 }
 
-// The source Gaussian of every destination row.  Rank inside the workgroup: lanes below in the wave (ballot), waves below
-// in the workgroup (LDS); the workgroup's first row of each segment: the scan's offsets.
+// The source Gaussian of every destination row: the lane's rank inside the workgroup plus the workgroup's first row of each
+// segment, the scan's offsets.
 __global__ __launch_bounds__(kBlock) void map_kernel(int P, Plan p)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * kBlock + tid;
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool in = i < P;
     const uint8_t f = in ? p.flags[i] : 0;
     bool row[kSegCounts];
     rows_of(f, in, row[0], row[1], row[2]);
-    __shared__ int s_count[kWaves][kSegCounts];
+    __shared__ int s_count[kSegCounts][r3::kScanWaves];
     int rank[kSegCounts];
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int k = 0; k < kSegCounts; k++) {
-        const unsigned long long m = __ballot(row[k]);
-        rank[k] = __popcll(m & below);
-        if (lane == 0) s_count[wave][k] = __popcll(m);
-    }
-    __syncthreads();
+    r3::block_rank(row, s_count, rank);
     const int nA = p.header[0], nB = p.header[1], nC = p.header[2];
     const int first[kSegCounts] = {0, nA, nA + nB};
 #pragma unroll
     for (int k = 0; k < kSegCounts; k++) {
         if (!row[k]) continue;
-        int r = rank[k] + p.offsets[(long long)blockIdx.x * kSegCounts + k];
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) r += w < wave ? s_count[w][k] : 0;
+        const int r = rank[k] + p.offsets[(long long)blockIdx.x * kSegCounts + k];
         p.map[first[k] + r] = (int)i;
         if (k == 2) p.map[first[k] + nC + r] = (int)i;   // segment D: the second child, same rank
     }
 }
 
-struct Entry {
-    const uint32_t* src;
-    uint32_t* dst;
-    long long chunk_begin;   // first workgroup of this tensor
-    long long words;         // destination words
-    int W;                   // words per row
-    int kind;                // R3DGS_DENSIFY_*
-    int dst_vec, src_vec;    // the base is 16-byte aligned
+struct Entry : r3::RowEntry {
+    int dst_vec, src_vec;   // the base is 16-byte aligned
 };
 struct MoveTable {
     int n, P, nA, nB, nC, pad;
@@ -241,9 +183,7 @@ __global__ __launch_bounds__(kBlock) void move_kernel(const MoveTable t)
     // a plan made for other sizes than the caller claims: write nothing rather than follow a map that is not there
     if (t.header[0] != t.nA || t.header[1] != t.nB || t.header[2] != t.nC || t.header[R3DGS_DENSIFY_TOTALS] != t.P) return;
     const long long b = blockIdx.x;
-    int ei = 0;
-    while (ei + 1 < t.n && t.e[ei + 1].chunk_begin <= b) ei++;
-    const Entry& e = t.e[ei];
+    const Entry& e = t.e[r3::entry_of(t.e, t.n, b)];
     const int W = e.W;
     const long long block_first = (b - e.chunk_begin) * kChunkWords;   // wave-uniform: one 64-bit divide per workgroup
     const long long block_row = block_first / W;
@@ -293,8 +233,6 @@ __global__ __launch_bounds__(kBlock) void move_kernel(const MoveTable t)
     }
 }
 
-constexpr long long kMaxP = 1LL << 30;   // 2 P destination rows are counted in int32
-
 void check_plan_args(const char* what, int P, const char* workspace, const int* totals)
 {
     if (P > kMaxP) throw r3::Error(std::string(what) + ": P exceeds 2^30");
@@ -324,7 +262,7 @@ extern "C" {
 size_t r3dgs_densify_workspace_bytes(int P)
 {
     if (P <= 0 || P > kMaxP) return 0;
-    return plan_bytes(P);
+    return carve_plan(nullptr, P, nullptr);
 }
 
 int r3dgs_densify_plan(int P, int densify, const float* accum, const float* denom, const float* scaling, const float* opacity,
@@ -354,7 +292,8 @@ int r3dgs_densify_plan(int P, int densify, const float* accum, const float* deno
         t.world_scale = world_scale;
         t.densify = densify ? 1 : 0;
         t.screen = screen ? 1 : 0;
-        const Plan plan = carve_plan(workspace, P);
+        Plan plan;
+        carve_plan(workspace, P, &plan);
         plan_kernel<false><<<(unsigned)plan_blocks(P), kBlock, 0, s>>>(P, t, accum, denom, scaling, opacity, max_radii2D, nullptr,
                                                                        plan);
         r3::check_launch("densify plan", s, false);
@@ -375,7 +314,8 @@ int r3dgs_prune_plan(int P, const uint8_t* mask, char* workspace, int* totals, v
         }
         check_plan_args("prune_plan", P, workspace, totals);
         if (!mask) throw r3::Error("prune_plan: mask is NULL");
-        const Plan plan = carve_plan(workspace, P);
+        Plan plan;
+        carve_plan(workspace, P, &plan);
         plan_kernel<true><<<(unsigned)plan_blocks(P), kBlock, 0, s>>>(P, r3::DensifyThresholds{}, nullptr, nullptr, nullptr, nullptr,
                                                                       nullptr, mask, plan);
         r3::check_launch("prune plan", s, false);
@@ -398,7 +338,8 @@ int r3dgs_densify_move(int P, int nA, int nB, int nC, int n, const r3dgs_densify
         if (!workspace || (uintptr_t)workspace % 16) throw r3::Error("densify_move: workspace is NULL or not 16-byte aligned");
         if (nC > 0 && (!xyz || !scaling || !rotation || !noise))
             throw r3::Error("densify_move: split rows need xyz, scaling, rotation and noise");
-        const Plan plan = carve_plan(const_cast<char*>(workspace), P);
+        Plan plan;
+        carve_plan(const_cast<char*>(workspace), P, &plan);
         MoveTable t{};
         t.P = P;
         t.nA = nA;
@@ -410,28 +351,16 @@ int r3dgs_densify_move(int P, int nA, int nB, int nC, int n, const r3dgs_densify
         t.scaling = scaling;
         t.rotation = rotation;
         t.noise = noise;
-        long long chunks = 0;
-        for (int i = 0; i < n; i++) {
-            const r3dgs_densify_tensor& x = tensors[i];
-            const std::string where = "densify_move: tensor " + std::to_string(i);
-            if (x.row_words < 0 || x.row_words > (1 << 20)) throw r3::Error(where + ": row_words out of range");
-            if (x.kind < R3DGS_DENSIFY_COPY || x.kind > R3DGS_DENSIFY_SCALING) throw r3::Error(where + ": unknown kind");
-            if ((x.kind == R3DGS_DENSIFY_XYZ || x.kind == R3DGS_DENSIFY_SCALING) && x.row_words != 3)
-                throw r3::Error(where + ": xyz and scaling rows have 3 words");
-            if (x.row_words == 0) continue;
-            if (!x.src || !x.dst) throw r3::Error(where + ": src or dst is NULL");
-            if ((uintptr_t)x.src % 4 || (uintptr_t)x.dst % 4) throw r3::Error(where + ": not 4-byte aligned");
-            Entry& e = t.e[t.n++];
-            e.src = static_cast<const uint32_t*>(x.src);
-            e.dst = static_cast<uint32_t*>(x.dst);
-            e.chunk_begin = chunks;
-            e.words = rows * x.row_words;
-            e.W = x.row_words;
-            e.kind = x.kind;
-            e.dst_vec = (uintptr_t)x.dst % 16 == 0;
-            e.src_vec = (uintptr_t)x.src % 16 == 0;
-            chunks += (e.words + kChunkWords - 1) / kChunkWords;
-            if (chunks >= (1LL << 31)) throw r3::Error("densify_move: too many elements in one launch");
+        const long long chunks = r3::fill_entries(
+            "densify_move", tensors, n, rows, kChunkWords, R3DGS_DENSIFY_SCALING,
+            [](int kind, int row_words) {
+                const bool child = kind == R3DGS_DENSIFY_XYZ || kind == R3DGS_DENSIFY_SCALING;
+                return child && row_words != 3 ? ": xyz and scaling rows have 3 words" : nullptr;
+            },
+            nullptr, t.e, t.n);
+        for (int i = 0; i < t.n; i++) {
+            t.e[i].dst_vec = (uintptr_t)t.e[i].dst % 16 == 0;
+            t.e[i].src_vec = (uintptr_t)t.e[i].src % 16 == 0;
         }
         if (chunks == 0) return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);

@@ -7,7 +7,7 @@
 //           formed: v = R^T n, v_j *= s_j^2, R v.
 //   plan    weights  one lane per Gaussian: its weight (fp32 sigmoid, 0 for a dead row), ratio = 1, and per workgroup the
 //                    double sum of the weights (a fixed tree) and the counts of dead rows and of rows of positive weight.
-//           scan     ONE workgroup walks the per-workgroup sums and counts in rounds of kScanSpan (as densify.hip's) and
+//           scan     ONE workgroup walks the per-workgroup sums and counts in rounds of kScanSpan (block_scan.h) and
 //                    writes the header: total weight, dead, positive, draws, the no-op flag.
 //           cdf      one lane per Gaussian again: cdf = workgroup offset + the same tree's inclusive value; a row of positive
 //                    weight writes (cdf, index) at its rank among the positive rows, a dead row writes its index into slots.
@@ -18,19 +18,22 @@
 //   move    values   one lane per Gaussian: a drawn source's new raw opacity and scaling, into the workspace -- so that no
 //                    row of the in-place relocation is read while it is half-written.
 //           relocate / grow   one thread per 4-byte word of every tensor of the table.
+// The workgroup scans, counts and ranks are block_scan.h's; the workspace carver and the tensor table row_table.h's.
 #include "../../include/r3dgs_mcmc.h"
 
-#include "common.h"
+#include "block_scan.h"
 #include "mcmc_math.h"
+#include "row_table.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kScanSpan = kBlock;   // plan workgroups the scan workgroup takes per round (= 65536 Gaussians)
+constexpr int kBlock = r3::kScanBlock;
+constexpr int kWaves = r3::kScanWaves;
 constexpr int kMaxTensors = R3DGS_MCMC_MAX_TENSORS;
-constexpr long long kMaxP = 1LL << 30;
+constexpr long long kMaxP = r3::kMaxP;
 constexpr int kValWords = 4;        // new raw opacity, three new raw scales
+using r3::plan_blocks;
+static_assert(kBlock == r3::kPlanBlock && R3DGS_MCMC_COPY == 0, "row_table.h's grid and kind range");
 
 __constant__ r3::McmcBinom kBinom = r3::make_mcmc_binom();
 
@@ -51,28 +54,22 @@ struct Plan {
     int* idx;        // [pos] their indices
     float* vals;     // [P][kValWords] new raw opacity and scaling of the drawn sources (move)
 };
-inline long long plan_blocks(long long P) { return (P + kBlock - 1) / kBlock; }
-inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+// The layout of the workspace; with ws == NULL only its size.
 inline size_t carve_plan(char* ws, long long P, Plan* p)
 {
     const size_t nb = (size_t)plan_blocks(P);
-    char* at = ws;
-    auto take = [&](size_t bytes) {
-        char* r = at;
-        at += round16(bytes);
-        return r;
-    };
+    r3::Carver16 c{ws};
     Plan q;
-    q.header = reinterpret_cast<Header*>(take(sizeof(Header)));
-    q.sums = reinterpret_cast<double*>(take(nb * sizeof(double)));
-    q.soff = reinterpret_cast<double*>(take(nb * sizeof(double)));
-    q.cdf = reinterpret_cast<double*>(take((size_t)P * sizeof(double)));
-    q.counts = reinterpret_cast<int*>(take(nb * 2 * sizeof(int)));
-    q.offs = reinterpret_cast<int*>(take(nb * 2 * sizeof(int)));
-    q.idx = reinterpret_cast<int*>(take((size_t)P * sizeof(int)));
-    q.vals = reinterpret_cast<float*>(take((size_t)P * kValWords * sizeof(float)));
+    q.header = c.take<Header>(1);
+    q.sums = c.take<double>(nb);
+    q.soff = c.take<double>(nb);
+    q.cdf = c.take<double>((size_t)P);
+    q.counts = c.take<int>(nb * 2);
+    q.offs = c.take<int>(nb * 2);
+    q.idx = c.take<int>((size_t)P);
+    q.vals = c.take<float>((size_t)P * kValWords);
     if (p) *p = q;
-    return (size_t)(at - ws);
+    return c.used();
 }
 
 // ---- noise ----------------------------------------------------------------------------------------------------------------
@@ -104,97 +101,42 @@ __global__ __launch_bounds__(kBlock) void noise_kernel(int P, float* __restrict_
 
 // ---- plan -----------------------------------------------------------------------------------------------------------------
 
-// Inclusive scan of x over the workgroup in a fixed tree: shuffles inside a wave, the waves' totals in wave order.  Every
-// thread of the workgroup calls it; s_wave: kWaves doubles of LDS.  -> the lane's inclusive value; total: the workgroup's.
-__device__ __forceinline__ double block_scan(double x, double* s_wave, double& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    double before = 0.0, all = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) {
-        const double s = s_wave[w];
-        before += w < wave ? s : 0.0;
-        all += s;
-    }
-    total = all;
-    return before + x;
-}
-
 __global__ __launch_bounds__(kBlock) void weights_kernel(int P, const float* __restrict__ opacity, float min_opacity, int relocate,
                                                          int* __restrict__ ratio, Plan out)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * kBlock + tid;
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool in = i < P;
     bool dead = false;
     const float w = in ? r3::mcmc_weight(opacity[i], min_opacity, relocate, dead) : 0.f;
     if (in) ratio[i] = 1;
     __shared__ double s_wave[kWaves];
-    __shared__ int s_count[kWaves][2];
+    __shared__ int s_count[2][kWaves];
     double total;
-    block_scan((double)w, s_wave, total);
-    const int nd = (int)__popcll(__ballot(dead)), np = (int)__popcll(__ballot(w > 0.f));
-    if (lane == 0) {
-        s_count[wave][0] = nd;
-        s_count[wave][1] = np;
-    }
-    __syncthreads();
-    if (tid < 2) {
-        int sum = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; k++) sum += s_count[k][tid];
-        out.counts[(long long)blockIdx.x * 2 + tid] = sum;
-    }
-    if (tid == 0) out.sums[blockIdx.x] = total;
+    r3::block_scan((double)w, s_wave, total);
+    const bool flag[2] = {dead, w > 0.f};
+    r3::block_count(flag, s_count, out.counts + (long long)blockIdx.x * 2);
+    if (threadIdx.x == 0) out.sums[blockIdx.x] = total;
 }
 
 // One workgroup.  Round r takes plan workgroups r * kScanSpan + tid; the carries live in every thread's registers.
 __global__ __launch_bounds__(kBlock) void scan_kernel(int P, int mode, int n_draws, long long nb, Plan p, int* __restrict__ totals)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ int s_int[kWaves][2];
+    __shared__ int s_int[2][kWaves];
     __shared__ double s_wave[kWaves];
     int carry[2] = {0, 0};
     double wcarry = 0.0;
-    for (long long b0 = 0; b0 < nb; b0 += kScanSpan) {
+    for (long long b0 = 0; b0 < nb; b0 += r3::kScanSpan) {
         const long long b = b0 + tid;
-        int v[2], inc[2];
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            v[k] = b < nb ? p.counts[b * 2 + k] : 0;
-            int x = v[k];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int y = __shfl_up(x, off);
-                if (lane >= off) x += y;
-            }
-            inc[k] = x;
-        }
-        if (lane == 63) {
-            s_int[wave][0] = inc[0];
-            s_int[wave][1] = inc[1];
-        }
+        int v[2], inc[2], off[2];
+        r3::scan_round_publish(p.counts, b, nb, v, inc, s_int);
         const double wv = b < nb ? p.sums[b] : 0.0;
         double wall;
-        const double winc = block_scan(wv, s_wave, wall);   // its barrier also publishes s_int
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; w++) {
-                const int s = s_int[w][k];
-                before += w < wave ? s : 0;
-                all += s;
-            }
-            if (b < nb) p.offs[b * 2 + k] = carry[k] + before + inc[k] - v[k];
-            carry[k] += all;
+        const double winc = r3::block_scan(wv, s_wave, wall);   // its barrier also publishes s_int
+        r3::scan_round_combine(v, inc, s_int, carry, off);
+        if (b < nb) {
+            p.offs[b * 2] = off[0];
+            p.offs[b * 2 + 1] = off[1];
         }
         // the offset of workgroup b: everything before the round, plus the round's inclusive value of workgroup b - 1 (the
         // exclusive value is never formed by a subtraction)
@@ -230,31 +172,21 @@ __global__ __launch_bounds__(kBlock) void scan_kernel(int P, int mode, int n_dra
 __global__ __launch_bounds__(kBlock) void cdf_kernel(int P, const float* __restrict__ opacity, float min_opacity, int relocate,
                                                      int* __restrict__ slots, Plan p)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * kBlock + tid;
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool in = i < P;
     bool dead = false;
     const float w = in ? r3::mcmc_weight(opacity[i], min_opacity, relocate, dead) : 0.f;
     __shared__ double s_wave[kWaves];
-    __shared__ int s_count[kWaves][2];
+    __shared__ int s_count[2][kWaves];
     double total;
-    const double inc = block_scan((double)w, s_wave, total);
+    const double inc = r3::block_scan((double)w, s_wave, total);
     const bool flag[2] = {dead, w > 0.f};
-    const unsigned long long below = (1ull << lane) - 1ull;
     int rank[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const unsigned long long m = __ballot(flag[k]);
-        rank[k] = __popcll(m & below);
-        if (lane == 0) s_count[wave][k] = __popcll(m);
-    }
-    __syncthreads();
+    r3::block_rank(flag, s_count, rank);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         if (!flag[k]) continue;
-        int r = rank[k] + p.offs[(long long)blockIdx.x * 2 + k];
-#pragma unroll
-        for (int v = 0; v < kWaves; v++) r += v < wave ? s_count[v][k] : 0;
+        const int r = rank[k] + p.offs[(long long)blockIdx.x * 2 + k];
         if (r < 0 || r >= P) continue;   // cannot happen with the scan's own offsets
         if (k == 0) {
             if (slots) slots[r] = (int)i;
@@ -318,14 +250,7 @@ __global__ __launch_bounds__(kBlock) void values_kernel(int P, const float* __re
     vals[kValWords * i + 3] = ns[2];
 }
 
-struct Entry {
-    const uint32_t* src;
-    uint32_t* dst;
-    long long chunk_begin;   // first workgroup of this tensor
-    long long words;         // words the launch walks: P rows (RELOCATE) or P + n_new rows (GROW)
-    int W;                   // words per row
-    int kind;                // R3DGS_MCMC_*
-};
+using Entry = r3::RowEntry;   // words: P rows (RELOCATE) or P + n_new rows (GROW)
 struct MoveTable {
     int n, P, n_new, zero_relocated;
     const int *sampled, *slots, *ratio, *totals;
@@ -345,8 +270,7 @@ __device__ __forceinline__ uint32_t updated_word(const MoveTable& t, const Entry
 __device__ __forceinline__ bool locate(const MoveTable& t, int& ei, long long& g)
 {
     const long long b = blockIdx.x;
-    ei = 0;
-    while (ei + 1 < t.n && t.e[ei + 1].chunk_begin <= b) ei++;
+    ei = r3::entry_of(t.e, t.n, b);
     g = (b - t.e[ei].chunk_begin) * kBlock + threadIdx.x;
     return g < t.e[ei].words;
 }
@@ -493,29 +417,17 @@ int r3dgs_mcmc_move(int P, int mode, int n_new, int zero_relocated, float min_op
         t.totals = totals;
         t.vals = reinterpret_cast<const uint32_t*>(plan.vals);
         const long long rows = (long long)P + n_new;
-        long long chunks = 0;
-        for (int i = 0; i < n; i++) {
-            const r3dgs_mcmc_tensor& x = tensors[i];
-            const std::string where = "mcmc_move: tensor " + std::to_string(i);
-            if (x.row_words < 0 || x.row_words > (1 << 20)) throw r3::Error(where + ": row_words out of range");
-            if (x.kind < R3DGS_MCMC_COPY || x.kind > R3DGS_MCMC_SCALING) throw r3::Error(where + ": unknown kind");
-            if (x.kind == R3DGS_MCMC_OPACITY && x.row_words != 1) throw r3::Error(where + ": opacity rows have 1 word");
-            if (x.kind == R3DGS_MCMC_SCALING && x.row_words != 3) throw r3::Error(where + ": scaling rows have 3 words");
-            if (x.row_words == 0) continue;
-            if (!x.src || !x.dst) throw r3::Error(where + ": src or dst is NULL");
-            if ((uintptr_t)x.src % 4 || (uintptr_t)x.dst % 4) throw r3::Error(where + ": not 4-byte aligned");
-            if (relocate && x.src != x.dst) throw r3::Error(where + ": relocation is in place, src must equal dst");
-            if (!relocate && x.src == x.dst) throw r3::Error(where + ": growth writes new tensors, src must differ from dst");
-            Entry& e = t.e[t.n++];
-            e.src = static_cast<const uint32_t*>(x.src);
-            e.dst = static_cast<uint32_t*>(x.dst);
-            e.chunk_begin = chunks;
-            e.words = rows * x.row_words;
-            e.W = x.row_words;
-            e.kind = x.kind;
-            chunks += (e.words + kBlock - 1) / kBlock;
-            if (chunks >= (1LL << 31)) throw r3::Error("mcmc_move: too many elements in one launch");
-        }
+        const long long chunks = r3::fill_entries(
+            "mcmc_move", tensors, n, rows, kBlock, R3DGS_MCMC_SCALING,
+            [](int kind, int row_words) -> const char* {
+                if (kind == R3DGS_MCMC_OPACITY && row_words != 1) return ": opacity rows have 1 word";
+                return kind == R3DGS_MCMC_SCALING && row_words != 3 ? ": scaling rows have 3 words" : nullptr;
+            },
+            [relocate](const void* src, const void* dst) -> const char* {
+                if (relocate && src != dst) return ": relocation is in place, src must equal dst";
+                return !relocate && src == dst ? ": growth writes new tensors, src must differ from dst" : nullptr;
+            },
+            t.e, t.n);
         hipStream_t s = static_cast<hipStream_t>(stream);
         values_kernel<<<(unsigned)plan_blocks(P), kBlock, 0, s>>>(P, opacity_raw, scaling_raw, ratio, min_opacity, plan.vals);
         r3::check_launch("mcmc values", s, false);

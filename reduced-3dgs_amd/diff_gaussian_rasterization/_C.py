@@ -39,12 +39,11 @@ class _AdamCapturableSegment(C.Structure):   # r3dgs_adam_capturable_segment (in
                 ("n", _ll), ("lr_value", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
-class _DensifyTensor(C.Structure):   # r3dgs_densify_tensor (include/r3dgs_densify.h); filled by r3dgs_densify.py
+class _DensifyTensor(C.Structure):   # r3dgs_densify_tensor (include/r3dgs_densify.h); filled by r3dgs_model_state.fill_table
     _fields_ = [("src", _vp), ("dst", _vp), ("row_words", _i), ("kind", _i)]
 
 
-class _McmcTensor(C.Structure):   # r3dgs_mcmc_tensor (include/r3dgs_mcmc.h), the same shape; filled by r3dgs_mcmc.py
-    _fields_ = [("src", _vp), ("dst", _vp), ("row_words", _i), ("kind", _i)]
+_McmcTensor = _DensifyTensor   # r3dgs_mcmc_tensor (include/r3dgs_mcmc.h): the same shape, so the same class
 
 
 # ---- the C ABI of libr3dgs_hip.so, once: {group: (sentence, {name: (restype, [argtypes])})}, a row for every prototype under

@@ -38,10 +38,9 @@ graph; nothing else waits.  No empty_cache().  P == 0 before or after is valid. 
 are non-contiguous tensors, wrong dtypes and tensors whose first dimension is not P.  n_points_cloned, n_points_split and
 n_points_pruned are stored as Python ints.
 """
-import numpy as np
 import torch
-from torch import nn
 
+import r3dgs_model_state as ms
 from diff_gaussian_rasterization import _C
 
 __all__ = ["densify_and_prune", "prune", "prune_points"]
@@ -52,111 +51,10 @@ _C._need("densify", ImportError)
 COPY, ZERO_NEW, XYZ, SCALING = 0, 1, 2, 3     # R3DGS_DENSIFY_*
 MAX_TENSORS, TOTALS = 32, 8
 
-
 _Tensor = _C._DensifyTensor   # r3dgs_densify_tensor: the struct sits next to the table that declares the pointer to it
-
-_GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
-           ("scaling", "_scaling"), ("rotation", "_rotation"))
-_NAMES = {name for name, _ in _GROUPS}
+_GROUPS = ms.GROUPS
 _CHILD_KIND = {"xyz": XYZ, "scaling": SCALING}
-_ACCUMULATORS = ("xyz_gradient_accum", "denom", "max_radii2D")
-
-
-def _check(what, name, t, dtype, P):
-    """dtype and shape first, so that a wrong tensor is named for what is wrong with it wherever it lives"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{what}: {name} is {t.dtype}, expected {dtype}")
-    if t.dim() < 1 or t.shape[0] != P:
-        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected [P, ...] with P = {P}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: {name} is not contiguous; densification takes contiguous tensors only")
-
-
-def _check_extra(what, name, t, dtype, shape, shape_text):
-    """noise and mask: looked at before the model's tensors, except for where they live"""
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-        raise TypeError(f"{what}: {name} must be a {dtype} tensor")
-    if tuple(t.shape) != shape:
-        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape_text}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: {name} is not contiguous; densification takes contiguous tensors only")
-
-
-def _model_size(what, pc):
-    xyz = pc._xyz
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2:
-        raise TypeError(f"{what}: pc._xyz must be a [P,3] tensor")
-    return xyz.shape[0]
-
-
-def _collect(what, pc, store_grads, accumulators):
-    """-> (P, device, entries): entries are (kind, source tensor, setter of the new tensor), in table order.  Every refusal
-    comes from here, before anything is launched or changed: dtypes, shapes and layouts of all tensors first, then where
-    they live."""
-    P = _model_size(what, pc)
-    xyz = pc._xyz
-    widths = {"xyz": (3,), "opacity": (1,), "scaling": (3,), "rotation": (4,)}
-    groups = {}
-    for group in pc.optimizer.param_groups:
-        name = group.get("name")
-        if name not in _NAMES or len(group["params"]) != 1:
-            raise ValueError(f"{what}: the optimizer must have one single-parameter group per name in {sorted(_NAMES)}; "
-                             f"found {name!r} with {len(group['params'])} parameters")
-        groups[name] = group
-    entries = []
-    for name, attr in _GROUPS:
-        if name not in groups:
-            raise ValueError(f"{what}: the optimizer has no group named {name!r}")
-        group = groups[name]
-        p = group["params"][0]
-        if getattr(pc, attr) is not p:
-            raise ValueError(f"{what}: pc.{attr} is not the parameter of the optimizer's group {name!r}")
-        _check(what, f"pc.{attr}", p, torch.float32, P)
-        if name in widths and tuple(p.shape[1:]) != widths[name]:
-            raise ValueError(f"{what}: pc.{attr} has shape {tuple(p.shape)}, expected {(P,) + widths[name]}")
-        state = pc.optimizer.state.get(p, None)
-        entries.append((_CHILD_KIND.get(name, COPY), p.detach(), ("param", group, attr, state)))
-        if state is not None:
-            for key in ("exp_avg", "exp_avg_sq"):
-                if key not in state:
-                    raise ValueError(f"{what}: the optimizer state of group {name!r} has no {key}")
-                _check(what, f"{key} of group {name!r}", state[key], torch.float32, P)
-                if state[key].shape != p.shape:
-                    raise ValueError(f"{what}: {key} of group {name!r} has shape {tuple(state[key].shape)}, its parameter "
-                                     f"{tuple(p.shape)}")
-                entries.append((ZERO_NEW, state[key], ("state", state, key)))
-            if store_grads:
-                if p.grad is None:
-                    raise ValueError(f"{what}: store_grads=True but pc.{attr} has no .grad")
-                _check(what, f"pc.{attr}.grad", p.grad, torch.float32, P)
-                if p.grad.shape != p.shape:
-                    raise ValueError(f"{what}: pc.{attr}.grad has shape {tuple(p.grad.shape)}, its parameter {tuple(p.shape)}")
-                entries.append((ZERO_NEW, p.grad, ("grad", group)))
-    _check(what, "pc._degrees", pc._degrees, torch.int32, P)
-    entries.append((COPY, pc._degrees, ("attr", "_degrees")))
-    for name in _ACCUMULATORS:
-        t = getattr(pc, name)
-        _check(what, f"pc.{name}", t, torch.float32, P)
-        if t.numel() != P:
-            raise ValueError(f"{what}: pc.{name} has shape {tuple(t.shape)}, expected {P} elements")
-        if accumulators:
-            entries.append((COPY, t, ("attr", name)))
-    dev = xyz.device
-    for t in [e[1] for e in entries] + [getattr(pc, name) for name in _ACCUMULATORS]:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: the model has host tensors; densification needs device tensors (no CPU path)")
-        if t.device != dev:
-            raise ValueError(f"{what}: a tensor is on {t.device}, pc._xyz on {dev}")
-    if len(entries) > MAX_TENSORS:
-        raise RuntimeError(f"{what}: more than {MAX_TENSORS} tensors")
-    return P, dev, entries
-
-
-def _f32(x):
-    """a Python double rounded to float32 once, as torch rounds the scalar it compares a float32 tensor with"""
-    return float(np.float32(x))
+_f32 = ms.f32
 
 
 def _run(what, pc, entries, P, dev, plan, noise, zero_accumulators):
@@ -172,36 +70,13 @@ def _run(what, pc, entries, P, dev, plan, noise, zero_accumulators):
         else:
             ws, totals = None, [0] * TOTALS
         nA, nB, nC, _, _, _, _, rows = totals
-        new = [torch.empty((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for _, t, _ in entries]
+        new = ms.new_rows(entries, rows, dev)
         if rows > 0:
-            table = (_Tensor * len(entries))()
-            for slot, (kind, t, _), out in zip(table, entries, new):
-                words = t.numel() // P
-                slot.src, slot.dst, slot.row_words, slot.kind = (t.data_ptr() if words else None), \
-                    (out.data_ptr() if words else None), words, kind
+            table = ms.fill_table(_Tensor, entries, new, P)
             _C._check(_lib.r3dgs_densify_move(P, nA, nB, nC, len(entries), table, pc._xyz.data_ptr(), pc._scaling.data_ptr(),
                                               pc._rotation.data_ptr(), noise.data_ptr() if noise is not None else None,
                                               ws.data_ptr(), stream), what)
-        # hand-over, as _prune_optimizer / cat_tensors_to_optimizer: the same state dict under the new parameter
-        params = {}
-        for (_, _, dest), out in zip(entries, new):
-            if dest[0] == "param":
-                _, group, attr, state = dest
-                old = group["params"][0]
-                if state is not None:
-                    del pc.optimizer.state[old]
-                p = nn.Parameter(out.requires_grad_(True))
-                group["params"][0] = p
-                if state is not None:
-                    pc.optimizer.state[p] = state
-                setattr(pc, attr, p)
-                params[id(group)] = p
-            elif dest[0] == "state":
-                dest[1][dest[2]] = out
-            elif dest[0] == "grad":
-                params[id(dest[1])].grad = out
-            else:
-                setattr(pc, dest[1], out)
+        ms.hand_over(pc, entries, new)
         if zero_accumulators:   # densification_postfix, gaussian_model.py:617-620
             pc.xyz_gradient_accum = torch.zeros((rows, 1), device=dev)
             pc.density_gradient_accum = torch.zeros((rows, 1), device=dev)
@@ -219,14 +94,13 @@ def densify_and_prune(pc, max_grad, min_opacity, extent, max_screen_size, densif
         raise ValueError(f"{what}: max_grad = {max_grad!r} must be > 0 (the reference takes the split decision after the clones "
                          "were appended with a zero gradient: max_grad <= 0 would split the clones)")
     if noise is not None:
-        P = _model_size(what, pc)
-        _check_extra(what, "noise", noise, torch.float32, (2, P, 3), f"(2, P, 3) with P = {P}")
-    P, dev, entries = _collect(what, pc, store_grads, accumulators=False)
+        P = ms.model_size(what, pc)
+        ms.check_extra(what, "noise", noise, torch.float32, (2, P, 3), f"(2, P, 3) with P = {P}")
+    P, dev, entries = ms.collect(what, pc, _CHILD_KIND, ZERO_NEW, store_grads, accumulators=False)
     if noise is None:
         noise = torch.randn((2, P, 3), generator=generator, device=dev, dtype=torch.float32)
-    elif noise.device != dev:
-        raise RuntimeError(f"{what}: noise is on {noise.device}, pc._xyz on {dev}; densification needs device tensors "
-                           "(no CPU path)")
+    else:
+        ms.check_extra_device(what, "noise", noise, dev)
     thresholds = (_f32(max_grad), _f32(pc.percent_dense * extent), _f32(min_opacity), 1 if max_screen_size else 0,
                   _f32(max_screen_size) if max_screen_size else 0.0, _f32(0.1 * extent))
 
@@ -243,7 +117,7 @@ def prune(pc, min_opacity, extent, max_screen_size, densification_statistics_dic
     """GaussianModel.prune (scene/gaussian_model.py:684-691) called on its own: the screen-size term sees max_radii2D as it
     is, and the three accumulators are compacted with the parameters."""
     what = "prune"
-    P, dev, entries = _collect(what, pc, store_grads, accumulators=True)
+    P, dev, entries = ms.collect(what, pc, _CHILD_KIND, ZERO_NEW, store_grads, accumulators=True)
     thresholds = (1.0, 0.0, _f32(min_opacity), 1 if max_screen_size else 0, _f32(max_screen_size) if max_screen_size else 0.0,
                   _f32(0.1 * extent))
 
@@ -258,12 +132,10 @@ def prune_points(pc, mask, store_grads=False):
     """GaussianModel.prune_points (scene/gaussian_model.py:553-568): removes the Gaussians with mask True.  mask: bool [P] on
     the device (what mercy_points builds in torch)."""
     what = "prune_points"
-    P = _model_size(what, pc)
-    _check_extra(what, "mask", mask, torch.bool, (P,), f"(P,) with P = {P}")
-    P, dev, entries = _collect(what, pc, store_grads, accumulators=True)
-    if mask.device != dev:
-        raise RuntimeError(f"{what}: mask is on {mask.device}, pc._xyz on {dev}; densification needs device tensors "
-                           "(no CPU path)")
+    P = ms.model_size(what, pc)
+    ms.check_extra(what, "mask", mask, torch.bool, (P,), f"(P,) with P = {P}")
+    P, dev, entries = ms.collect(what, pc, _CHILD_KIND, ZERO_NEW, store_grads, accumulators=True)
+    ms.check_extra_device(what, "mask", mask, dev)
 
     def plan(ws, totals, stream):
         return _lib.r3dgs_prune_plan(P, mask.data_ptr(), ws, totals, stream)

@@ -24,11 +24,9 @@ None), `uniforms` float32 in [0,1) (torch.rand with `generator` when None): P en
 
 Host tensors are refused (no CPU path), as are non-contiguous tensors, wrong dtypes and tensors whose first dimension is not P.
 """
-import numpy as np
 import torch
-from torch import nn
 
-import r3dgs_densify as _dn
+import r3dgs_model_state as ms
 from diff_gaussian_rasterization import _C
 
 __all__ = ["inject_noise", "relocate", "add_new", "regularisation", "n_new_rows", "MCMCStrategy"]
@@ -41,71 +39,12 @@ COPY, MOMENT, OPACITY, SCALING = 0, 1, 2, 3    # R3DGS_MCMC_*
 MAX_TENSORS, TOTALS, MAX_RATIO = 32, 8, 51
 GROW_MIN_OPACITY = 0.005   # the lower clamp of a grown source's new opacity: the strategy's default min_opacity
 
-_GROUPS = _dn._GROUPS
 _KIND = {"opacity": OPACITY, "scaling": SCALING}
-_ACCUMULATORS = ("xyz_gradient_accum", "denom", "max_radii2D")
-_WIDTHS = {"xyz": (3,), "opacity": (1,), "scaling": (3,), "rotation": (4,)}
-
-
-def _collect(what, pc):
-    """-> (P, device, entries): entries are (kind, tensor, where it goes), in table order.  Every refusal comes from here,
-    before anything is launched or changed, in r3dgs_densify's order: dtypes, shapes and layouts of all tensors first, then
-    where they live."""
-    P = _dn._model_size(what, pc)
-    groups = {}
-    for group in pc.optimizer.param_groups:
-        name = group.get("name")
-        if name not in _dn._NAMES or len(group["params"]) != 1:
-            raise ValueError(f"{what}: the optimizer must have one single-parameter group per name in {sorted(_dn._NAMES)}; "
-                             f"found {name!r} with {len(group['params'])} parameters")
-        groups[name] = group
-    entries = []
-    for name, attr in _GROUPS:
-        if name not in groups:
-            raise ValueError(f"{what}: the optimizer has no group named {name!r}")
-        group = groups[name]
-        p = group["params"][0]
-        if getattr(pc, attr) is not p:
-            raise ValueError(f"{what}: pc.{attr} is not the parameter of the optimizer's group {name!r}")
-        _dn._check(what, f"pc.{attr}", p, torch.float32, P)
-        if name in _WIDTHS and tuple(p.shape[1:]) != _WIDTHS[name]:
-            raise ValueError(f"{what}: pc.{attr} has shape {tuple(p.shape)}, expected {(P,) + _WIDTHS[name]}")
-        state = pc.optimizer.state.get(p, None)
-        entries.append((_KIND.get(name, COPY), p.detach(), ("param", group, attr, state)))
-        if state is not None:
-            for key in ("exp_avg", "exp_avg_sq"):
-                if key not in state:
-                    raise ValueError(f"{what}: the optimizer state of group {name!r} has no {key}")
-                _dn._check(what, f"{key} of group {name!r}", state[key], torch.float32, P)
-                if state[key].shape != p.shape:
-                    raise ValueError(f"{what}: {key} of group {name!r} has shape {tuple(state[key].shape)}, its parameter "
-                                     f"{tuple(p.shape)}")
-                entries.append((MOMENT, state[key], ("state", state, key)))
-    _dn._check(what, "pc._degrees", pc._degrees, torch.int32, P)
-    entries.append((COPY, pc._degrees, ("attr", "_degrees")))
-    dev = pc._xyz.device
-    for _, t, _ in entries:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: the model has host tensors; densification needs device tensors (no CPU path)")
-        if t.device != dev:
-            raise ValueError(f"{what}: a tensor is on {t.device}, pc._xyz on {dev}")
-    if len(entries) > MAX_TENSORS:
-        raise RuntimeError(f"{what}: more than {MAX_TENSORS} tensors")
-    return P, dev, entries
+_f32 = ms.f32
 
 
 def _extra(what, name, t, shape, shape_text):
-    _dn._check_extra(what, name, t, torch.float32, shape, shape_text)
-
-
-def _extra_device(what, name, t, dev):
-    if t.device != dev:
-        raise RuntimeError(f"{what}: {name} is on {t.device}, pc._xyz on {dev}; densification needs device tensors "
-                           "(no CPU path)")
-
-
-def _f32(x):
-    return float(np.float32(x))
+    ms.check_extra(what, name, t, torch.float32, shape, shape_text)
 
 
 def _stats(totals, sampled, slots, ratio):
@@ -114,36 +53,23 @@ def _stats(totals, sampled, slots, ratio):
             "totals": totals, "sampled": sampled, "slots": slots, "ratio": ratio}
 
 
-def _table(entries, new, P):
-    table = (_Tensor * len(entries))()
-    for slot, (kind, t, _), out in zip(table, entries, new):
-        words = t.numel() // P
-        slot.src, slot.dst, slot.row_words, slot.kind = (t.data_ptr() if words else None), \
-            (out.data_ptr() if words else None), words, kind
-    return table
-
-
 def inject_noise(pc, scale, noise=None, generator=None):
     """pc._xyz += scale * gate(opacity) * (covariance @ noise row), in place, in one launch; scale = noise_lr * the current
     learning rate of xyz.  A zero noise row leaves its xyz row bit for bit.  Capturable in a graph when `noise` is given."""
     what = "inject_noise"
-    P = _dn._model_size(what, pc)
+    P = ms.model_size(what, pc)
     if noise is not None:
         _extra(what, "noise", noise, (P, 3), f"(P, 3) with P = {P}")
     tensors = (("pc._xyz", pc._xyz, (3,)), ("pc._opacity", pc._opacity, (1,)), ("pc._scaling", pc._scaling, (3,)),
                ("pc._rotation", pc._rotation, (4,)))
     for name, t, width in tensors:
-        _dn._check(what, name, t, torch.float32, P)
+        ms.check(what, name, t, torch.float32, P)
         if tuple(t.shape[1:]) != width:
             raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {(P,) + width}")
     dev = pc._xyz.device
-    for _, t, _ in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: the model has host tensors; densification needs device tensors (no CPU path)")
-        if t.device != dev:
-            raise ValueError(f"{what}: a tensor is on {t.device}, pc._xyz on {dev}")
+    ms.check_devices(what, [t for _, t, _ in tensors], dev)
     if noise is not None:
-        _extra_device(what, "noise", noise, dev)
+        ms.check_extra_device(what, "noise", noise, dev)
     if P == 0:
         return
     with torch.no_grad(), _C._on_device(dev):
@@ -160,12 +86,12 @@ def relocate(pc, min_opacity=0.005, uniforms=None, generator=None, zero_relocate
     object is replaced, state['step'] is untouched.  -> a dict of device tensors (n_dead, n_draws, n_sources, n_clamped, noop,
     totals, sampled, slots, ratio).  Capturable in a graph when `uniforms` is given."""
     what = "relocate"
-    P = _dn._model_size(what, pc)
+    P = ms.model_size(what, pc)
     if uniforms is not None:
         _extra(what, "uniforms", uniforms, (P,), f"(P,) with P = {P}")
-    P, dev, entries = _collect(what, pc)
+    P, dev, entries = ms.collect(what, pc, _KIND, MOMENT)   # the accumulators are not looked at
     if uniforms is not None:
-        _extra_device(what, "uniforms", uniforms, dev)
+        ms.check_extra_device(what, "uniforms", uniforms, dev)
     with torch.no_grad(), _C._on_device(dev):
         stream = _C._stream()
         totals = torch.empty((TOTALS,), dtype=torch.int32, device=dev)
@@ -180,7 +106,7 @@ def relocate(pc, min_opacity=0.005, uniforms=None, generator=None, zero_relocate
                                        slots.data_ptr() if P else None, ratio.data_ptr() if P else None, totals.data_ptr(),
                                        ws.data_ptr() if P else None, stream), what)
         if P > 0:
-            table = _table(entries, [t for _, t, _ in entries], P)
+            table = ms.fill_table(_Tensor, entries, [t for _, t, _ in entries], P)
             _C._check(_lib.r3dgs_mcmc_move(P, RELOCATE, 0, 1 if zero_relocated else 0, _f32(min_opacity), len(entries), table,
                                            pc._opacity.data_ptr(), pc._scaling.data_ptr(), sampled.data_ptr(), slots.data_ptr(),
                                            ratio.data_ptr(), totals.data_ptr(), ws.data_ptr(), stream), what)
@@ -199,13 +125,13 @@ def add_new(pc, cap_max, growth=1.05, uniforms=None, generator=None):
     the model has them; the optimizer state is re-keyed as r3dgs_densify does it.  With nothing to add nothing changes and
     no tensor object is replaced.  -> a dict of device tensors as relocate's (slots is None), plus "n_new" (a Python int)."""
     what = "add_new"
-    P = _dn._model_size(what, pc)
+    P = ms.model_size(what, pc)
     n_new = n_new_rows(P, cap_max, growth)
     if uniforms is not None:
         _extra(what, "uniforms", uniforms, (n_new,), f"(n_new,) with n_new = {n_new}")
-    P, dev, entries = _collect(what, pc)
+    P, dev, entries = ms.collect(what, pc, _KIND, MOMENT)   # the accumulators are not looked at
     if uniforms is not None:
-        _extra_device(what, "uniforms", uniforms, dev)
+        ms.check_extra_device(what, "uniforms", uniforms, dev)
     with torch.no_grad(), _C._on_device(dev):
         stream = _C._stream()
         totals = torch.empty((TOTALS,), dtype=torch.int32, device=dev)
@@ -222,28 +148,13 @@ def add_new(pc, cap_max, growth=1.05, uniforms=None, generator=None):
         _C._check(_lib.r3dgs_mcmc_plan(P, pc._opacity.data_ptr(), 0.0, GROW, n_new, uniforms.data_ptr(), sampled.data_ptr(), None,
                                        ratio.data_ptr(), totals.data_ptr(), ws.data_ptr(), stream), what)
         rows = P + n_new
-        new = [torch.empty((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for _, t, _ in entries]
-        table = _table(entries, new, P)
+        new = ms.new_rows(entries, rows, dev)
+        table = ms.fill_table(_Tensor, entries, new, P)
         _C._check(_lib.r3dgs_mcmc_move(P, GROW, n_new, 0, _f32(GROW_MIN_OPACITY), len(entries), table, pc._opacity.data_ptr(),
                                        pc._scaling.data_ptr(), sampled.data_ptr(), None, ratio.data_ptr(), totals.data_ptr(),
                                        ws.data_ptr(), stream), what)
-        # hand-over, as r3dgs_densify: the same state dict under the new parameter
-        for (_, _, dest), out in zip(entries, new):
-            if dest[0] == "param":
-                _, group, attr, state = dest
-                old = group["params"][0]
-                if state is not None:
-                    del pc.optimizer.state[old]
-                p = nn.Parameter(out.requires_grad_(True))
-                group["params"][0] = p
-                if state is not None:
-                    pc.optimizer.state[p] = state
-                setattr(pc, attr, p)
-            elif dest[0] == "state":
-                dest[1][dest[2]] = out
-            else:
-                setattr(pc, dest[1], out)
-        for name in _ACCUMULATORS:
+        ms.hand_over(pc, entries, new)
+        for name in ms.ACCUMULATORS:
             old = getattr(pc, name, None)
             if isinstance(old, torch.Tensor):
                 setattr(pc, name, torch.zeros((rows,) + tuple(old.shape[1:]), dtype=old.dtype, device=dev))

@@ -136,6 +136,35 @@ def test_densify_and_prune_equals_the_restatement(P, sh_degree):
         assert np.array_equal(a, b), "not bit-identical from run to run"
 
 
+def _four_bytes_off(t):
+    """The same values in a contiguous view whose storage starts 4 bytes past a 16-byte boundary."""
+    view = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)[1:].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+def test_sources_four_bytes_off_a_sixteen_byte_boundary_move_word_by_word():
+    """A parameter and a moment whose bases are not 16-byte aligned: their units are assembled from 4-byte loads
+    (csrc/densify.hip move_kernel, src_vec == 0) and stored as 16 bytes.  Held to the restatement bit for bit."""
+    import r3dgs_densify as dn
+    P, M = 65, 16
+    thr = ref.thresholds(ref.MAX_GRAD, ref.MIN_OPACITY, ref.EXTENT, 20, ref.PERCENT_DENSE)
+    state = _band_free(P, M, seed=P + 3, thr=thr, grads=True)
+    noise = np.random.default_rng(P).standard_normal((2, P, 3)).astype(F32)
+    out = ref.densify_and_prune(state, ref.MAX_GRAD, ref.MIN_OPACITY, ref.EXTENT, 20, ref.PERCENT_DENSE, noise)
+    assert out["nA"] > 0 and out["nB"] > 0 and out["nC"] > 0, "every segment has rows"
+    pc = _model(state)
+    with torch.no_grad():
+        pc._features_rest.data = _four_bytes_off(pc._features_rest.data)          # 45-word rows
+        moments = pc.optimizer.state[pc._xyz]
+        moments["exp_avg"] = _four_bytes_off(moments["exp_avg"])                  # 3-word rows
+    old_states = {g["name"]: pc.optimizer.state[g["params"][0]] for g in pc.optimizer.param_groups}
+    dn.densify_and_prune(pc, ref.MAX_GRAD, ref.MIN_OPACITY, ref.EXTENT, 20, {}, store_grads=True, noise=_dev(noise))
+    _assert_equals_restatement(pc, out, store_grads=True, compacted=False)
+    _assert_handed_over(pc, old_states, 7.0)
+
+
 def test_drawn_noise_is_seeded_by_the_generator_and_reads_only_split_parents():
     import r3dgs_densify as dn
     thr = ref.thresholds(ref.MAX_GRAD, ref.MIN_OPACITY, ref.EXTENT, None, ref.PERCENT_DENSE)

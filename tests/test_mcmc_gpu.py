@@ -147,6 +147,23 @@ def test_relocate_equals_the_reference(P, kind, zero_relocated, moments):
     assert all(torch.equal(stats[k], stats2[k]) for k in ("totals", "ratio")) and torch.equal(stats["sampled"][:n], stats2["sampled"][:n])
 
 
+@pytest.mark.parametrize("P,kind,zero_relocated", [(64, "torch", False), (65, "r3dgs", True), (257, "torch", True)])
+def test_relocate_at_the_wave_and_workgroup_edges_of_the_rank(P, kind, zero_relocated):
+    """One full wave, one lane of a second wave, one lane of a second workgroup (csrc/block_scan.h block_rank): dead and drawn
+    rows on both sides of every edge the model has, so that `slots` and the compacted cdf take ranks from across it."""
+    state = _state(P, seed=P + 7)
+    edges = [i for i in (0, 63, 64, 255, 256) if i < P]
+    state["opacity"][edges] = -8.0                                    # dead
+    state["opacity"][[i + 1 for i in edges if i + 1 < P and i + 1 not in edges]] = 1.5   # alive
+    uniforms = np.random.default_rng(P).random(P).astype(F32)
+    uniforms[0], uniforms[1] = 0.0, BELOW_ONE                         # the first and the last row of positive weight
+    _, stats, worst, n = _relocate_and_check(state, kind, zero_relocated, uniforms)
+    dead = ref.weights(state["opacity"].reshape(-1), MIN_OPACITY, ref.RELOCATE)[1]   # _check_plan held slots to flatnonzero(dead)
+    assert dead[edges].all() and not dead[[i + 1 for i in edges if i + 1 < P and i + 1 not in edges]].any()
+    assert int(stats["n_dead"]) == int(dead.sum()) == n >= len(edges)
+    print(f"\nrelocate P={P} {kind}: {n} draws over the edges {edges}, worst error / bound = {worst:.3f}")
+
+
 def test_sixty_with_fifty_nine_dead_clamps_the_ratio():
     state = _state(60, seed=3)
     state["opacity"][:] = -8.0
