@@ -226,32 +226,8 @@ void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int hei
 {
     const AuxBwdWork w = AuxBwdWork::carve(workspace, (size_t)R, pair_sort_temp_bytes((size_t)R));
     launch_pair_sort("aux maps backward", st, P, R, w.sort, s);
-    AuxGaussArgs g;
-    g.rec = st.geom.rec;
-    g.radii = in.radii;
-    g.tiles = st.geom.tiles;
-    g.keys = w.sort.keys_out;
-    g.slots = w.sort.slots_out;
+    AuxGaussArgs g = gauss_args_of<AuxGaussArgs>(st, w.sort, P, R, width, height, in);
     g.slab = w.slab;
-    g.view = in.viewmatrix;
-    g.proj = in.projmatrix;
-    g.means3D = in.means3D;
-    g.scales = in.scales;
-    g.rotations = in.rotations;
-    g.cov3D_precomp = in.cov3D_precomp;
-    g.tan_fovx = in.tan_fovx;
-    g.tan_fovy = in.tan_fovy;
-    g.scale_modifier = in.scale_modifier;
-    g.W = width;
-    g.H = height;
-    g.P = (uint32_t)P;
-    g.R = (uint32_t)R;
-    g.dL_dmeans2D = in.dL_dmeans2D;
-    g.dL_dmeans3D = in.dL_dmeans3D;
-    g.dL_dopacity = in.dL_dopacity;
-    g.dL_dscales = in.dL_dscales;
-    g.dL_drotations = in.dL_drotations;
-    g.dL_dcov3D = in.dL_dcov3D;
     const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
     if (g_f64_chain.get())
         hipLaunchKernelGGL(aux_bwd_gauss_kernel<true>, dim3(gblocks), dim3(64), 0, s, g);
@@ -287,22 +263,16 @@ int r3dgs_aux_maps_backward(int P, int R, int width, int height, char* geom_buff
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
-        check_replay_dims("aux_maps_backward", P, R, width, height);
-        if (P == 0) return 0;   // every output has P rows
         const AuxBwdGeom geom = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
                                  cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
-        const bool no_upstream = !dL_ddepth && !dL_dalpha && !dL_dmedian;
-        if (R == 0 || no_upstream) {   // nothing to walk: zeros, the blobs are not read
-            aux_bwd_zero_outputs(P, geom, s);
-            return 0;
-        }
-        if (!geom.any_output()) return 0;
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("aux_maps_backward: state buffers must not be NULL");
-        if (!workspace) throw Error("aux_maps_backward: the workspace must not be NULL");
-        aux_bwd_check_geom("aux_maps_backward", geom);
-        const TileGrid grid = replay_grid("aux_maps_backward", width, height);
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
-        const AuxBwdArgs a = {walk_args_of(st, grid, P, R, width, height), dL_ddepth, dL_dalpha, dL_dmedian,
+        const auto w = replay_bwd_open(
+            "aux_maps_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer},
+            dL_ddepth || dL_dalpha || dL_dmedian, geom, nullptr, 0, workspace, s,
+            [&](const char* what) { check_replay_dims(what, P, R, width, height); },
+            [&] { aux_bwd_check_geom("aux_maps_backward", geom); });
+        if (!w) return 0;
+        const PassStates& st = w->st;
+        const AuxBwdArgs a = {walk_args_of(st, w->grid, P, R, width, height), dL_ddepth, dL_dalpha, dL_dmedian,
                               aux_bwd_slab(workspace, (size_t)R)};
         hipLaunchKernelGGL(aux_bwd_pixel_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
         check_launch("aux maps backward, pixel pass", s, false);

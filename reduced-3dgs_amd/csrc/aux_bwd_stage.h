@@ -2,13 +2,17 @@
 //   * the slab rows a pixel pass writes (aux_bwd_pixel_kernel, dist_bwd_pixel_kernel): 32-byte rows of seven wave sums at
 //     slab[(list slot * 4 + quadrant) * 8], zero rows for an entry nobody blended and for the slots behind the walk;
 //   * the ends of a per-Gaussian kernel: the zero gradient and the six guarded stores;
+//   * the opening of a backward entry point (replay_bwd_open) and the fill of a per-Gaussian kernel's arguments;
 //   * the host side of aux_bwd.hip's second stage (defined there): the workspace layout, the zero fill of a call with
 //     nothing to walk, and the three launches behind the pixel pass -- keys, the stable sort (pair_sort.h), the per-Gaussian
 //     sum in double and chain.
 #pragma once
+#include <optional>
+
 #include "aux_math.h"
 #include "common.h"
 #include "pair_sort.h"
+#include "pass_driver.h"
 #include "replay_walk.h"
 
 namespace r3 {
@@ -119,6 +123,62 @@ float* aux_bwd_slab(char* workspace, size_t R);
 void aux_bwd_zero_outputs(int P, const AuxBwdGeom& g, hipStream_t s);
 // the pointer checks of a call that walks (`what`: the entry point's name, for the message)
 void aux_bwd_check_geom(const char* what, const AuxBwdGeom& g);
+// The opening of a backward entry point, by the plan of pass_driver.h replay_bwd_plan: nullopt when the call is complete
+// (nothing to do, or the outputs -- `rows_out`, P rows of `row_floats`, is a unit's output beside g's six -- were zero-filled),
+// else the carved state and the grid of a call that walks.  check_dims(what) and check_inputs() are the unit's own refusals:
+// the first of all, and behind the NULL checks on the blobs and the workspace.
+struct ReplayBwdWalk {
+    PassStates st;
+    TileGrid grid;
+};
+template <class Dims, class Inputs>
+std::optional<ReplayBwdWalk> replay_bwd_open(const char* what, int P, int R, int width, int height, const PassBlobs& blobs,
+                                             bool has_upstream, const AuxBwdGeom& g, float* rows_out, size_t row_floats,
+                                             const char* workspace, hipStream_t s, Dims check_dims, Inputs check_inputs)
+{
+    check_dims(what);
+    const ReplayPlan plan = replay_bwd_plan(P, R, has_upstream, g.any_output() || rows_out);
+    if (plan == ReplayPlan::ZeroOutputs) {
+        if (rows_out) R3_HIP(hipMemsetAsync(rows_out, 0, sizeof(float) * row_floats * (size_t)P, s));
+        aux_bwd_zero_outputs(P, g, s);
+    }
+    if (plan != ReplayPlan::Walk) return std::nullopt;
+    const PassStates st = replay_states(what, P, R, width, height, blobs);
+    if (!workspace) throw Error(std::string(what) + ": the workspace must not be NULL");
+    check_inputs();
+    return ReplayBwdWalk{st, replay_grid(what, width, height)};
+}
+// The arguments of a per-Gaussian kernel (A: AuxGaussArgs, FeatGaussArgs) but for its slab and what else is the unit's own.
+template <class A>
+A gauss_args_of(const PassStates& st, const PairSortWork& sort, int P, int R, int width, int height, const AuxBwdGeom& in)
+{
+    A g = {};
+    g.rec = st.geom.rec;
+    g.radii = in.radii;
+    g.tiles = st.geom.tiles;
+    g.keys = sort.keys_out;
+    g.slots = sort.slots_out;
+    g.view = in.viewmatrix;
+    g.proj = in.projmatrix;
+    g.means3D = in.means3D;
+    g.scales = in.scales;
+    g.rotations = in.rotations;
+    g.cov3D_precomp = in.cov3D_precomp;
+    g.tan_fovx = in.tan_fovx;
+    g.tan_fovy = in.tan_fovy;
+    g.scale_modifier = in.scale_modifier;
+    g.W = width;
+    g.H = height;
+    g.P = (uint32_t)P;
+    g.R = (uint32_t)R;
+    g.dL_dmeans2D = in.dL_dmeans2D;
+    g.dL_dmeans3D = in.dL_dmeans3D;
+    g.dL_dopacity = in.dL_dopacity;
+    g.dL_dscales = in.dL_dscales;
+    g.dL_drotations = in.dL_drotations;
+    g.dL_dcov3D = in.dL_dcov3D;
+    return g;
+}
 // keys, sort, per-Gaussian sum and chain over a slab the pixel pass has been launched on, on the same stream
 void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int height, const AuxBwdGeom& g, char* workspace,
                           hipStream_t s);

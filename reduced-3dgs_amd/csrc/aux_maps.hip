@@ -113,11 +113,10 @@ int r3dgs_aux_maps(int P, int R, int width, int height, char* geom_buffer, char*
             if (n_check) R3_HIP(hipMemsetAsync(n_check, 0, sizeof(uint32_t) * N, s));
             return 0;
         }
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("aux_maps: state buffers must not be NULL");
-        if (!depth && !alpha && !median_depth && !T_check && !n_check) return 0;
         // (the arrays read here lie in front of the geometry blob's temp storage and of its optional tail: their offsets
         // are those of every forward's carve, lean or full)
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
+        const PassStates st = replay_states("aux_maps", P, R, width, height, {geom_buffer, binning_buffer, image_buffer});
+        if (!depth && !alpha && !median_depth && !T_check && !n_check) return 0;
         const AuxArgs a = {walk_args_of(st, grid, P, R, width, height), depth, alpha, median_depth, T_check, n_check};
         hipLaunchKernelGGL(aux_maps_kernel, dim3(a.nblocks), dim3(64), 0, s, a);
         check_launch("aux maps", s, false);

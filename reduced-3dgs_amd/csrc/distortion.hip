@@ -218,9 +218,8 @@ int r3dgs_distortion_map(int P, int R, int width, int height, char* geom_buffer,
             if (saved_moments) R3_HIP(hipMemsetAsync(saved_moments, 0, sizeof(float) * 2 * N, s));
             return 0;
         }
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("distortion_map: state buffers must not be NULL");
+        const PassStates st = replay_states("distortion_map", P, R, width, height, {geom_buffer, binning_buffer, image_buffer});
         if (!distortion && !saved_moments) return 0;
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
         DistArgs a = args_of(st, P, R, width, height, grid, near, far);
         a.distortion = distortion;
         a.moments = saved_moments;
@@ -254,23 +253,18 @@ int r3dgs_distortion_map_backward(int P, int R, int width, int height, char* geo
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
-        check_call("distortion_map_backward", P, R, width, height, near, far);
-        if (P == 0) return 0;   // every output has P rows
         const AuxBwdGeom geom = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
                                  cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
-        if (R == 0 || !dL_ddistortion) {   // nothing to walk: zeros, the blobs are not read
-            aux_bwd_zero_outputs(P, geom, s);
-            return 0;
-        }
-        if (!geom.any_output()) return 0;
-        if (!geom_buffer || !binning_buffer || !image_buffer)
-            throw Error("distortion_map_backward: state buffers must not be NULL");
-        if (!saved_moments) throw Error("distortion_map_backward: saved_moments must not be NULL");
-        if (!workspace) throw Error("distortion_map_backward: the workspace must not be NULL");
-        aux_bwd_check_geom("distortion_map_backward", geom);
-        const TileGrid grid = replay_grid("distortion_map_backward", width, height);
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
-        DistArgs a = args_of(st, P, R, width, height, grid, near, far);
+        const auto w = replay_bwd_open(
+            "distortion_map_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_ddistortion != nullptr,
+            geom, nullptr, 0, workspace, s, [&](const char* what) { check_call(what, P, R, width, height, near, far); },
+            [&] {
+                if (!saved_moments) throw Error("distortion_map_backward: saved_moments must not be NULL");
+                aux_bwd_check_geom("distortion_map_backward", geom);
+            });
+        if (!w) return 0;
+        const PassStates& st = w->st;
+        DistArgs a = args_of(st, P, R, width, height, w->grid, near, far);
         a.g = dL_ddistortion;
         a.saved = saved_moments;
         a.slab = aux_bwd_slab(workspace, (size_t)R);

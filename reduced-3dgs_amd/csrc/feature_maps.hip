@@ -506,9 +506,8 @@ int r3dgs_feature_maps(int P, int R, int width, int height, char* geom_buffer, c
             R3_HIP(hipMemsetAsync(out, 0, sizeof(float) * N * (size_t)C, s));
             return 0;
         }
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("feature_maps: state buffers must not be NULL");
+        const PassStates st = replay_states("feature_maps", P, R, width, height, {geom_buffer, binning_buffer, image_buffer});
         if (!features) throw Error("feature_maps: features must not be NULL");
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
         FeatArgs a = base_args(st, grid, P, R, width, height, features, C);
         a.out = out;
         const dim3 g(a.nblocks, a.ngroups);
@@ -547,30 +546,25 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
-        check_dims("feature_maps_backward", P, R, C, width, height);
-        if (P == 0) return 0;   // every output has P rows
         const AuxBwdGeom in = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
                                cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
         const bool geom = in.any_output();
         const bool feat = dL_dfeatures != nullptr;
-        if (R == 0 || !dL_dout) {   // nothing to walk: zeros, the blobs are not read
-            if (dL_dfeatures) R3_HIP(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)C * (size_t)P, s));
-            aux_bwd_zero_outputs(P, in, s);
-            return 0;
-        }
-        if (!geom && !feat) return 0;
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("feature_maps_backward: state buffers must not be NULL");
-        if (!workspace) throw Error("feature_maps_backward: the workspace must not be NULL");
-        if (!radii) throw Error("feature_maps_backward: radii must not be NULL");
-        if (geom) {
-            if (!features) throw Error("feature_maps_backward: the geometry gradients need features");
-            if (!viewmatrix || !projmatrix || !means3D)
-                throw Error("feature_maps_backward: the geometry gradients need viewmatrix, projmatrix and means3D");
-            if (!cov3D_precomp && (!scales || !rotations))
-                throw Error("feature_maps_backward: need scales and rotations, or cov3D_precomp");
-        }
-        const TileGrid grid = replay_grid("feature_maps_backward", width, height);
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
+        const auto walk = replay_bwd_open(
+            "feature_maps_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_dout != nullptr, in,
+            dL_dfeatures, (size_t)C, workspace, s, [&](const char* what) { check_dims(what, P, R, C, width, height); },
+            [&] {
+                if (!radii) throw Error("feature_maps_backward: radii must not be NULL");
+                if (!geom) return;   // a frozen geometry: none of its inputs is read
+                if (!features) throw Error("feature_maps_backward: the geometry gradients need features");
+                if (!viewmatrix || !projmatrix || !means3D)
+                    throw Error("feature_maps_backward: the geometry gradients need viewmatrix, projmatrix and means3D");
+                if (!cov3D_precomp && (!scales || !rotations))
+                    throw Error("feature_maps_backward: need scales and rotations, or cov3D_precomp");
+            });
+        if (!walk) return 0;
+        const PassStates& st = walk->st;
+        const TileGrid& grid = walk->grid;
         const FeatWork w = FeatWork::carve(workspace, (size_t)R, C, pair_sort_temp_bytes((size_t)R));
 
         FeatArgs a = base_args(st, grid, P, R, width, height, features, C);
@@ -606,33 +600,9 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
             check_launch("feature maps backward, feature sums", s, false);
         }
         if (geom) {
-            FeatGaussArgs g;
-            g.rec = st.geom.rec;
-            g.radii = radii;
-            g.tiles = st.geom.tiles;
-            g.keys = w.sort.keys_out;
-            g.slots = w.sort.slots_out;
+            FeatGaussArgs g = gauss_args_of<FeatGaussArgs>(st, w.sort, P, R, width, height, in);
             g.slab_g = w.slab_g;
-            g.view = viewmatrix;
-            g.proj = projmatrix;
-            g.means3D = means3D;
-            g.scales = scales;
-            g.rotations = rotations;
-            g.cov3D_precomp = cov3D_precomp;
-            g.tan_fovx = tan_fovx;
-            g.tan_fovy = tan_fovy;
-            g.scale_modifier = scale_modifier;
-            g.W = width;
-            g.H = height;
-            g.P = (uint32_t)P;
-            g.R = (uint32_t)R;
             g.ngroups = a.ngroups;
-            g.dL_dmeans2D = dL_dmeans2D;
-            g.dL_dmeans3D = dL_dmeans3D;
-            g.dL_dopacity = dL_dopacity;
-            g.dL_dscales = dL_dscales;
-            g.dL_drotations = dL_drotations;
-            g.dL_dcov3D = dL_dcov3D;
             const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
             if (g_f64_chain.get())
                 hipLaunchKernelGGL(feat_bwd_gauss_kernel<true>, dim3(gblocks), dim3(64), 0, s, g);

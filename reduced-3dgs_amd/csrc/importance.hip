@@ -205,9 +205,8 @@ int r3dgs_contribution_scores(int P, int R, int width, int height, char* geom_bu
         }
         const bool scores = score_sum || score_max || score_count || score_views;
         if (!scores && !T_check && !n_check) return 0;
-        if (!geom_buffer || !binning_buffer || !image_buffer) throw Error("contribution_scores: state buffers must not be NULL");
+        const PassStates st = replay_states("contribution_scores", P, R, width, height, {geom_buffer, binning_buffer, image_buffer});
         if (!workspace) throw Error("contribution_scores: the workspace must not be NULL");
-        const PassStates st = carve_pass(P, (uint32_t)R, width, height, {geom_buffer, binning_buffer, image_buffer}, 0);
         const ImpWork w = ImpWork::carve(workspace, (size_t)R, pair_sort_temp_bytes((size_t)R));
 
         const ImpArgs a = {walk_args_of(st, grid, P, R, width, height), pixel_weight, w.rows, T_check, n_check};

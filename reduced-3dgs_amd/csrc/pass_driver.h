@@ -126,6 +126,23 @@ inline TileGrid replay_grid(const char* what, int width, int height)   // a walk
     return grid;
 }
 
+// the three state blobs of a call that walks, carved (arithmetic only: nothing is read here)
+inline PassStates replay_states(const char* what, int P, int R, int width, int height, const PassBlobs& blobs)
+{
+    if (!blobs.geom || !blobs.binning || !blobs.image) throw Error(std::string(what) + ": state buffers must not be NULL");
+    return carve_pass(P, (uint32_t)R, width, height, blobs, 0);
+}
+// What a replay backward does (DESIGN.md "Replay passes", the host contract), in the order the cases are tried: every output
+// has P rows, so P == 0 leaves nothing to write; without pairs or without an upstream gradient the outputs are zeros and the
+// blobs are not read; a walk nobody reads is not launched.
+enum class ReplayPlan { Nothing, ZeroOutputs, Walk };
+inline ReplayPlan replay_bwd_plan(int P, int R, bool has_upstream, bool any_output)
+{
+    if (P == 0) return ReplayPlan::Nothing;
+    if (R == 0 || !has_upstream) return ReplayPlan::ZeroOutputs;
+    return any_output ? ReplayPlan::Walk : ReplayPlan::Nothing;
+}
+
 void profile_enable(int on);
 void profile_read(double* total_ms, int* launches);
 

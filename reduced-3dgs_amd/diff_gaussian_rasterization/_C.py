@@ -1189,6 +1189,44 @@ class forward_state:
         _tls.forward_recorder = self._outer
 
 
+# ---- the replay calls: what their wrappers share (DESIGN.md "Replay passes", the host contract) ----------------------------
+_NO_CPU_PATH = "the MI355X rasterizer needs device tensors (no CPU path)"
+
+
+def _subset(what, kind, names, allowed):
+    """`names` as a tuple; a name outside `allowed` is refused (kind: what a name is called in the message)."""
+    names = tuple(names)
+    for name in names:
+        if name not in allowed:
+            raise ValueError(f"{what}: unknown {kind} {name!r} (expected a subset of {allowed})")
+    return names
+
+
+def _replay_state(what, who, P, R, H, W, geomBuffer, binningBuffer, imageBuffer, model=None, fallback=None):
+    """The state of a replay call -> (P, H, W, pair capacity, device).  The device is the `model` tensor's, and the three
+    buffers must live there too; model=None: the state buffers' own (the image buffer's, the geometry buffer's behind an empty
+    one).  Host tensors are refused unless P == 0; then nothing says where, and it is `fallback` if that is a device, else the
+    current device, as the forward's empty result.  who: the subject of the one-device refusal.  R: a NumRendered, or a plain
+    pair capacity (_pair_capacity)."""
+    P, H, W = int(P), int(H), int(W)
+    dev = model.device if model is not None else imageBuffer.device if imageBuffer.numel() else geomBuffer.device
+    if P and dev.type != "cuda":
+        raise RuntimeError(_NO_CPU_PATH)
+    if dev.type != "cuda":
+        dev = fallback if fallback is not None and fallback.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device == (imageBuffer.device if model is None else dev)):
+        raise RuntimeError(f"{what}: {who} must live on one device")
+    return P, H, W, int(_pair_capacity(R, P, W, H, binningBuffer)) if P else 0, dev
+
+
+def _workspace(what, nbytes, dev, work):
+    """The workspace of a call whose size query said `nbytes`, from torch's caching allocator (at least one byte: never a NULL
+    pointer).  A query that says 0 although there is `work` has failed: refused with the library's message."""
+    if nbytes == 0 and work:
+        _check(-1, f"{what}_workspace_bytes")
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
 AUX_MAPS = ("depth", "alpha", "median_depth")
 
 
@@ -1198,33 +1236,21 @@ def aux_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, maps=AUX_MAPS, 
     T, "median_depth" = z of the first entry that leaves T < 0.5 (0: none).  R: the forward's num_rendered (a NumRendered) or
     the pair capacity of its binning buffer.  checks=True adds "T_check" (float [H,W]) and "n_check" (int32 [H,W]): the pass's
     own final T and last contributor.  The buffers are only read; the maps carry no gradient."""
-    maps = tuple(maps)
-    for name in maps:
-        if name not in AUX_MAPS:
-            raise ValueError(f"aux_maps: unknown map {name!r} (expected a subset of {AUX_MAPS})")
-    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    P, H, W = int(P), int(H), int(W)
-    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
-        raise RuntimeError("aux_maps: the three state buffers must live on one device")
+    maps = _subset("aux_maps", "map", maps, AUX_MAPS)
+    P, H, W, cap, dev = _replay_state("aux_maps", "the three state buffers", P, R, H, W, geomBuffer, binningBuffer, imageBuffer)
     if _ext is not None:
-        cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
-        got = _ext.aux_maps(P, int(cap), H, W, geomBuffer, binningBuffer, imageBuffer, "depth" in maps, "alpha" in maps,
+        got = _ext.aux_maps(P, cap, H, W, geomBuffer, binningBuffer, imageBuffer, "depth" in maps, "alpha" in maps,
                             "median_depth" in maps, bool(checks))
         out = {name: t for name, t in zip(AUX_MAPS, got[:3]) if name in maps}
         if checks:
             out["T_check"], out["n_check"] = got[3], got[4]
         return out
-    if dev.type != "cuda":   # P == 0 and nothing says where: the current device, as the forward's empty result
-        dev = torch.device("cuda", torch.cuda.current_device())
     out = {name: torch.empty((1, H, W), dtype=torch.float32, device=dev) for name in maps}
     if checks:
         out["T_check"] = torch.empty((H, W), dtype=torch.float32, device=dev)
         out["n_check"] = torch.empty((H, W), dtype=torch.int32, device=dev)
-    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
     with _on_device(dev):
-        _check(_lib.r3dgs_aux_maps(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+        _check(_lib.r3dgs_aux_maps(P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                                    _ptr(out.get("depth")), _ptr(out.get("alpha")), _ptr(out.get("median_depth")),
                                    _ptr(out.get("T_check")), _ptr(out.get("n_check")), _stream()), "aux_maps")
     return out
@@ -1242,40 +1268,39 @@ def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewma
     ACTIVATED values (or cov3D_precomp is given and they are empty).  -> {name: float [P, cols]} for the names in `want` (a
     subset of AUX_GRADS); "opacity" is the gradient of the raw opacity, "means2D" what densification reads.  The buffers are
     only read; the workspace is allocated here, per call, from torch's caching allocator."""
-    want = tuple(want)
-    for name in want:
-        if name not in AUX_GRADS:
-            raise ValueError(f"aux_maps_backward: unknown gradient {name!r} (expected a subset of {AUX_GRADS})")
-    P, H, W = int(P), int(H), int(W)
-    dev = means3D.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    if dev.type != "cuda":
-        dev = torch.device("cuda", torch.cuda.current_device())
+    want = _subset("aux_maps_backward", "gradient", want, AUX_GRADS)
+    P, H, W, cap, dev = _replay_state("aux_maps_backward", "the state buffers and the model", P, R, H, W, geomBuffer,
+                                      binningBuffer, imageBuffer, means3D)
     ups = []
     for name, g in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha), ("dL_dmedian", dL_dmedian)):
         g = _dev(g, dev)
         if g is not None and g.numel() != H * W:
             raise RuntimeError(f"aux_maps_backward: {name} has {g.numel()} elements, the image {H * W}")
         ups.append(g)
-    out = {name: torch.empty((P, _AUX_GRAD_COLS[name]), dtype=torch.float32, device=dev) for name in want}
+    return _map_backward("aux_maps_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
+                         (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
+                         (lambda: _lib.r3dgs_aux_maps_backward_workspace_bytes(P, cap, W, H), _lib.r3dgs_aux_maps_backward),
+                         (), [_ptr(g) for g in ups], AUX_GRADS, _AUX_GRAD_COLS, want)
+
+
+def _map_backward(what, dev, P, cap, H, W, buffers, geometry, native, lead, trail, names, cols, want):
+    """The body of the three map backwards, behind the unit's own checks -> {name: float [P, cols[name]]} for the names in
+    `want`.  geometry: viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp,
+    radii, as the wrappers take them.  native: the unit's (workspace query, call); lead / trail: the call's own arguments
+    in front of viewmatrix and behind radii; names: every output of the call, in its order."""
+    out = {name: torch.empty((P, cols[name]), dtype=torch.float32, device=dev) for name in want}
     if P == 0:
         return out
-    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
-        raise RuntimeError("aux_maps_backward: the state buffers and the model must live on one device")
+    viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii = geometry
     m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
     rad = _dev(radii, dev, torch.int32)
     vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
-    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
+    query, call = native
     with _on_device(dev):
-        nbytes = _lib.r3dgs_aux_maps_backward_workspace_bytes(P, cap, W, H)
-        if nbytes == 0 and cap:
-            _check(-1, "aux_maps_backward_workspace_bytes")
-        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        _check(_lib.r3dgs_aux_maps_backward(
-            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
-            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(ups[0]), _ptr(ups[1]),
-            _ptr(ups[2]), *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "aux_maps_backward")
+        work = _workspace(what, query(), dev, cap)
+        _check(call(P, cap, W, H, *[_ptr(b) for b in buffers], *lead, _ptr(vm), _ptr(pm), float(tanfovx), float(tanfovy), _ptr(m3),
+                    _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), *trail,
+                    *[_ptr(out.get(name)) for name in names], work.data_ptr(), _stream()), what)
     return out
 
 
@@ -1299,19 +1324,12 @@ def distortion_map(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, near=0.0,
     near = far = 0, 2DGS's for 0 < near < far).  want_moments=True -> (map, moments float [2,H,W]): what distortion_map_backward
     reads.  R as in aux_maps.  One launch, no host wait; the buffers are only read; the map carries no gradient."""
     near, far = depth_mapping((near, far))
-    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    P, H, W = int(P), int(H), int(W)
-    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
-        raise RuntimeError("distortion_map: the three state buffers must live on one device")
-    if dev.type != "cuda":   # P == 0 and nothing says where: the current device, as the forward's empty result
-        dev = torch.device("cuda", torch.cuda.current_device())
+    P, H, W, cap, dev = _replay_state("distortion_map", "the three state buffers", P, R, H, W, geomBuffer, binningBuffer,
+                                      imageBuffer)
     out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     moments = torch.empty((2, H, W), dtype=torch.float32, device=dev) if want_moments else None
-    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
     with _on_device(dev):
-        _check(_lib.r3dgs_distortion_map(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), near, far,
+        _check(_lib.r3dgs_distortion_map(P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), near, far,
                                          _ptr(out), _ptr(moments), _stream()), "distortion_map")
     return (out, moments) if want_moments else out
 
@@ -1324,40 +1342,18 @@ def distortion_map_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, 
     the same (near, far).  Everything else as aux_maps_backward: activated scales / rotations or cov3D_precomp -> {name: float
     [P, cols]} for the names in `want` (a subset of AUX_GRADS).  The workspace is allocated here, per call."""
     near, far = depth_mapping((near, far))
-    want = tuple(want)
-    for name in want:
-        if name not in AUX_GRADS:
-            raise ValueError(f"distortion_map_backward: unknown gradient {name!r} (expected a subset of {AUX_GRADS})")
-    P, H, W = int(P), int(H), int(W)
-    dev = means3D.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    if dev.type != "cuda":
-        dev = torch.device("cuda", torch.cuda.current_device())
+    want = _subset("distortion_map_backward", "gradient", want, AUX_GRADS)
+    P, H, W, cap, dev = _replay_state("distortion_map_backward", "the state buffers and the model", P, R, H, W, geomBuffer,
+                                      binningBuffer, imageBuffer, means3D)
     g, mom = _dev(dL_ddistortion, dev), _dev(moments, dev)
     if g is not None and g.numel() != H * W:
         raise RuntimeError(f"distortion_map_backward: dL_ddistortion has {g.numel()} elements, the image {H * W}")
     if g is not None and P and (mom is None or mom.numel() != 2 * H * W):
         raise RuntimeError(f"distortion_map_backward: moments must have {2 * H * W} elements (distortion_map(want_moments=True))")
-    out = {name: torch.empty((P, _AUX_GRAD_COLS[name]), dtype=torch.float32, device=dev) for name in want}
-    if P == 0:
-        return out
-    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
-        raise RuntimeError("distortion_map_backward: the state buffers and the model must live on one device")
-    m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
-    rad = _dev(radii, dev, torch.int32)
-    vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
-    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
-    with _on_device(dev):
-        nbytes = _lib.r3dgs_distortion_map_backward_workspace_bytes(P, cap, W, H)
-        if nbytes == 0 and cap:
-            _check(-1, "distortion_map_backward_workspace_bytes")
-        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        _check(_lib.r3dgs_distortion_map_backward(
-            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), near, far, _ptr(vm), _ptr(pm), float(tanfovx),
-            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(g), _ptr(mom),
-            *[_ptr(out.get(name)) for name in AUX_GRADS], work.data_ptr(), _stream()), "distortion_map_backward")
-    return out
+    return _map_backward("distortion_map_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
+                         (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
+                         (lambda: _lib.r3dgs_distortion_map_backward_workspace_bytes(P, cap, W, H), _lib.r3dgs_distortion_map_backward),
+                         (near, far), (_ptr(g), _ptr(mom)), AUX_GRADS, _AUX_GRAD_COLS, want)
 
 
 FEATURE_MAX_CHANNELS = 512   # R3DGS_FEATURE_MAX_CHANNELS (include/r3dgs_features.h)
@@ -1384,20 +1380,13 @@ def feature_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, features):
     float [C, H, W], out[c] = sum over the blended Gaussians of features[id, c] * alpha * T (not normalised, no background
     term).  R: the forward's num_rendered (a NumRendered) or the pair capacity of its binning buffer.  The buffers are only
     read; the map carries no gradient."""
-    P, H, W = int(P), int(H), int(W)
-    feats, C_ = _feature_tensor(features, P, None, "feature_maps")
-    dev = imageBuffer.device if imageBuffer.numel() else geomBuffer.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    if dev.type != "cuda":
-        dev = features.device if features.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    feats, C_ = _feature_tensor(features, int(P), None, "feature_maps")
+    P, H, W, cap, dev = _replay_state("feature_maps", "the three state buffers", P, R, H, W, geomBuffer, binningBuffer, imageBuffer,
+                                      fallback=features.device)
     _feature_tensor(features, P, dev, "feature_maps")
-    if P and not (geomBuffer.device == binningBuffer.device == imageBuffer.device):
-        raise RuntimeError("feature_maps: the three state buffers must live on one device")
     out = torch.empty((C_, H, W), dtype=torch.float32, device=dev)
-    cap = _pair_capacity(R, P, W, H, binningBuffer) if P else 0
     with _on_device(dev):
-        _check(_lib.r3dgs_feature_maps(P, int(cap), W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(feats),
+        _check(_lib.r3dgs_feature_maps(P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(feats),
                                        C_, out.data_ptr(), _stream()), "feature_maps")
     return out
 
@@ -1409,40 +1398,17 @@ def feature_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, vi
     its units.  With only "features" wanted the geometry is frozen: the geometric sums and the per-Gaussian chain are skipped and
     viewmatrix .. cov3D_precomp may be None.  The buffers are only read; the workspace is allocated here, per call, from
     torch's caching allocator."""
-    want = tuple(want)
-    for name in want:
-        if name not in FEATURE_GRADS:
-            raise ValueError(f"feature_maps_backward: unknown gradient {name!r} (expected a subset of {FEATURE_GRADS})")
-    P, H, W = int(P), int(H), int(W)
-    dev = features.device
-    if P and dev.type != "cuda":
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
-    if dev.type != "cuda":
-        dev = torch.device("cuda", torch.cuda.current_device())
+    want = _subset("feature_maps_backward", "gradient", want, FEATURE_GRADS)
+    P, H, W, cap, dev = _replay_state("feature_maps_backward", "the state buffers and the features", P, R, H, W, geomBuffer,
+                                      binningBuffer, imageBuffer, features)
     feats, C_ = _feature_tensor(features, P, dev, "feature_maps_backward")
     g = _dev(dL_dout, dev)
     if g is not None and g.numel() != C_ * H * W:
         raise RuntimeError(f"feature_maps_backward: dL_dout has {g.numel()} elements, the map {C_ * H * W}")
-    cols = dict(_AUX_GRAD_COLS, features=C_)
-    out = {name: torch.empty((P, cols[name]), dtype=torch.float32, device=dev) for name in want}
-    if P == 0:
-        return out
-    if not (geomBuffer.device == binningBuffer.device == imageBuffer.device == dev):
-        raise RuntimeError("feature_maps_backward: the state buffers and the features must live on one device")
-    m3, sc, rot, cov = _dev(means3D, dev), _dev(scales, dev), _dev(rotations, dev), _dev(cov3D_precomp, dev)
-    rad = _dev(radii, dev, torch.int32)
-    vm, pm = _dev(viewmatrix, dev), _dev(projmatrix, dev)
-    cap = int(_pair_capacity(R, P, W, H, binningBuffer))
-    with _on_device(dev):
-        nbytes = _lib.r3dgs_feature_maps_backward_workspace_bytes(P, cap, C_, W, H)
-        if nbytes == 0 and cap:
-            _check(-1, "feature_maps_backward_workspace_bytes")
-        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        _check(_lib.r3dgs_feature_maps_backward(
-            P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(vm), _ptr(pm), float(tanfovx),
-            float(tanfovy), _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(rad), _ptr(feats), C_, _ptr(g),
-            *[_ptr(out.get(name)) for name in FEATURE_GRADS], work.data_ptr(), _stream()), "feature_maps_backward")
-    return out
+    return _map_backward("feature_maps_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
+                         (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
+                         (lambda: _lib.r3dgs_feature_maps_backward_workspace_bytes(P, cap, C_, W, H), _lib.r3dgs_feature_maps_backward),
+                         (), (_ptr(feats), C_, _ptr(g)), FEATURE_GRADS, dict(_AUX_GRAD_COLS, features=C_), want)
 
 
 SCORES = ("sum", "max", "count", "views")
@@ -1486,7 +1452,7 @@ def contribution_scores(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, pixe
             dev = t.device
             break
     if P and (dev is None or imageBuffer.device.type != "cuda"):
-        raise RuntimeError("the MI355X rasterizer needs device tensors (no CPU path)")
+        raise RuntimeError(_NO_CPU_PATH)
     if out is not None:
         if not isinstance(out, dict) or any(name not in SCORES for name in out):
             raise ValueError(f"contribution_scores: out must be a dict with names among {SCORES}")
@@ -1514,10 +1480,7 @@ def contribution_scores(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, pixe
         res["T_check"] = torch.empty((H, W), dtype=torch.float32, device=dev)
         res["n_check"] = torch.empty((H, W), dtype=torch.int32, device=dev)
     with _on_device(dev):
-        nbytes = _lib.r3dgs_contribution_scores_workspace_bytes(P, cap, W, H)
-        if nbytes == 0 and P and cap:
-            _check(-1, "contribution_scores_workspace_bytes")
-        work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        work = _workspace("contribution_scores", _lib.r3dgs_contribution_scores_workspace_bytes(P, cap, W, H), dev, P and cap)
         _check(_lib.r3dgs_contribution_scores(
             P, cap, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(pixel_weight),
             *[_ptr(out.get(name)) for name in SCORES], int(bool(accumulate)), _ptr(res.get("T_check")), _ptr(res.get("n_check")),
@@ -1557,10 +1520,7 @@ def camera_backward(means3D, degrees, sh, sh_rest, scales, rotations, scale_modi
     model's raw tensors.  geomBuffer: the forward's.  -> {name: tensor} for the names in `want` (a subset of CAMERA_GRADS).
     Two launches, no host wait; the workspace comes from torch's caching allocator per call.  Tensors are read in place: a
     host tensor, a wrong dtype or a non-contiguous tensor is refused."""
-    want = tuple(want)
-    for name in want:
-        if name not in CAMERA_GRADS:
-            raise ValueError(f"camera_backward: unknown gradient {name!r} (expected a subset of {CAMERA_GRADS})")
+    want = _subset("camera_backward", "gradient", want, CAMERA_GRADS)
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("camera_backward: means3D must have dimensions (num_points, 3)")
     dev = means3D.device
@@ -1594,8 +1554,7 @@ def camera_backward(means3D, degrees, sh, sh_rest, scales, rotations, scale_modi
         M = int(shc.size(1))
     out = {name: torch.empty(_CAMERA_GRAD_SHAPES[name], dtype=torch.float32, device=dev) for name in want}
     with _on_device(dev):
-        nbytes = int(_lib.r3dgs_camera_backward_workspace_bytes(P))
-        work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        work = _workspace("camera_backward", _lib.r3dgs_camera_backward_workspace_bytes(P), dev, False)   # (P == 0: no bytes)
         _check(_lib.r3dgs_camera_backward(
             P, _ptr(deg), M, W, H, _ptr(m3), _ptr(shc), _ptr(rest), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), int(raw),
             _ptr(vm), _ptr(pm), _ptr(cp), float(tanfovx), float(tanfovy), _ptr(rad), _ptr(geom), _ptr(g2), _ptr(gcon), _ptr(gcol),

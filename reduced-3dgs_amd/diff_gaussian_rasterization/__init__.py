@@ -341,6 +341,43 @@ def aux_maps_backward(*args, **kwargs):
         return _C.aux_maps_backward(*args, **kwargs)
 
 
+# ---- the three replay maps with gradients (_AuxMaps, _DistortionMap, _FeatureMaps) share what they save and their backward
+# The six model tensors in autograd's input order.  The native calls name the same six as _C.AUX_GRADS, which puts means2D
+# first; the mapping between the two orders is by NAME, below, never by position.
+_MODEL_INPUTS = ("means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
+assert sorted(_MODEL_INPUTS) == sorted(_C.AUX_GRADS)
+
+
+def _replay_call(native, state, rs, *args, **kwargs):
+    """native(P, num_rendered, H, W, the three buffers of the forward's six-tuple `state`, ...)."""
+    num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
+    return native(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer, imgBuffer, *args,
+                  **kwargs)
+
+
+def _replay_save(ctx, state, rs, means3D, scales, rotations, cov3D_precomp, *more):
+    """What _replay_backward reads, then the unit's own tensors `more` (ctx.saved_tensors[8:])."""
+    ctx.raster_settings, ctx.num_rendered = rs, state[0]
+    ctx.save_for_backward(means3D, scales, rotations, cov3D_precomp, *state[2:], *more)
+
+
+def _replay_backward(ctx, native, names, *upstream):
+    """One native backward asked for the gradients autograd wants.  names: the function's leading inputs that can take one,
+    by the native call's names; upstream: that call's arguments behind radii."""
+    rs = ctx.raster_settings
+    means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors[:8]
+    want = tuple(n for n, need in zip(names, ctx.needs_input_grad) if need)
+    got = native(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer, imgBuffer,
+                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D, scales, rs.scale_modifier, rotations,
+                 cov3D_precomp, radii, *upstream, want=want)
+    return tuple(got.get(n) for n in names) + (None,) * (len(ctx.needs_input_grad) - len(names))
+
+
+def _or_empty(*tensors):
+    """The optional scales / rotations / cov3D_precomp as an autograd function takes them: an empty tensor for None."""
+    return tuple(torch.Tensor([]) if t is None else t for t in tensors)
+
+
 class _AuxMaps(torch.autograd.Function):
     """`aux_maps` with gradients.  Inputs: means3D, means2D, opacities (raw), scales (activated), rotations (unit),
     cov3D_precomp (or an empty tensor), then without gradient: the forward's six-tuple `state` (num_rendered, color, radii,
@@ -349,27 +386,16 @@ class _AuxMaps(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, maps):
-        rs = raster_settings
-        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
-        got = _C.aux_maps(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer,
-                          imgBuffer, maps=maps)
-        ctx.raster_settings, ctx.num_rendered, ctx.maps = rs, num_rendered, tuple(maps)
-        ctx.save_for_backward(means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
+        got = _replay_call(_C.aux_maps, state, raster_settings, maps=maps)
+        ctx.maps = tuple(maps)
+        _replay_save(ctx, state, raster_settings, means3D, scales, rotations, cov3D_precomp)
         ctx.set_materialize_grads(False)
         return tuple(got[name] for name in maps)
 
     @staticmethod
     def backward(ctx, *grads):
-        rs = ctx.raster_settings
-        means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors
         up = dict(zip(ctx.maps, grads))
-        names = ("means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
-        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:6]) if need)
-        got = _C.aux_maps_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
-                                   binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D,
-                                   scales, rs.scale_modifier, rotations, cov3D_precomp, radii, up.get("depth"), up.get("alpha"),
-                                   up.get("median_depth"), want=want)
-        return tuple(got.get(n) for n in names) + (None, None, None)
+        return _replay_backward(ctx, _C.aux_maps_backward, _MODEL_INPUTS, up.get("depth"), up.get("alpha"), up.get("median_depth"))
 
 
 def aux_maps_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
@@ -377,11 +403,8 @@ def aux_maps_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_pre
     """The maps of `aux_maps` ATTACHED to the model's tensors -> {name: float [1,H,W]}.  `state`: the six-tuple the forward
     returned (what `_C.forward_state()` records); scales / rotations: the activated values the forward saw (or cov3D_precomp);
     means2D: the screen-space tensor whose .grad densification reads -- it receives the maps' share as well."""
-    empty = torch.Tensor([])
     maps = tuple(maps)
-    got = _AuxMaps.apply(means3D, means2D, opacities, empty if scales is None else scales,
-                         empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
-                         state, raster_settings, maps)
+    got = _AuxMaps.apply(means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state, raster_settings, maps)
     return dict(zip(maps, got))
 
 
@@ -402,37 +425,23 @@ class _DistortionMap(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, mapping):
-        rs = raster_settings
-        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
-        near, far = _C.depth_mapping(mapping)
-        out, moments = _C.distortion_map(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer,
-                                         binningBuffer, imgBuffer, near, far, want_moments=True)
-        ctx.raster_settings, ctx.num_rendered, ctx.mapping = rs, num_rendered, (near, far)
-        ctx.save_for_backward(means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer, moments)
+        ctx.mapping = _C.depth_mapping(mapping)
+        out, moments = _replay_call(_C.distortion_map, state, raster_settings, *ctx.mapping, want_moments=True)
+        _replay_save(ctx, state, raster_settings, means3D, scales, rotations, cov3D_precomp, moments)
         ctx.set_materialize_grads(False)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        rs = ctx.raster_settings
-        means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer, moments = ctx.saved_tensors
-        names = ("means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
-        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:6]) if need)
-        got = _C.distortion_map_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
-                                         binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-                                         means3D, scales, rs.scale_modifier, rotations, cov3D_precomp, radii, grad, moments,
-                                         *ctx.mapping, want=want)
-        return tuple(got.get(n) for n in names) + (None, None, None)
+        return _replay_backward(ctx, _C.distortion_map_backward, _MODEL_INPUTS, grad, ctx.saved_tensors[8], *ctx.mapping)
 
 
 def distortion_map_with_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
                              near=0.0, far=0.0):
     """The map of `distortion_map` ATTACHED to the model's tensors -> float [1,H,W].  Arguments as `aux_maps_with_grad`;
     means2D receives the map's share of the screen-space gradient as well."""
-    empty = torch.Tensor([])
-    return _DistortionMap.apply(means3D, means2D, opacities, empty if scales is None else scales,
-                                empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
-                                state, raster_settings, (near, far))
+    return _DistortionMap.apply(means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state, raster_settings,
+                                (near, far))
 
 
 def feature_maps(P, num_rendered, image_height, image_width, geomBuffer, binningBuffer, imgBuffer, features):
@@ -460,34 +469,21 @@ class _FeatureMaps(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings):
-        rs = raster_settings
-        num_rendered, _, radii, geomBuffer, binningBuffer, imgBuffer = state
-        out = _C.feature_maps(int(radii.numel()), num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer,
-                              imgBuffer, features)
-        ctx.raster_settings, ctx.num_rendered = rs, num_rendered
-        ctx.save_for_backward(features, means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer)
-        return out
+        out = _replay_call(_C.feature_maps, state, raster_settings, features)
+        _replay_save(ctx, state, raster_settings, means3D, scales, rotations, cov3D_precomp, features)
+        return out   # (no set_materialize_grads(False) here, unlike the two above)
 
     @staticmethod
     def backward(ctx, grad_out):
-        rs = ctx.raster_settings
-        features, means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors
-        names = ("features", "means3D", "means2D", "opacity", "scales", "rotations", "cov3D")
-        want = tuple(n for n, need in zip(names, ctx.needs_input_grad[:7]) if need)
-        got = _C.feature_maps_backward(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer,
-                                       binningBuffer, imgBuffer, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D,
-                                       scales, rs.scale_modifier, rotations, cov3D_precomp, radii, features, grad_out, want=want)
-        return tuple(got.get(n) for n in names) + (None, None)
+        return _replay_backward(ctx, _C.feature_maps_backward, ("features",) + _MODEL_INPUTS, ctx.saved_tensors[8], grad_out)
 
 
 def feature_maps_with_grad(features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings):
     """The map of `feature_maps` ATTACHED to `features` and to whichever of the model's tensors require grad -> float
     [C, H, W].  `state`: the six-tuple the forward returned (what `_C.forward_state()` records); scales / rotations: the
     activated values the forward saw (or cov3D_precomp); means2D: the screen-space tensor whose .grad densification reads."""
-    empty = torch.Tensor([])
-    return _FeatureMaps.apply(features, means3D, means2D, opacities, empty if scales is None else scales,
-                              empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp,
-                              state, raster_settings)
+    return _FeatureMaps.apply(features, means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state,
+                              raster_settings)
 
 
 class GaussianRasterizer(nn.Module):

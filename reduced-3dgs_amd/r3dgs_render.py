@@ -296,6 +296,12 @@ def _checked_geom_grad(pc, camera):
         raise ValueError("render: features_geom_grad=True under no_grad: there is no graph to attach the map to")
 
 
+def _anchored(zero, tensors):
+    """An empty model's map: `zero`, attached to those of `tensors` that require grad (a backward through it is valid and
+    leaves zero gradients)."""
+    return zero + 0.0 * sum(t.sum() for t in tensors if t is not None and t.requires_grad)
+
+
 def _feature_map(features, camera, out, state, rs, inputs=None):
     """The "features" entry of the result: [C,H,W] from the six-tuple `state` of the forward that produced `out` (None: an empty
     model -- a zero map), attached to `features` when it requires grad and, with `inputs` (means3D, opacities, scales,
@@ -304,7 +310,7 @@ def _feature_map(features, camera, out, state, rs, inputs=None):
     attach = torch.is_grad_enabled() and (features.requires_grad or inputs is not None)
     if state is None:
         zero = torch.zeros((features.shape[1], H, W), dtype=torch.float32, device=out["render"].device)
-        return zero + 0.0 * features.sum() if attach and features.requires_grad else zero
+        return _anchored(zero, (features,)) if attach and features.requires_grad else zero
     if not attach:
         num_rendered, _, radii, geom, binning, img = state
         return feature_maps(int(radii.numel()), num_rendered, H, W, geom, binning, img, features)
@@ -322,9 +328,7 @@ def _distortion_map(mapping, camera, out, state, rs, inputs):
     near, far = mapping
     if state is None:
         zero = torch.zeros((1, H, W), dtype=torch.float32, device=out["render"].device)
-        if inputs is None:
-            return zero
-        return zero + 0.0 * sum(t.sum() for t in inputs if t is not None and t.requires_grad)
+        return zero if inputs is None else _anchored(zero, inputs)
     if inputs is None:
         num_rendered, _, radii, geom, binning, img = state
         return distortion_map(int(radii.numel()), num_rendered, H, W, geom, binning, img, near, far)
@@ -525,10 +529,9 @@ def render(*args, aux=None, **kwargs):
     out = blended(out)
     if not aux_grad:
         return _with_aux(aux, camera, out, st.result)
-    if st.result is None:   # an empty model: nothing was rendered -- zero maps, attached all the same (a backward through
-        out = _with_aux(aux, camera, out, None)   # them is valid and leaves zero gradients)
-        anchor = 0.0 * sum(t.sum() for t in got["inputs"] if t is not None and t.requires_grad)
-        out.update({name: out[name] + anchor for name in aux})
+    if st.result is None:   # an empty model: nothing was rendered -- zero maps, attached all the same
+        out = _with_aux(aux, camera, out, None)
+        out.update({name: _anchored(out[name], got["inputs"]) for name in aux})
         return out
     out.update(aux_maps_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, st.result, rs, maps=aux))
     return out

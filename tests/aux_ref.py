@@ -82,6 +82,12 @@ SCENE_B = dict(P=700, W=40, H=24, f=30.0, cam_seed=5, gseed=23, degree_mode="mix
 
 
 SCENE_17 = dict(P=300, W=17, H=17, f=15.0, cam_seed=2, gseed=8, degree_mode="mixed", scale_mu=0.08)   # one pixel past a tile
+# Small models on a 17x19 image (partial tiles on both axes).  SCENE_65: one Gaussian past a 64-lane wave; 274 pixels blended, 10.5 %
+# of them with a median depth.  SCENE_1: one Gaussian over 13 pixels, alpha up to 0.87 (one pixel below T = 0.5).  Measured with the
+# CPU oracle: no threshold-ambiguous pixel in either.
+SCENE_65 = dict(SCENE_17, P=65, W=19, H=17)
+SCENE_1 = dict(SCENE_17, P=1, W=19, H=17, gseed=11)
+SMALL = dict(P65_17x19=SCENE_65, P1_17x19=SCENE_1)
 PORTRAIT = dict(camera="portrait_far", P=1500, seed=3)   # tests/camera_cases.py: fx != fy, portrait, far-rotated
 
 

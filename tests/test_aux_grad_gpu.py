@@ -166,6 +166,16 @@ def test_17x17_image(C_):
     held(call(C_, g, cam, c.H, c.W, c.fout, ups), c.ref(ups), "17x17")
 
 
+@pytest.mark.parametrize("name", sorted(ar.SMALL))
+def test_small_models_on_a_17x19_image(C_, name):
+    """P = 65 (one Gaussian past a wave: two blocks of the per-Gaussian kernel) and P = 1 on 17x19, partial tiles on both axes."""
+    kw = ar.SMALL[name]
+    cam, g, _ = ar.make_scene(kw)
+    c = Case(C_, cam, g, kw["H"], kw["W"])
+    ups = upstream(c.H, c.W, 17, c.ok)
+    held(call(C_, g, cam, c.H, c.W, c.fout, ups), c.ref(ups), name)
+
+
 def test_portrait_camera_with_non_square_pixels(C_):
     cam, g = cc.cloud(ar.PORTRAIT["camera"], "gpu", 600, ar.PORTRAIT["seed"])
     c = Case(C_, cam, g, cam.image_height, cam.image_width)
@@ -233,6 +243,7 @@ def test_each_output_alone_and_no_upstream(C_, scene_a):
     for k in C_.AUX_GRADS:
         one = call(C_, c.g, c.cam, c.H, c.W, c.fout, ups, want=(k,))
         assert set(one) == {k} and torch.equal(one[k], full[k]), k
+    assert call(C_, c.g, c.cam, c.H, c.W, c.fout, ups, want=()) == {}   # no output asked for: nothing comes back
     none = call(C_, c.g, c.cam, c.H, c.W, c.fout, [None, None, None])
     assert all(not t.any() for t in none.values())
 

@@ -68,7 +68,7 @@ def consistent(C_, P, H, W, fout, got):
     return ex
 
 
-def parity(C_, cam, g, H, W, tag):
+def parity(C_, cam, g, H, W, tag, min_median=0.2):
     """The exact-size forward, the maps, and every bar of the module's docstring -> (forward's result, maps, flagged shares)."""
     P = len(g["means3D"])
     fout = C_._forward_common(None, *forward_args(g, cam, H, W), exact=True)
@@ -97,7 +97,7 @@ def parity(C_, cam, g, H, W, tag):
     assert err <= 1e-5 * max(1.0, zmax)
     median = got["median_depth"][0].cpu().numpy()
     np.testing.assert_array_equal(median.view(np.uint32)[ok], want["median_depth"].view(np.uint32)[ok])
-    assert (want["median_depth"] > 0).mean() > 0.2, "the case must bring pixels below T = 0.5"
+    assert (want["median_depth"] > 0).mean() > min_median, "the case must bring pixels below T = 0.5"
     empty = (st["n_contrib"].reshape(H, W) == 0) & ~amb
     for k in MAPS:
         assert not got[k][0].cpu().numpy()[empty].any(), k
@@ -251,6 +251,16 @@ def test_17x17_image():
     kw = ar.SCENE_17
     cam, g, _ = ar.make_scene(kw)
     parity(_C, cam, g, kw["H"], kw["W"], "17x17")
+
+
+@pytest.mark.parametrize("name", sorted(ar.SMALL))
+def test_small_models_on_a_17x19_image(name):
+    """P = 65 (one Gaussian past a wave) and P = 1 on 17x19, partial tiles on both axes: every bar of `parity`, except that only
+    some pixel, not a fifth of them, has to have a median depth (tests/aux_ref.py: 10.5 % and one pixel)."""
+    from diff_gaussian_rasterization import _C
+    kw = ar.SMALL[name]
+    cam, g, _ = ar.make_scene(kw)
+    parity(_C, cam, g, kw["H"], kw["W"], name, min_median=0.0)
 
 
 def test_portrait_camera_with_non_square_pixels():

@@ -200,6 +200,22 @@ def test_backward_parity(C_, scene_a, scene_b, portrait, name, C):
         C_.set_f64_chain(was)
 
 
+@pytest.mark.parametrize("name,channels", [("P65_17x19", (1, 4, 5, 8, 9, GROUP, GROUP + 1)), ("P1_17x19", (5,))])
+def test_small_models_on_a_17x19_image(C_, name, channels):
+    """P = 65 (one Gaussian past a wave) and P = 1 on 17x19, partial tiles on both axes: map and every gradient against the
+    reference.  On the P = 65 scene the backward runs at every channel count around its group widths (4, 8, 16): one short of a
+    full group, full, and one past it."""
+    kw = ar.SMALL[name]
+    cam, g, _ = ar.make_scene(kw)
+    c = Case(C_, cam, g, kw["H"], kw["W"])
+    for C in channels:
+        F, up, ref = reference(c, C)
+        value_held(fwd(C_, c, F).cpu().numpy(), fr.feature_map(c.st, F), c.ok.astype(bool), 1.0, f"{name}, C = {C}")
+        got = bwd(C_, c, F, up)
+        assert got["features"].shape == (c.P, C)
+        held(got, ref, ("features",) + GEOM, f"{name}, C = {C}")
+
+
 def test_backward_with_a_precomputed_covariance(C_, scene_b):
     c = scene_b
     g, cam, C = c.g, c.cam, 3
@@ -266,6 +282,7 @@ def test_null_outputs_equal_the_full_call(C_, scene_a):
         assert torch.equal(only_g[k], full[k]), k
     one = bwd(C_, c, F, g, want=("opacity",))
     assert torch.equal(one["opacity"], full["opacity"])
+    assert bwd(C_, c, F, g, want=()) == {}   # no output asked for: nothing comes back
     none = bwd(C_, c, F, None, want=C_.FEATURE_GRADS)
     assert all(not t.any() for t in none.values())
     # frozen geometry needs none of the camera and geometry inputs

@@ -1,12 +1,14 @@
 """CPU checks of the replay passes' index arithmetic (reduced-3dgs_amd/csrc/replay_walk.h): the header's own xcd_remap,
-quad_lane and walk_span, called through tests/hostcheck_walk, against plain Python.  No GPU needed."""
+quad_lane and walk_span, called through tests/hostcheck_walk, against plain Python, and of the host plan of a replay backward
+(pass_driver.h replay_bwd_plan).  No GPU needed."""
 import ctypes as C
 import itertools
 import os
+import subprocess
 
 import pytest
 
-from tests.hostcheck_build import EXACT, build_shim
+from tests.hostcheck_build import EXACT, HIPCC, build_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck_walk", "hostcheck_walk.hip")
@@ -23,6 +25,8 @@ def lib():
     lib.hw_quad_lane.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
     lib.hw_walk_span.restype = None
     lib.hw_walk_span.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]
+    lib.hw_replay_bwd_plan.restype = C.c_int
+    lib.hw_replay_bwd_plan.argtypes = [C.c_int] * 4
     return lib
 
 
@@ -97,3 +101,47 @@ def test_walk_span(lib):
         assert (first, first + length) == forward_form(rx, ry, qd, R), case
         cut += ry > R and ry > rx
     assert cut > 50   # the cases do reach lists that run past the blob
+
+
+NOTHING, ZERO_OUTPUTS, WALK = 0, 1, 2
+
+
+def plan_cases():
+    """(P, R, upstream, outputs) -> the plan: DESIGN.md's contract written out row by row, no expression shared with the code."""
+    N, Z, W = NOTHING, ZERO_OUTPUTS, WALK
+    return {
+        (0, 0, 0, 0): N, (0, 0, 0, 1): N, (0, 0, 1, 0): N, (0, 0, 1, 1): N,   # P == 0: every output has P rows
+        (0, 1, 0, 0): N, (0, 1, 0, 1): N, (0, 1, 1, 0): N, (0, 1, 1, 1): N,
+        (1, 0, 0, 0): Z, (1, 0, 0, 1): Z, (1, 0, 1, 0): Z, (1, 0, 1, 1): Z,   # R == 0: nothing to walk, asked for or not
+        (1, 1, 0, 0): Z, (1, 1, 0, 1): Z,                                     # no upstream: the same
+        (1, 1, 1, 0): N,                                                      # pairs and an upstream, but nothing asked for
+        (1, 1, 1, 1): W,
+    }
+
+
+def test_replay_bwd_plan_truth_table(lib):
+    table = plan_cases()
+    assert len(table) == 16 and sorted(set(table.values())) == [NOTHING, ZERO_OUTPUTS, WALK]
+    assert table[1, 1, 1, 1] == WALK and sum(v == WALK for v in table.values()) == 1
+    assert table[1, 0, 1, 0] == ZERO_OUTPUTS and table[1, 1, 0, 0] == ZERO_OUTPUTS   # "nothing to walk" before "nothing asked"
+    for case, want in table.items():
+        assert lib.hw_replay_bwd_plan(*case) == want, case
+
+
+SAN = ("-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined")
+
+
+@pytest.mark.parametrize("name,extra", [("hostcheck_walk", ()), ("hostcheck_walk_san", SAN)])
+def test_replay_bwd_plan_program(name, extra):
+    """The same table checked by the stand-alone program, plainly and under the host sanitizers."""
+    exe = os.path.join(HERE, "hostcheck_walk", name)
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", *EXACT, *extra, "-o", exe, SRC])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+    rows = out.stdout.split()
+    table = plan_cases()
+    assert len(rows) == 16 * 5
+    for k in range(16):
+        P, R, up, outs, plan = (int(f.split("=")[1]) for f in rows[5 * k:5 * k + 5])
+        assert table[P, R, up, outs] == plan
