@@ -131,6 +131,13 @@ def counter_passes(_C, qm, c):
     return outs
 
 
+def transmittance_rounding(c, sums):
+    """How far two runs' out_transmittance sums may lie apart (test_counter_mode derives it): n positive addends summed in
+    two orders differ by at most 2 (n-1) 2^-24 of the sum, n <= the image's 8x8 regions."""
+    regions = ((c.W + 7) // 8) * ((c.H + 7) // 8)
+    return 2 * (regions - 1) * 2.0 ** -24 * sums
+
+
 @pytest.mark.parametrize("image", list(IMAGES))
 def test_counter_mode(image):
     """A model whose Gaussians spread over many tiles.  The forward blend adds one float per (8x8-pixel region, Gaussian) to
@@ -147,8 +154,7 @@ def test_counter_mode(image):
     assert torch.equal(got[1], want[1]) and torch.equal(got[2], want[2])
     assert t_w.sum() > 0 and torch.equal(t_g, t_w), "out_touched_pixels"
     assert (m_w > 0).any() and torch.equal(m_g > 0, m_w > 0)
-    regions = ((c.W + 7) // 8) * ((c.H + 7) // 8)
-    assert ((m_g - m_w).abs() <= 2 * (regions - 1) * 2.0 ** -24 * m_w).all(), "out_transmittance"
+    assert ((m_g - m_w).abs() <= transmittance_rounding(c, m_w)).all(), "out_transmittance"
 
 
 def two_region_model(image):
