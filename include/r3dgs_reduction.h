@@ -48,7 +48,11 @@ int r3dgs_min_redundancy(int P, int knn, const int* redundancy, const int* neigh
  * cluster).  The convergence test stays on the device: all updates are enqueued and become no-ops once converged.
  * workspace: r3dgs_kmeans_workspace_bytes(n_values, n_centers) bytes of device scratch (0 is returned, with
  * r3dgs_last_error set, when no GPU is present to size the sort).  ids[n_values], centers_out[n_centers] are
- * written; iterations_run (device int, may be NULL) receives the number of updates.  Values must not be NaN. */
+ * written; iterations_run (device int, may be NULL) receives the number of updates.  The workspace is scratch: its
+ * contents on entry do not matter.
+ * Infinite values are allowed: by the assignment rule they belong to centre 0 (no distance to them is below the
+ * initial inf), whose new value is the IEEE sum of its members over their number -- -inf, +inf, or 0 (NaN -> 0) when
+ * it holds both; every other centre is the mean of its own members, as in the reference.  Values must not be NaN. */
 size_t r3dgs_kmeans_workspace_bytes(int n_values, int n_centers);
 int r3dgs_kmeans(int n_values, int n_centers, const float* values, const float* centers_in, float tol,
                  int max_iterations, int* ids, float* centers_out, int* iterations_run, char* workspace,

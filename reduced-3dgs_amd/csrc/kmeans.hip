@@ -20,7 +20,19 @@
 // rounding) is contiguous with them; scanning outwards while the distance is equal and taking the smallest original
 // index reproduces the reference's first-index rule bit for bit, including duplicate and near-duplicate centres.
 // Sums: fp64 prefix differences rounded once to fp32 (the reference adds fp32 partials in atomic order, so its
-// centres are only defined to ~1e-6 relative; the oracle sums in fp64 too).  NaN VALUES are not supported (the
+// centres are only defined to ~1e-6 relative; the oracle sums in fp64 too).  The +-prefix entries of a cluster meet
+// in a 320-bit fixed-point accumulator (quantum 2^-149: every fp32 value and so every prefix entry is a multiple of
+// it; 2^-149 .. 2^160 fits), added word by word with integer atomics and explicit carries.  Integer addition is
+// exact and associative, so the sum does not depend on the order in which the atomics land: results are bit-identical
+// run to run even where a cluster has several runs (first-index ties between near-equal centres, or cluster 0
+// collecting every value whose squared distance overflows), and +P - P at the prefix's magnitude cancels exactly
+// instead of leaving an ulp of P behind.  An fp64 atomicAdd here made such clusters' centres depend on the order.
+// INFINITE VALUES are supported and stay out of the prefix (they enter it as 0, so every entry is finite and no
+// other cluster's difference sees them).  Under the reference's rule an infinite value is at distance inf or NaN
+// from every centre, never beats the initial inf and so belongs to cluster 0; sorted, the -inf values are a head
+// run and the +inf values a tail run.  The pass adds each run's length to cluster 0's size and notes its sign in a
+// flag word; the centre kernel adds -inf / +inf to cluster 0's sum, which is the IEEE sum of the members in any
+// order: -inf, +inf, or NaN -> 0 when both are present; every other centre is the mean of its own (finite) members.  NaN VALUES are not supported (the
 // reference turns centre 0 into 0 when one is present); NaN / inf centres behave as in the reference.
 #include <cstring>
 
@@ -35,18 +47,19 @@ constexpr int kMaxCenters = 1024;
 constexpr int kBlock = 256;
 constexpr int kItems = 8;           // consecutive sorted values per thread in the segment pass
 constexpr int kPad = 0x7fffffff;
+constexpr int kAccWords = 5;        // 320-bit two's complement accumulator per cluster, quantum 2^-149
 
-struct ToDouble {
-    __host__ __device__ double operator()(float v) const { return (double)v; }
+struct ToDouble {     // infinite values enter the prefix as 0: the segment pass adds them to cluster 0 itself
+    __host__ __device__ double operator()(float v) const { return fabsf(v) < INFINITY ? (double)v : 0.0; }
 };
 
 struct KmeansWork {
     float* centers;      // [1024] current centres, original order
     float* s_val;        // [1024] sorted, deduplicated centre values
     int* s_idx;          // [1024] smallest original index of each
-    double* sums;        // [1024]
+    unsigned long long* sums;   // [1024][kAccWords] fixed-point cluster sums
     int* counts;         // [1024] (wrapping adds of +-position)
-    int* flags;          // m, done, iters
+    int* flags;          // m, done, iters, infinite runs seen by this update (bit 0: -inf, bit 1: +inf)
     float* sorted;       // [n]
     double* prefix;      // [n + 1] exclusive prefix of sorted
     char* temp;
@@ -62,7 +75,7 @@ struct KmeansWork {
         w.centers = reinterpret_cast<float*>(take(4 * kMaxCenters));
         w.s_val = reinterpret_cast<float*>(take(4 * kMaxCenters));
         w.s_idx = reinterpret_cast<int*>(take(4 * kMaxCenters));
-        w.sums = reinterpret_cast<double*>(take(8 * kMaxCenters));
+        w.sums = reinterpret_cast<unsigned long long*>(take(8 * kAccWords * kMaxCenters));
         w.counts = reinterpret_cast<int*>(take(4 * kMaxCenters));
         w.flags = reinterpret_cast<int*>(take(256));
         w.sorted = reinterpret_cast<float*>(take(4 * n));
@@ -140,6 +153,71 @@ __device__ inline int assign_sorted(float v, const float* __restrict__ sv, const
     return id;
 }
 
+// ---- the order-independent cluster sums ------------------------------------------------------------------------
+// acc += x for a finite double x that is a multiple of 2^-149 below 2^160 in magnitude (a prefix entry or its
+// negative).  Word i receives its share with one atomicAdd; a wrap of word i is carried into word i + 1.  Whatever the
+// interleaving with other adds, the five words end up holding the exact sum modulo 2^320.
+__device__ inline void acc_add(unsigned long long* __restrict__ acc, double x)
+{
+    if (x == 0.0) return;
+    const long long bits = __double_as_longlong(x);
+    int be = (int)((bits >> 52) & 0x7ff);
+    unsigned long long m = (unsigned long long)bits & 0xfffffffffffffULL;
+    if (be) m |= 1ULL << 52;
+    else be = 1;
+    int sh = be - 1075 + 149;           // x = +-m * 2^(be - 1075) = +-(m << sh) quanta
+    if (sh < 0) {                       // the bits shifted out are zero: x is a multiple of the quantum
+        m = sh > -64 ? m >> -sh : 0;
+        sh = 0;
+    }
+    const int w = sh >> 6, b = sh & 63;
+    if (w >= kAccWords) return;         // not reachable below 2^160
+    unsigned long long term[kAccWords];
+#pragma unroll
+    for (int i = 0; i < kAccWords; i++)
+        term[i] = i == w ? m << b : (i == w + 1 && b ? m >> (64 - b) : 0ULL);
+    if (bits < 0) {                     // two's complement
+        unsigned long long c = 1;
+#pragma unroll
+        for (int i = 0; i < kAccWords; i++) {
+            term[i] = ~term[i] + c;
+            c = (c && term[i] == 0) ? 1 : 0;
+        }
+    }
+    unsigned long long carry = 0;
+#pragma unroll
+    for (int i = 0; i < kAccWords; i++) {
+        const unsigned long long add = term[i] + carry;
+        if (add < carry) continue;      // term all ones + carry: nothing for this word, the carry moves on
+        carry = 0;
+        if (add) {
+            const unsigned long long old = atomicAdd(&acc[i], add);
+            carry = old + add < old ? 1 : 0;
+        }
+    }
+}
+
+// The accumulator as a double: at most three roundings of 2^-53 relative, in a fixed order.
+__device__ inline double acc_value(const unsigned long long* __restrict__ acc)
+{
+    unsigned long long wd[kAccWords];
+#pragma unroll
+    for (int i = 0; i < kAccWords; i++) wd[i] = acc[i];
+    const bool neg = (long long)wd[kAccWords - 1] < 0;
+    if (neg) {
+        unsigned long long c = 1;
+#pragma unroll
+        for (int i = 0; i < kAccWords; i++) {
+            wd[i] = ~wd[i] + c;
+            c = (c && wd[i] == 0) ? 1 : 0;
+        }
+    }
+    double r = 0.0;
+#pragma unroll
+    for (int i = kAccWords - 1; i >= 0; i--) r += ldexp((double)wd[i], 64 * i - 149);
+    return neg ? -r : r;
+}
+
 // ---- one block: (optionally) finish an update, then sort + deduplicate the centres for the next pass -----------
 __device__ inline bool key_less(float av, int ai, float bv, int bi)
 {
@@ -151,7 +229,7 @@ __device__ inline bool key_less(float av, int ai, float bv, int bi)
 
 template <bool UPDATE>
 __global__ __launch_bounds__(kMaxCenters) void kmeans_centres_kernel(int n_centers, float* __restrict__ centers,
-                                                                     double* __restrict__ sums,
+                                                                     unsigned long long* __restrict__ sums,
                                                                      int* __restrict__ counts, float tol,
                                                                      float* __restrict__ s_val_out,
                                                                      int* __restrict__ s_idx_out,
@@ -174,7 +252,12 @@ __global__ __launch_bounds__(kMaxCenters) void kmeans_centres_kernel(int n_cente
         // reduced_3dgs.cu:318-324: centre = sum / size, NaN (empty cluster) -> 0, shift = sum |old - new|
         float shift = 0.f;
         if (t < n_centers) {
-            float nc = (float)sums[t] / (float)counts[t];
+            double sum = acc_value(sums + kAccWords * t);
+            if (t == 0) {               // the infinite runs belong to cluster 0 (file header): the IEEE sum
+                if (flags[3] & 1) sum += -(double)INFINITY;
+                if (flags[3] & 2) sum += (double)INFINITY;
+            }
+            float nc = (float)sum / (float)counts[t];
             if (nc != nc) nc = 0.f;
             shift = fabsf(mine - nc);
             mine = nc;
@@ -191,9 +274,11 @@ __global__ __launch_bounds__(kMaxCenters) void kmeans_centres_kernel(int n_cente
         }
     }
     if (t < n_centers) {
-        sums[t] = 0.0;
+#pragma unroll
+        for (int i = 0; i < kAccWords; i++) sums[kAccWords * t + i] = 0;
         counts[t] = 0;
     }
+    if (t == 0) flags[3] = 0;
 
     // bitonic sort of (value, index) over blockDim.x = next power of two >= n_centers entries,
     // NaNs after the numbers, padding last
@@ -234,12 +319,25 @@ __global__ __launch_bounds__(kMaxCenters) void kmeans_centres_kernel(int n_cente
 }
 
 // ---- the per-update pass over the sorted values: only id changes touch the accumulators ------------------------
+// The -inf head and the +inf tail of the sorted values are runs of their own with these pseudo ids; both belong to
+// cluster 0 (file header).
+constexpr int kNegInfRun = -2;
+constexpr int kPosInfRun = -3;
+
+__device__ inline int run_id(float v, const float* __restrict__ sv, const int* __restrict__ si, int m)
+{
+    if (v == -INFINITY) return kNegInfRun;
+    if (v == INFINITY) return kPosInfRun;
+    return assign_sorted(v, sv, si, m);
+}
+
 __global__ __launch_bounds__(kBlock) void kmeans_segments_kernel(int n, const float* __restrict__ sorted,
                                                                  const double* __restrict__ prefix,
                                                                  const float* __restrict__ s_val,
                                                                  const int* __restrict__ s_idx,
-                                                                 const int* __restrict__ flags,
-                                                                 double* __restrict__ sums, int* __restrict__ counts)
+                                                                 int* __restrict__ flags,
+                                                                 unsigned long long* __restrict__ sums,
+                                                                 int* __restrict__ counts)
 {
     if (flags[1]) return;               // converged
     __shared__ float sv[kMaxCenters];
@@ -261,24 +359,37 @@ __global__ __launch_bounds__(kBlock) void kmeans_segments_kernel(int n, const fl
     } else {
         for (int k = 0; k < kItems; k++) v[k] = start + k < n ? sorted[start + k] : 0.f;
     }
-    int prev = start > 0 ? assign_sorted(sorted[start - 1], sv, si, m) : -1;
+    int prev = start > 0 ? run_id(sorted[start - 1], sv, si, m) : -1;
     for (int k = 0; k < kItems; k++) {
         const long long p = start + k;
         if (p >= n) break;
-        const int id = assign_sorted(v[k], sv, si, m);
+        const int id = run_id(v[k], sv, si, m);
         if (id != prev) {               // a run of `prev` ends before p, a run of `id` starts at p
             const double pre = prefix[p];
             if (prev >= 0) {
-                atomicAdd(&sums[prev], pre);
+                acc_add(sums + kAccWords * prev, pre);
                 atomicAdd(&counts[prev], (int)p);
+            } else if (prev == kNegInfRun) {            // the head run is [0, p)
+                atomicOr(&flags[3], 1);
+                atomicAdd(&counts[0], (int)p);
             }
-            atomicAdd(&sums[id], -pre);
-            atomicAdd(&counts[id], -(int)p);
+            if (id >= 0) {
+                acc_add(sums + kAccWords * id, -pre);
+                atomicAdd(&counts[id], -(int)p);
+            } else if (id == kPosInfRun) {              // the tail run is [p, n): nothing closes it
+                atomicOr(&flags[3], 2);
+                atomicAdd(&counts[0], n - (int)p);
+            }
             prev = id;
         }
         if (p == n - 1) {
-            atomicAdd(&sums[id], prefix[n]);
-            atomicAdd(&counts[id], n);
+            if (id >= 0) {
+                acc_add(sums + kAccWords * id, prefix[n]);
+                atomicAdd(&counts[id], n);
+            } else if (id == kNegInfRun) {              // every value is -inf
+                atomicOr(&flags[3], 1);
+                atomicAdd(&counts[0], n);
+            }
         }
     }
 }
