@@ -276,6 +276,39 @@ int r3dgs_backward_params(int P, const int* D, int M, int R, const float* backgr
 int r3dgs_activate_params(int P, const float* scaling_raw, const float* rotation_raw, float* scales_out,
                           float* rotations_out, void* stream);
 
+/* ---- absolute screen-space gradients (extension; AbsGS, gsplat's absgrad) ----------------------------------------------
+ * r3dgs_backward / r3dgs_backward_params that ALSO return, per Gaussian, the sum over its pixels of the ABSOLUTE value of
+ * what each pixel adds to dL_dmean2D (the per-pixel loop of the reference's backward renderCUDA), in the units and with the
+ * viewport factors of dL_dmean2D:
+ *   dL_dmean2D_abs [P,3]: column 0 = (W/2) sum |dL/dmean2D.x of the pixel|, column 1 = (H/2) sum |.. .y ..|, column 2 = 0;
+ *   rows of culled Gaussians and of Gaussians that reach no pixel are zero.  Every element is written.
+ * The signs are per pixel, so the sums come out of the backward blend itself (two more sums per list entry); every other
+ * output is what the call named without _absgrad writes, bit for bit.  abs_workspace: r3dgs_absgrad_workspace_floats(R)
+ * floats of device memory of the caller's (R as passed here), contents irrelevant before and after; may be NULL only when
+ * binning_buffer is.  Refused (r3dgs_last_error): dL_dmean2D_abs == NULL, a workspace that is NULL or too small.
+ * No float atomics: results are bit-identical run to run.  Describes the colour loss's backward only (the passes of
+ * r3dgs_aux.h, r3dgs_features.h and r3dgs_distortion.h add nothing to it). */
+size_t r3dgs_absgrad_workspace_floats(int R);
+int r3dgs_backward_absgrad(int P, const int* D, int M, int R, const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                           float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                           const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                           float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                           const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                           float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                           float lambda_sh_sparsity, int debug, void* stream, float* dL_dmean2D_abs, float* abs_workspace,
+                           size_t abs_workspace_floats);
+int r3dgs_backward_params_absgrad(int P, const int* D, int M, int R, const float* background, int width, int height,
+                                  const float* means3D, const float* features_dc, const float* features_rest,
+                                  const float* scaling_raw, float scale_modifier, const float* rotation_raw,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer,
+                                  char* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                                  float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                  float* dL_dfeatures_dc, float* dL_dfeatures_rest, float* dL_dscaling_raw,
+                                  float* dL_drotation_raw, float lambda_sh_sparsity, int debug, void* stream,
+                                  float* dL_dmean2D_abs, float* abs_workspace, size_t abs_workspace_floats);
+
 /* Debug accessor for bit-exact checks of the integer stages (SURVEY.md 8b "provide a debug accessor"):
  * copies, out of the opaque blobs of a finished forward, the sorted list in the REFERENCE's format --
  * keys[i] = (tile << 32) | depth_bits (rasterizer_impl.cu:110-113), point_list, per-tile ranges,

@@ -76,6 +76,9 @@ UNITS = {  # depth_sort.h roles are instantiated in preprocess.hip (fused with t
     "normals.hip": EXACT,
     # camera gradients: the per-Gaussian backward's chain continued to the camera, so the per-Gaussian backward's flags
     "camera_bwd.hip": EXACT,
+    # per-Gaussian sums of the abs columns an ABS backward blend leaves (absolute screen-space gradients): plain adds in a
+    # fixed order, nothing a flag could change
+    "absgrad.hip": [],
     "capi.hip": [],
     # the pass driver behind the C ABI (split out of capi.hip): compiled as it was there
     "pass_driver.hip": [],

@@ -240,6 +240,22 @@ __device__ __forceinline__ float wave_reduce9(const SplatSums& g, int lane)
     return z;
 }
 
+// The two abs sums of an ABS pass (blend_math.h SplatAbsSums), reduced the same transposing way: the first step exchanges
+// the two between partner lanes, one register goes through the other five.  Afterwards every even lane holds the wave total
+// of ax and every odd lane that of ay.  7 VALU + 2 DS per reduced entry.
+__device__ __forceinline__ float wave_reduce2(float ax, float ay, int lane)
+{
+    R3_DPP_ADD(ax, 0xb1, 0xf);   // quad_perm [1,0,3,2]
+    R3_DPP_ADD(ay, 0xb1, 0xf);
+    float z = (lane & 1) ? ay : ax;
+    R3_DPP_ADD(z, 0x4e, 0xf);    // quad_perm [2,3,0,1]
+    R3_DPP_ADD(z, 0x124, 0xf);   // row_ror:4
+    R3_DPP_ADD(z, 0x128, 0xf);   // row_ror:8
+    z += __shfl_xor(z, 16);
+    z += __shfl_xor(z, 32);
+    return z;
+}
+
 template <int PPL>
 __device__ __forceinline__ void pixel_of(int tile_x, int tile_y, int part, int q, int lane, int* px, int* py)
 {
@@ -470,6 +486,7 @@ void issue_blend_forward(const FwdPlan& p, const BlendFwdArgs* a, hipStream_t s)
 // backward
 // ------------------------------------------------------------------------------------------------
 constexpr int kGradStride = 9;   // the 9 sums of a list entry (odd stride: the flush reads without bank conflicts)
+constexpr int kGradStrideAbs = 11;   // ABS: and the two abs sums (still odd)
 
 // REUSE: the region pre-test masks are the forward's (BinState::quad_masks) instead of being recomputed per chunk.
 // 6 waves per SIMD (80 VGPRs, three spilled values outside the entry loop).  With round 2's 96-register body 5 and 6
@@ -484,14 +501,23 @@ constexpr int kGradStride = 9;   // the 9 sums of a list entry (odd stride: the 
 // FIRST: this is the first kernel of the backward (no unit order): it installs the pass block for the kernels behind it and
 // reads its own arguments from the kernarg segment; otherwise unit_order_kernel (unit_order.hip) did and the arguments come from the block
 // (a graph replay refreshes the by-value arguments of its first node only).
-template <int PPL, bool REUSE, bool FIRST>
-__global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdPassArgs v)
+// ABS (r3dgs_backward_absgrad): the walk also sums, per entry, the absolute values of what each pixel adds to dL_dmean2D
+// (blend_math.h bwd_accumulate_abs): 11 sums per entry are accumulated, reduced, parked and cleared, and the two abs columns
+// leave in columns 9 and 10 of the entry's slab row, which the other instantiations write as zeros.  Its register budget is
+// its own (bwd_waves below); the instantiations without ABS are compiled exactly as before the parameter existed.
+// Waves per SIMD: 6 as ever without ABS.  With ABS the body needs 93 VGPRs (REUSE) / 98 (the pre-test repeated): 5 waves hold
+// the first without a spill and the second only with one, so that one is built for 4 (rule 1: a wave is
+// not bought with spills; profiles/absgrad_kernel_resources.txt).
+constexpr int bwd_waves(bool reuse, bool abs) { return abs ? (reuse ? 5 : 4) : 6; }
+template <int PPL, bool REUSE, bool FIRST, bool ABS = false>
+__global__ __launch_bounds__(64, bwd_waves(REUSE, ABS)) void blend_bwd_kernel(BwdPassArgs* dst, BwdPassArgs v)
 {
+    constexpr int GS = ABS ? kGradStrideAbs : kGradStride;
     __shared__ LdsRec s_rec[kChunk];
     if (FIRST && blockIdx.x == 0) install_block_from_kernarg(dst, (int)threadIdx.x, 64);
     R3_TL_BEGIN(blockIdx.x)
     const BlendBwdArgs a = FIRST ? v.blend : dst->blend;
-    __shared__ float s_grad[kChunk * kGradStride];
+    __shared__ float s_grad[kChunk * GS];
 #ifndef R3_OLD_TRIP_FORMS
     __shared__ float4 s_zero[3];   // nine zeros (and three spare): what the sums of an entry are reset from, see below
     if (threadIdx.x < 3) s_zero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -607,6 +633,8 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
     float* const s_grad_slot = s_grad + reduce9_component(lane);
     SplatSums sg;   // zero whenever an entry starts: cleared after every reduction, untouched by entries without a hit
     sg.sx = sg.sy = sg.sxx = sg.sxy = sg.syy = sg.sm = sg.r = sg.g = sg.b = 0.f;
+    SplatAbsSums sa;   // ABS only
+    sa.ax = sa.ay = 0.f;
     for (int cbase = cfirst; cbase >= (int)lo; cbase -= kChunk) {
         __syncthreads();
         stage_entry(s_rec[lane], nxa, nxb, nxc);
@@ -658,13 +686,20 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
                     // `hit` only gates the reduction, so it may over-approximate: power > 0 (a degenerate conic) is
                     // left out, such an entry then reduces and stores the zeros it accumulated.
                     hit |= __builtin_amdgcn_ballot_w64(e.in_list) & __builtin_amdgcn_ballot_w64(e.visible);
-                    if (valid) bwd_accumulate(s, e, pix[q], sg);
+                    if (valid) {
+                        if (ABS) bwd_accumulate_abs(s, e, pix[q], sa);
+                        bwd_accumulate(s, e, pix[q], sg);
+                    }
                 }
             if (hit != 0ull) {
                 const float z = wave_reduce9(sg, lane);
-                int joff = j * kGradStride;
+                int joff = j * GS;
                 asm("" : "+s"(joff));   // stays a scalar multiply + v_add (else: one quarter-rate v_mad_u64_u32)
                 if (writer) s_grad_slot[joff] = z;
+                if (ABS) {
+                    const float z2 = wave_reduce2(sa.ax, sa.ay, lane);
+                    if (lane < 2) s_grad[joff + kGradStride + lane] = z2;
+                }
                 contributed |= 1ull << j;
 #ifndef R3_OLD_TRIP_FORMS
                 {   // The nine sums are cleared by three broadcast LDS reads of zeros (2 x b128 + b32) instead of nine v_mov:
@@ -678,9 +713,16 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
                     const float z2 = *(const volatile float __attribute__((address_space(3)))*)(zp + 2);
                     sg.sx = z0.x; sg.sy = z0.y; sg.sxx = z0.z; sg.sxy = z0.w;
                     sg.syy = z1.x; sg.sm = z1.y; sg.r = z1.z; sg.g = z1.w; sg.b = z2;
+                    if (ABS) {   // the spare zeros of s_zero
+                        const volatile float __attribute__((address_space(3)))* zf =
+                            (const volatile float __attribute__((address_space(3)))*)(zp + 2);
+                        sa.ax = zf[1];
+                        sa.ay = zf[2];
+                    }
                 }
 #else
                 sg.sx = sg.sy = sg.sxx = sg.sxy = sg.syy = sg.sm = sg.r = sg.g = sg.b = 0.f;
+                sa.ax = sa.ay = 0.f;
 #endif
             }
         }
@@ -696,7 +738,7 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
             const uint32_t slot = __float_as_uint(c.w) + ((uint32_t)tile_y - (rect_min >> 16)) * width +
                                   ((uint32_t)tile_x - (rect_min & 0xffffu));
             float4* dst = reinterpret_cast<float4*>(a.pair_grad + (size_t)slot * kPairStride);   // 48-B row, 3 x 16 B
-            const float* src = s_grad + lane * kGradStride;
+            const float* src = s_grad + lane * GS;
             SplatSums u;
             u.sx = src[0];
             u.sy = src[1];
@@ -711,7 +753,16 @@ __global__ __launch_bounds__(64, 6) void blend_bwd_kernel(BwdPassArgs* dst, BwdP
             const SplatGrad g = splat_grad_of(load_splat(s_rec[lane]), u);
             dst[0] = make_float4(g.mx * half_w, g.my * half_h, g.cA, g.cB);
             dst[1] = make_float4(g.cC, g.op, g.r, g.g);
-            dst[2] = make_float4(g.b, 0.f, 0.f, 0.f);
+            if (ABS) {
+                SplatAbsSums ua;
+                ua.ax = src[kGradStride];
+                ua.ay = src[kGradStride + 1];
+                float gax, gay;
+                splat_abs_grad_of(load_splat(s_rec[lane]), ua, &gax, &gay);
+                dst[2] = make_float4(g.b, gax * half_w, gay * half_h, 0.f);
+            } else {
+                dst[2] = make_float4(g.b, 0.f, 0.f, 0.f);
+            }
             if (kPairStride >= 16) dst[3] = make_float4(0.f, 0.f, 0.f, 0.f);   // 64-byte rows: the whole burst is written
             a.pair_flag[slot] = 1;
         }
@@ -726,15 +777,15 @@ extern "C" int r3dgs_debug_timeline(unsigned long long* host, int n)
 }
 #endif
 
-template <bool REUSE>
+template <bool REUSE, bool ABS>
 static void launch_bwd(uint32_t nblocks, uint32_t units_cap, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s)
 {
     if (v.blend.unit_order) {
         static const int lds_pad = env_int("R3DGS_BWD_LDS_PAD", 0, 0, 65536);
         // one workgroup per unit the pass MAY have (those beyond its count leave at once)
-        hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, false>), dim3(units_cap), dim3(64), lds_pad, s, dst, v);
+        hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, false, ABS>), dim3(units_cap), dim3(64), lds_pad, s, dst, v);
     } else {
-        hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, true>), dim3(nblocks), dim3(64), 0, s, dst, v);
+        hipLaunchKernelGGL((blend_bwd_kernel<4, REUSE, true, ABS>), dim3(nblocks), dim3(64), 0, s, dst, v);
     }
 }
 
@@ -742,10 +793,16 @@ void issue_blend_backward(const BwdPlan& p, BwdPassArgs* dst, const BwdPassArgs&
 {
     // one wave per tile (PPL = 4): the per-pair gradient slab has exactly one owner per (tile, Gaussian)
     const uint32_t nblocks = (uint32_t)(p.gx * p.gy);   // == v.blend.nblocks
-    if (v.blend.quad_masks)
-        launch_bwd<true>(nblocks, p.units_cap, dst, v, s);
-    else
-        launch_bwd<false>(nblocks, p.units_cap, dst, v, s);
+    if (p.absgrad) {
+        if (v.blend.quad_masks)
+            launch_bwd<true, true>(nblocks, p.units_cap, dst, v, s);
+        else
+            launch_bwd<false, true>(nblocks, p.units_cap, dst, v, s);
+    } else if (v.blend.quad_masks) {
+        launch_bwd<true, false>(nblocks, p.units_cap, dst, v, s);
+    } else {
+        launch_bwd<false, false>(nblocks, p.units_cap, dst, v, s);
+    }
 }
 
 }  // namespace r3

@@ -314,6 +314,39 @@ R3_HD void bwd_accumulate(const QSplat& s, const BwdEval& e, BwdPix& p, SplatSum
     a.syy = fmaf(m, e.o.dyy, a.syy);
 }
 
+// Absolute screen-space gradients (AbsGS; the blend kernel's ABS instantiations): next to the signed moments, the sums over a
+// Gaussian's pixels of the ABSOLUTE value of what each pixel adds to dL_dmean2D (backward.cu:553-554),
+//   |k (2 qa dx + qb dy) m|,  |k (2 qc dy + qb dx) m|     with k and m as in splat_grad_of / bwd_accumulate.
+// The signs are per pixel, so these cannot be formed from the moments; k is the entry's and leaves the sum
+// (splat_abs_grad_of).  bwd_accumulate_abs is called IN FRONT of bwd_accumulate for the same (pixel, entry) -- it reads the
+// pixel state that call advances -- and spells m out exactly as bwd_accumulate does, so that a compiler that sees both
+// keeps one copy of the common part: six more operations per (pixel, entry).
+struct SplatAbsSums {
+    float ax, ay;
+};
+
+R3_HD void bwd_accumulate_abs(const QSplat& s, const BwdEval& e, const BwdPix& p, SplatAbsSums& a)
+{
+    const float ra = R3_RCP(1.0f - e.alpha);
+    const float T = p.T * ra;
+    const float cg = s.r * p.g0 + s.g * p.g1 + s.b * p.g2;
+    const float behind = cg - p.A;
+    const float dL_dalpha = behind * T;
+    const float m = e.G * dL_dalpha;
+    const float tx = fmaf(2.f * s.qa, e.o.dx, s.qb * e.o.dy);
+    const float ty = fmaf(2.f * s.qc, e.o.dy, s.qb * e.o.dx);
+    a.ax = fmaf(fabsf(tx), fabsf(m), a.ax);
+    a.ay = fmaf(fabsf(ty), fabsf(m), a.ay);
+}
+
+// abs sums -> the two abs columns, WITHOUT the viewport factors (as SplatGrad::mx / my)
+R3_HD void splat_abs_grad_of(const QSplat& s, const SplatAbsSums& u, float* gx, float* gy)
+{
+    const float k = fabsf(s.op * kLn2);
+    *gx = k * u.ax;
+    *gy = k * u.ay;
+}
+
 // Whole step for one (pixel, entry) pair, adding into `a`; returns true when the entry contributed.
 R3_HD bool bwd_step(const Splat& s0, float pxf, float pyf, uint32_t pos, BwdPix& p, SplatGrad& a)
 {

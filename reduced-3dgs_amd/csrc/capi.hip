@@ -285,6 +285,30 @@ long long r3dgs_reserve_overflow_events(int* last_num_rendered, int* last_reserv
     return reserve_overflow_events(last_num_rendered, last_reserve);
 }
 
+// BwdCall's fields are the parameter list of r3dgs_backward, in this order, with the three blobs as one
+static BwdCall backward_call(int P, const int* D, int M, int R, const float* background, int width, int height,
+                             const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                             const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                             char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D,
+                             float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                             float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream)
+{
+    return {P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+            rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            {geom_buffer, binning_buffer, image_buffer}, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+            dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, lambda_sh_sparsity, debug,
+            static_cast<hipStream_t>(stream), nullptr, nullptr, 0};
+}
+
+static void ask_absgrad(BwdCall& c, float* dL_dmean2D_abs, float* abs_workspace, size_t abs_workspace_floats)
+{
+    c.absgrad = 1;
+    c.dL_dmean2D_abs = dL_dmean2D_abs;
+    c.abs_workspace = abs_workspace;
+    c.abs_workspace_floats = abs_workspace_floats;
+}
+
 int r3dgs_backward(int P, const int* D, int M, int R, const float* background, int width, int height,
                    const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                    float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -293,12 +317,33 @@ int r3dgs_backward(int P, const int* D, int M, int R, const float* background, i
                    float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
                    float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream)
 {
-    return guarded([&]() {   // BwdCall's fields are this list, in this order, with the three blobs as one
-        return backward_pass({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
-                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                              {geom_buffer, binning_buffer, image_buffer}, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
-                              dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, lambda_sh_sparsity, debug,
-                              static_cast<hipStream_t>(stream), nullptr, nullptr, 0});
+    return guarded([&]() {
+        return backward_pass(backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                           scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                           tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                           lambda_sh_sparsity, debug, stream));
+    });
+}
+
+size_t r3dgs_absgrad_workspace_floats(int R) { return r3::absgrad_workspace_floats((size_t)(R > 0 ? R : 1)); }
+
+int r3dgs_backward_absgrad(int P, const int* D, int M, int R, const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                           float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                           char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix, float* dL_dmean2D,
+                           float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                           float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_sh_sparsity, int debug, void* stream,
+                           float* dL_dmean2D_abs, float* abs_workspace, size_t abs_workspace_floats)
+{
+    return guarded([&]() {
+        BwdCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                                  rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                                  geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+                                  dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, lambda_sh_sparsity, debug, stream);
+        ask_absgrad(c, dL_dmean2D_abs, abs_workspace, abs_workspace_floats);
+        return backward_pass(c);
     });
 }
 
@@ -358,6 +403,26 @@ long long r3dgs_forward_params_reserved(char* geom_buffer, char* binning_buffer,
     });
 }
 
+static BwdCall backward_params_call(int P, const int* D, int M, int R, const float* background, int width, int height,
+                                    const float* means3D, const float* features_dc, const float* features_rest,
+                                    const float* scaling_raw, float scale_modifier, const float* rotation_raw,
+                                    const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                    float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                    const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                    float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dfeatures_dc,
+                                    float* dL_dfeatures_rest, float* dL_dscaling_raw, float* dL_drotation_raw,
+                                    float lambda_sh_sparsity, int debug, void* stream)
+{
+    check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
+    if (P > 0 && (!dL_dfeatures_dc || (M > 1 && !dL_dfeatures_rest)))
+        throw r3::Error("raw-parameter path: a gradient output pointer is NULL");
+    return {P, D, M, R, background, width, height, means3D, features_dc, nullptr, scaling_raw, scale_modifier,
+            rotation_raw, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            {geom_buffer, binning_buffer, image_buffer}, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+            dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dfeatures_dc, dL_dscaling_raw, dL_drotation_raw,
+            lambda_sh_sparsity, debug, static_cast<hipStream_t>(stream), features_rest, dL_dfeatures_rest, 1};
+}
+
 int r3dgs_backward_params(int P, const int* D, int M, int R, const float* background, int width, int height,
                           const float* means3D, const float* features_dc, const float* features_rest, const float* scaling_raw,
                           float scale_modifier, const float* rotation_raw, const float* viewmatrix, const float* projmatrix,
@@ -368,14 +433,34 @@ int r3dgs_backward_params(int P, const int* D, int M, int R, const float* backgr
                           int debug, void* stream)
 {
     return guarded([&]() {
-        check_params(P, D, M, features_dc, features_rest, scaling_raw, rotation_raw);
-        if (P > 0 && (!dL_dfeatures_dc || (M > 1 && !dL_dfeatures_rest)))
-            throw r3::Error("raw-parameter path: a gradient output pointer is NULL");
-        return backward_pass({P, D, M, R, background, width, height, means3D, features_dc, nullptr, scaling_raw, scale_modifier,
-                              rotation_raw, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                              {geom_buffer, binning_buffer, image_buffer}, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
-                              dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dfeatures_dc, dL_dscaling_raw, dL_drotation_raw,
-                              lambda_sh_sparsity, debug, static_cast<hipStream_t>(stream), features_rest, dL_dfeatures_rest, 1});
+        return backward_pass(backward_params_call(P, D, M, R, background, width, height, means3D, features_dc, features_rest,
+                                                  scaling_raw, scale_modifier, rotation_raw, viewmatrix, projmatrix, campos,
+                                                  tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                                  dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
+                                                  dL_dfeatures_dc, dL_dfeatures_rest, dL_dscaling_raw, dL_drotation_raw,
+                                                  lambda_sh_sparsity, debug, stream));
+    });
+}
+
+int r3dgs_backward_params_absgrad(int P, const int* D, int M, int R, const float* background, int width, int height,
+                                  const float* means3D, const float* features_dc, const float* features_rest,
+                                  const float* scaling_raw, float scale_modifier, const float* rotation_raw,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dfeatures_dc, float* dL_dfeatures_rest,
+                                  float* dL_dscaling_raw, float* dL_drotation_raw, float lambda_sh_sparsity, int debug,
+                                  void* stream, float* dL_dmean2D_abs, float* abs_workspace, size_t abs_workspace_floats)
+{
+    return guarded([&]() {
+        if (P > 0) check_absgrad_args(R, binning_buffer != nullptr, dL_dmean2D_abs, abs_workspace, abs_workspace_floats);
+        BwdCall c = backward_params_call(P, D, M, R, background, width, height, means3D, features_dc, features_rest, scaling_raw,
+                                         scale_modifier, rotation_raw, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                                         geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+                                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dfeatures_dc, dL_dfeatures_rest, dL_dscaling_raw,
+                                         dL_drotation_raw, lambda_sh_sparsity, debug, stream);
+        ask_absgrad(c, dL_dmean2D_abs, abs_workspace, abs_workspace_floats);
+        return backward_pass(c);
     });
 }
 

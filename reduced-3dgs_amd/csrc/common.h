@@ -751,10 +751,19 @@ struct FwdPassArgs {
     const float* shs_rest;   // raw-parameter forward only: features_rest [P,M-1,3] (see FwdInputs)
     QuantInputs quant;       // quantised forward only
 };
+// Absolute screen-space gradients (r3dgs_backward_absgrad; absgrad.hip): where the per-Gaussian sums of the slab's abs columns
+// go.  Everything else those kernels need is the pair reduction's (PairReduceArgs).
+struct AbsGradArgs {
+    float* out;         // [P,3] dL_dmean2D_abs (third column zero); null: not an abs pass
+    float* workspace;   // [absgrad_workspace_floats(R)] the caller's: leading / trailing pieces of the runs a 64-pair group cuts
+};
+constexpr int kAbsCols = 2, kAbsPiece = 2 * kAbsCols;   // floats per group in the workspace: leading pair, trailing pair
+inline size_t absgrad_workspace_floats(size_t R) { return (R / 64 + 1) * (size_t)kAbsPiece; }
 struct BwdPassArgs {
     BlendBwdArgs blend;
     PairReduceArgs reduce;
     PreBwdArgs pre;
+    AbsGradArgs abs;   // BEHIND everything the plain pass uses (as PreBwdArgs::shs_rest): no existing field moves
 };
 static_assert(sizeof(FwdPassArgs) <= 3072 && sizeof(BwdPassArgs) <= 3072, "pass blocks travel as by-value kernel arguments");
 
@@ -782,6 +791,7 @@ struct BwdPlan {
     int has_pairs;         // 0: the forward ran with an empty reservation (P > 0, no binning blob)
     int f64_chain;         // the per-Gaussian backward evaluates the covariance chain in double (gauss_math.h; default)
     int raw_params;        // raw-parameter backward (BwdOutputs::dL_dsh_dc / dL_dsh_rest; activation backward applied)
+    int absgrad;           // abs pass (AbsGradArgs): the blend's ABS instantiations and the abs reduction behind them
 };
 
 // stage ids of the optional per-stage timers (pass_driver.hip)
@@ -823,6 +833,7 @@ void issue_blend_forward(const FwdPlan& p, const BlendFwdArgs* a, hipStream_t s)
 void issue_unit_order(const BwdPlan& p, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s);   // installs the block (if it runs)
 void issue_blend_backward(const BwdPlan& p, BwdPassArgs* dst, const BwdPassArgs& v, hipStream_t s);   // installs the block otherwise
 void issue_pair_reduce(const BwdPlan& p, const PairReduceArgs* a, hipStream_t s);
+void issue_absgrad_reduce(const BwdPlan& p, const BwdPassArgs* a, hipStream_t s);   // absgrad.hip; in front of issue_pair_reduce
 void issue_preprocess_backward(const BwdPlan& p, const PreBwdArgs* a, hipStream_t s);
 
 void launch_colour_variance_accumulate(int P, const int* D, int M, int max_sh_deg, const float* means3D,

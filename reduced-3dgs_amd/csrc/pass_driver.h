@@ -80,7 +80,23 @@ struct BwdCall {
     const float* shs_rest;
     float* dL_dsh_rest;
     int raw;
+    // r3dgs_backward_absgrad / r3dgs_backward_params_absgrad: the pass also returns the abs columns (common.h AbsGradArgs);
+    // absgrad == 0: the plain pass, the three fields behind it are not looked at
+    int absgrad = 0;
+    float* dL_dmean2D_abs = nullptr;
+    float* abs_workspace = nullptr;
+    size_t abs_workspace_floats = 0;
 };
+
+// the refusals of the *_absgrad entry points (looked at before anything else of the call)
+inline void check_absgrad_args(int R, bool has_binning, const float* out, const float* workspace, size_t workspace_floats)
+{
+    if (!out) throw Error("absgrad: dL_dmean2D_abs is NULL");
+    const size_t need = absgrad_workspace_floats((size_t)(R > 0 ? R : 1));
+    if (has_binning && (!workspace || workspace_floats < need))
+        throw Error("absgrad: the workspace holds " + std::to_string(workspace ? workspace_floats : 0) +
+                    " floats, r3dgs_absgrad_workspace_floats(R) = " + std::to_string(need));
+}
 
 struct Allocators {   // the exact-size contract's callbacks
     r3dgs_alloc_fn geometry;

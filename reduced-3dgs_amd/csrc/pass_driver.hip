@@ -277,6 +277,7 @@ struct GraphCtx {
     hipGraphNode_t node0 = nullptr;
     hipKernelNodeParams node0_params = {};
     uint64_t last_use = 0;
+    bool pinned = false;   // a caller's captured graph refers to d_args (launch_graph): never evicted
 };
 std::mutex g_ctx_mu;
 std::map<CtxKey, GraphCtx> g_graphs;
@@ -302,9 +303,10 @@ hipStream_t capture_stream(int dev)
 void evict_graphs_locked()
 {
     while (g_graphs.size() > kMaxGraphs) {
-        auto victim = g_graphs.begin();
+        auto victim = g_graphs.end();
         for (auto it = g_graphs.begin(); it != g_graphs.end(); ++it)
-            if (it->second.last_use < victim->second.last_use) victim = it;
+            if (!it->second.pinned && (victim == g_graphs.end() || it->second.last_use < victim->second.last_use)) victim = it;
+        if (victim == g_graphs.end()) return;   // every entry is held by a caller's graph
         // the exec may still be queued on its stream: wait for that stream before tearing it down (rare path)
         (void)hipStreamSynchronize(victim->first.stream);
         if (victim->second.exec) (void)hipGraphExecDestroy(victim->second.exec);
@@ -375,9 +377,11 @@ void issue_backward(const BwdPlan& p, BwdPassArgs* d, const BwdPassArgs& args, h
         h.begin(kBlendBwdKernel, s);
         issue_blend_backward(p, d, args, s);
         h.end(kBlendBwdKernel, "blend backward kernel", s);
+        if (p.absgrad) issue_absgrad_reduce(p, d, s);   // reads the pair flags pair_reduce clears
         issue_pair_reduce(p, &d->reduce, s);
     } else {
         launch_write_args(d, args, s);
+        if (p.absgrad) issue_absgrad_reduce(p, d, s);   // nothing was binned: zeros
     }
     h.end(kBlendBwd, "blend backward", s);
     h.begin(kPreBwd, s);
@@ -399,6 +403,24 @@ template <class Block, class Plan, class IssueFn>
 void launch_graph(const CtxKey& key, const Plan& plan, const Block& args, hipStream_t s, IssueFn&& issue)
 {
     std::lock_guard<std::mutex> lk(g_ctx_mu);
+    // Is the caller capturing `s` into a graph of its own (torch.cuda.graph)?  (The null stream cannot be captured, and is what a
+    // trainer usually runs on: nothing is asked for it.)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (s != nullptr) R3_HIP(hipStreamIsCapturing(s, &capturing));
+    if (capturing == hipStreamCaptureStatusActive) {
+        // A launch of our exec would enter the caller's graph as a copy of the chain with the arguments of the pass it was
+        // captured from.  The chain goes into the caller's graph as it is instead, with THIS pass's block in its first node.
+        // The shape's block must exist already -- nothing may be allocated or captured inside the caller's capture -- and
+        // stays for good from here on: the caller's graph refers to it for as long as it is replayed.
+        auto it = g_graphs.find(key);
+        if (it == g_graphs.end() || !it->second.exec)
+            throw Error("this pass is being captured into a graph of the caller's, but its shape has not run on this stream "
+                        "yet: run the step once on the stream before capturing it (warm-up)");
+        it->second.pinned = true;
+        it->second.last_use = ++g_use_clock;
+        issue(plan, static_cast<Block*>(it->second.d_args), args, s);
+        return;
+    }
     GraphCtx& c = g_graphs[key];
     if (!c.exec) {
         try {
@@ -693,6 +715,7 @@ Block* direct_args(int dev, int kind, hipStream_t s)
 
 void validate_backward(const BwdCall& c)
 {
+    if (c.absgrad) check_absgrad_args(c.R, c.blobs.binning != nullptr, c.dL_dmean2D_abs, c.abs_workspace, c.abs_workspace_floats);
     if (!c.blobs.geom || !c.blobs.image) throw Error("state buffers must not be NULL");
     if (!c.means3D || !c.viewmatrix || !c.projmatrix || !c.campos || !c.background || !c.dL_dpix)
         throw Error("a required pointer is NULL");
@@ -720,6 +743,7 @@ BwdPlan make_bwd_plan(const BwdCall& c)
     p.units_cap = bwd_units_cap(p.reserve, grid);
     p.f64_chain = f64_chain();
     p.raw_params = c.raw ? 1 : 0;
+    p.absgrad = c.absgrad ? 1 : 0;
     return p;
 }
 
@@ -820,13 +844,18 @@ void fill_bwd_args(BwdPassArgs& a, const BwdPlan& plan, const BwdCall& c, const 
     static const int stagger = env_int("R3DGS_PREBWD_STAGGER", 127, 0, 4096);   // 0 / 64 / 127 / 254 / 508:
                                                                                  // 84.0 / 79.5 / 79.8 / 79.7 / 88.6 us
     pb.stagger = stagger;
+    if (plan.absgrad) {
+        a.abs.out = c.dL_dmean2D_abs;
+        a.abs.workspace = c.abs_workspace;
+    }
 }
 
 uint32_t bwd_flags(const BwdPlan& p, const BwdPassArgs& a)
 {
     return ((uint32_t)p.has_pairs << 3) | ((uint32_t)p.layout.wide << 4) |
            ((uint32_t)(a.blend.unit_order != nullptr) << 6) |   // one more kernel in the chain
-           ((uint32_t)p.f64_chain << 7) | ((uint32_t)p.raw_params << 8);
+           ((uint32_t)p.f64_chain << 7) | ((uint32_t)p.raw_params << 8) |
+           ((uint32_t)p.absgrad << 9);   // the abs pass is a chain of its own: other blend instantiations, three more kernels
 }
 
 }  // namespace

@@ -86,7 +86,10 @@ using at::Tensor;
     X(r3dgs_alpha_regul_backward, false)                      \
     X(r3dgs_densification_stats, false)                       \
     X(r3dgs_quantised_codebook_grad_workspace_bytes, false)   \
-    X(r3dgs_quantised_codebook_grad, false)
+    X(r3dgs_quantised_codebook_grad, false)                   \
+    X(r3dgs_absgrad_workspace_floats, false)                  \
+    X(r3dgs_backward_absgrad, false)                          \
+    X(r3dgs_backward_params_absgrad, false)
 
 struct Api {   // (types taken from the C headers)
 #define R3_MEMBER(name, required) decltype(&::name) name = nullptr;
@@ -260,20 +263,29 @@ ReservedPass forward_reserved(
 
 // RasterizeGaussiansBackwardCUDA (rasterize_points.cu:224-305).  `capacity`: the pair capacity the forward carved the
 // binning blob with.  Every element of every output is written by the library: at::empty, no fills.
-std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
-                             const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp,
-                             const Tensor& viewmatrix, const Tensor& projmatrix, double tan_fovx, double tan_fovy,
-                             const Tensor& dL_dout_color, const Tensor& sh, const Tensor& degrees, const Tensor& campos,
-                             const Tensor& geomBuffer, int64_t capacity, const Tensor& binningBuffer, const Tensor& imageBuffer,
-                             double lambda_sh_sparsity, bool debug, bool want_conic)
+// absgrad: through r3dgs_backward_absgrad, + dL_dmeans2D_abs [P,3] as the last element (the workspace is this call's own).
+std::vector<Tensor> backward_impl(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
+                                  const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp,
+                                  const Tensor& viewmatrix, const Tensor& projmatrix, double tan_fovx, double tan_fovy,
+                                  const Tensor& dL_dout_color, const Tensor& sh, const Tensor& degrees, const Tensor& campos,
+                                  const Tensor& geomBuffer, int64_t capacity, const Tensor& binningBuffer, const Tensor& imageBuffer,
+                                  double lambda_sh_sparsity, bool debug, bool want_conic, bool absgrad)
 {
     need_bound();
+    if (absgrad) {
+        need(api.r3dgs_backward_absgrad, "absolute-gradient entry points (r3dgs_backward_absgrad)");
+        need(api.r3dgs_absgrad_workspace_floats, "absolute-gradient entry points (r3dgs_backward_absgrad)");
+    }
     const c10::Device dev = means3D.device();
     const int P = (int)means3D.size(0);
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
     const int M = (sh.defined() && sh.numel() != 0) ? (int)sh.size(1) : 0;
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    if (P == 0) return zero_grads(f32, {{0, 3}, {0, 3}, {0, 1}, {0, 3}, {0, 6}, {0, M, 3}, {0, 3}, {0, 4}});
+    if (P == 0) {
+        std::vector<Tensor> z = zero_grads(f32, {{0, 3}, {0, 3}, {0, 1}, {0, 3}, {0, 6}, {0, M, 3}, {0, 3}, {0, 4}});
+        if (absgrad) z.push_back(at::zeros({0, 3}, f32));
+        return z;
+    }
     Tensor dL_dmeans3D = at::empty({P, 3}, f32), dL_dmeans2D = at::empty({P, 3}, f32), dL_dcolors = at::empty({P, 3}, f32);
     Tensor dL_dopacity = at::empty({P, 1}, f32), dL_dcov3D = at::empty({P, 6}, f32), dL_dsh = at::empty({P, M, 3}, f32);
     Tensor dL_dscales = at::empty({P, 3}, f32), dL_drotations = at::empty({P, 4}, f32);
@@ -283,20 +295,45 @@ std::vector<Tensor> backward(const Tensor& background, const Tensor& means3D, co
     const Tensor vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev), cp = dev_f32(campos, dev);
     const Tensor g = dev_f32(dL_dout_color, dev), shc = dev_f32(sh, dev), deg = dev_i32(degrees, dev), rad = dev_i32(radii, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int st = api.r3dgs_backward(
-        P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, opt_ptr<float>(m3), opt_ptr<float>(shc),
-        opt_ptr<float>(col), opt_ptr<float>(sc), (float)scale_modifier, opt_ptr<float>(rot), opt_ptr<float>(cov),
-        opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy, opt_ptr<int>(rad),
-        blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g), dL_dmeans2D.data_ptr<float>(),
-        dL_dconic.defined() ? dL_dconic.data_ptr<float>() : nullptr, dL_dopacity.data_ptr<float>(),
-        dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(),
-        M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
-        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev));
+    Tensor dL_abs, abs_ws;
+    if (absgrad) {
+        dL_abs = at::empty({P, 3}, f32);
+        abs_ws = at::empty({(int64_t)api.r3dgs_absgrad_workspace_floats((int)capacity)}, f32);
+    }
+#define R3_BACKWARD_ARGS                                                                                                  \
+    P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, opt_ptr<float>(m3), opt_ptr<float>(shc),            \
+        opt_ptr<float>(col), opt_ptr<float>(sc), (float)scale_modifier, opt_ptr<float>(rot), opt_ptr<float>(cov),         \
+        opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy, opt_ptr<int>(rad),  \
+        blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g),                          \
+        dL_dmeans2D.data_ptr<float>(), dL_dconic.defined() ? dL_dconic.data_ptr<float>() : nullptr,                       \
+        dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),                       \
+        dL_dcov3D.data_ptr<float>(), M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(),                \
+        dL_drotations.data_ptr<float>(), (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev)
+    const int st = absgrad ? api.r3dgs_backward_absgrad(R3_BACKWARD_ARGS, dL_abs.data_ptr<float>(), abs_ws.data_ptr<float>(),
+                                                        (size_t)abs_ws.numel())
+                           : api.r3dgs_backward(R3_BACKWARD_ARGS);
+#undef R3_BACKWARD_ARGS
     if (st < 0) fail("rasterize_gaussians_backward");
     std::vector<Tensor> out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
     if (want_conic) out.push_back(dL_dconic);
+    if (absgrad) out.push_back(dL_abs);
     return out;
 }
+
+#define R3_BACKWARD_PARAMS                                                                                                     \
+    const Tensor &background, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &scales,          \
+        const Tensor &rotations, double scale_modifier, const Tensor &cov3D_precomp, const Tensor &viewmatrix,                 \
+        const Tensor &projmatrix, double tan_fovx, double tan_fovy, const Tensor &dL_dout_color, const Tensor &sh,             \
+        const Tensor &degrees, const Tensor &campos, const Tensor &geomBuffer, int64_t capacity, const Tensor &binningBuffer,  \
+        const Tensor &imageBuffer, double lambda_sh_sparsity, bool debug, bool want_conic
+#define R3_BACKWARD_PASS                                                                                                       \
+    background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,    \
+        tan_fovy, dL_dout_color, sh, degrees, campos, geomBuffer, capacity, binningBuffer, imageBuffer, lambda_sh_sparsity,    \
+        debug, want_conic
+std::vector<Tensor> backward(R3_BACKWARD_PARAMS) { return backward_impl(R3_BACKWARD_PASS, false); }
+std::vector<Tensor> backward_absgrad(R3_BACKWARD_PARAMS) { return backward_impl(R3_BACKWARD_PASS, true); }
+#undef R3_BACKWARD_PARAMS
+#undef R3_BACKWARD_PASS
 
 // ---- raster from the model's raw parameters (r3dgs_*_params): the same marshalling as diff_gaussian_rasterization/_C.py's
 // rasterize_gaussian_params*; refusals (shapes, dtypes, contiguity) carry the same messages.
@@ -422,20 +459,30 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> forward_params(
 
 // -> (dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_dfeatures_dc, dL_dfeatures_rest, dL_dscaling, dL_drotation): gradients of
 // the tensors passed in, each written whole by the library into at::empty storage of the leaf's own shape
-std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz, const Tensor& radii, const Tensor& features_dc,
-                                    const Tensor& features_rest, const Tensor& degrees, const Tensor& opacity,
-                                    const Tensor& scaling, const Tensor& rotation, double scale_modifier, const Tensor& viewmatrix,
-                                    const Tensor& projmatrix, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color,
-                                    const Tensor& campos, const Tensor& geomBuffer, int64_t capacity, const Tensor& binningBuffer,
-                                    const Tensor& imageBuffer, double lambda_sh_sparsity, bool debug)
+// absgrad: through r3dgs_backward_params_absgrad, + dL_dmeans2D_abs [P,3] as the last element
+std::vector<Tensor> backward_params_impl(const Tensor& background, const Tensor& xyz, const Tensor& radii, const Tensor& features_dc,
+                                         const Tensor& features_rest, const Tensor& degrees, const Tensor& opacity,
+                                         const Tensor& scaling, const Tensor& rotation, double scale_modifier,
+                                         const Tensor& viewmatrix, const Tensor& projmatrix, double tan_fovx, double tan_fovy,
+                                         const Tensor& dL_dout_color, const Tensor& campos, const Tensor& geomBuffer,
+                                         int64_t capacity, const Tensor& binningBuffer, const Tensor& imageBuffer,
+                                         double lambda_sh_sparsity, bool debug, bool absgrad)
 {
     need_params();
+    if (absgrad) {
+        need(api.r3dgs_backward_params_absgrad, "absolute-gradient entry points (r3dgs_backward_absgrad)");
+        need(api.r3dgs_absgrad_workspace_floats, "absolute-gradient entry points (r3dgs_backward_absgrad)");
+    }
     const ParamPtrs p = check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees);
     const c10::Device dev = xyz.device();
     const int P = p.P, M = p.M;
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    if (P == 0) return zero_grads(f32, {{0, 3}, {0, 1}, {0, 3}, {0, 1, 3}, {0, M - 1, 3}, {0, 3}, {0, 4}});
+    if (P == 0) {
+        std::vector<Tensor> z = zero_grads(f32, {{0, 3}, {0, 1}, {0, 3}, {0, 1, 3}, {0, M - 1, 3}, {0, 3}, {0, 4}});
+        if (absgrad) z.push_back(at::zeros({0, 3}, f32));
+        return z;
+    }
     Tensor dL_dmeans3D = at::empty({P, 3}, f32), dL_dmeans2D = at::empty({P, 3}, f32), dL_dopacity = at::empty({P, 1}, f32);
     Tensor dL_ddc = at::empty({P, 1, 3}, f32), dL_drest = at::empty({P, M - 1, 3}, f32);
     Tensor dL_dscaling = at::empty({P, 3}, f32), dL_drotation = at::empty({P, 4}, f32);
@@ -444,17 +491,43 @@ std::vector<Tensor> backward_params(const Tensor& background, const Tensor& xyz,
     const Tensor bg = dev_f32(background, dev), vm = dev_f32(viewmatrix, dev), pm = dev_f32(projmatrix, dev);
     const Tensor cp = dev_f32(campos, dev), g = dev_f32(dL_dout_color, dev), deg = dev_i32(degrees, dev), rad = dev_i32(radii, dev);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int st = api.r3dgs_backward_params(
-        P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest, p.scaling, (float)scale_modifier,
-        p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy,
-        opt_ptr<int>(rad), blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g),
-        dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), scratch.data_ptr<float>(),
-        dL_dmeans3D.data_ptr<float>(), scratch.data_ptr<float>() + 3 * (size_t)P, dL_ddc.data_ptr<float>(),
-        M > 1 ? dL_drest.data_ptr<float>() : nullptr, dL_dscaling.data_ptr<float>(), dL_drotation.data_ptr<float>(),
-        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev));
+    Tensor dL_abs, abs_ws;
+    if (absgrad) {
+        dL_abs = at::empty({P, 3}, f32);
+        abs_ws = at::empty({(int64_t)api.r3dgs_absgrad_workspace_floats((int)capacity)}, f32);
+    }
+#define R3_BACKWARD_ARGS                                                                                                      \
+    P, opt_ptr<int>(deg), M, (int)capacity, opt_ptr<float>(bg), W, H, p.xyz, p.dc, p.rest, p.scaling, (float)scale_modifier,  \
+        p.rotation, opt_ptr<float>(vm), opt_ptr<float>(pm), opt_ptr<float>(cp), (float)tan_fovx, (float)tan_fovy,             \
+        opt_ptr<int>(rad), blob_ptr(geomBuffer), blob_ptr(binningBuffer), blob_ptr(imageBuffer), opt_ptr<float>(g),           \
+        dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), scratch.data_ptr<float>(),                     \
+        dL_dmeans3D.data_ptr<float>(), scratch.data_ptr<float>() + 3 * (size_t)P, dL_ddc.data_ptr<float>(),                   \
+        M > 1 ? dL_drest.data_ptr<float>() : nullptr, dL_dscaling.data_ptr<float>(), dL_drotation.data_ptr<float>(),          \
+        (float)lambda_sh_sparsity, debug ? 1 : 0, cur_stream(dev)
+    const int st = absgrad ? api.r3dgs_backward_params_absgrad(R3_BACKWARD_ARGS, dL_abs.data_ptr<float>(),
+                                                               abs_ws.data_ptr<float>(), (size_t)abs_ws.numel())
+                           : api.r3dgs_backward_params(R3_BACKWARD_ARGS);
+#undef R3_BACKWARD_ARGS
     if (st < 0) fail("rasterize_gaussian_params_backward");
-    return {dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation};
+    std::vector<Tensor> out{dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation};
+    if (absgrad) out.push_back(dL_abs);
+    return out;
 }
+
+#define R3_BACKWARD_PARAMS                                                                                                     \
+    const Tensor &background, const Tensor &xyz, const Tensor &radii, const Tensor &features_dc, const Tensor &features_rest,  \
+        const Tensor &degrees, const Tensor &opacity, const Tensor &scaling, const Tensor &rotation, double scale_modifier,    \
+        const Tensor &viewmatrix, const Tensor &projmatrix, double tan_fovx, double tan_fovy, const Tensor &dL_dout_color,     \
+        const Tensor &campos, const Tensor &geomBuffer, int64_t capacity, const Tensor &binningBuffer,                         \
+        const Tensor &imageBuffer, double lambda_sh_sparsity, bool debug
+#define R3_BACKWARD_PASS                                                                                                       \
+    background, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation, scale_modifier, viewmatrix,       \
+        projmatrix, tan_fovx, tan_fovy, dL_dout_color, campos, geomBuffer, capacity, binningBuffer, imageBuffer,               \
+        lambda_sh_sparsity, debug
+std::vector<Tensor> backward_params(R3_BACKWARD_PARAMS) { return backward_params_impl(R3_BACKWARD_PASS, false); }
+std::vector<Tensor> backward_params_absgrad(R3_BACKWARD_PARAMS) { return backward_params_impl(R3_BACKWARD_PASS, true); }
+#undef R3_BACKWARD_PARAMS
+#undef R3_BACKWARD_PASS
 
 // r3dgs_aux_maps over the three buffers a forward returned -> (depth, alpha, median_depth [1,H,W], T_check [H,W],
 // n_check int32 [H,W]); a map that was not asked for is an undefined tensor.  `capacity`: as backward's.
@@ -857,12 +930,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("entry_points", &entry_points);
     m.def("forward_reserved", &forward_reserved);
     m.def("backward", &backward);
+    m.def("backward_absgrad", &backward_absgrad);
     m.def("mark_visible", &mark_visible);
     m.def("aux_maps", &aux_maps);
     m.def("contribution_scores", &contribution_scores);
     m.def("forward_params", &forward_params);
     m.def("forward_params_reserved", &forward_params_reserved);
     m.def("backward_params", &backward_params);
+    m.def("backward_params_absgrad", &backward_params_absgrad);
     m.def("activate_params", &activate_params);
     m.def("quantised_codebook_grad", &quantised_codebook_grad);
     m.def("l1_ssim_forward", &l1_ssim_forward);

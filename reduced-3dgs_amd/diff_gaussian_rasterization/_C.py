@@ -94,6 +94,13 @@ _ABI = {
                                 _vp, _vp, _vp, _vp, _vp,                             # radii, the three blobs, dL_dpix
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,         # the nine gradients
                                 _f, _i, _vp]),
+        # absolute screen-space gradients: r3dgs_backward's parameters, then dL_dmean2D_abs, the workspace and its size
+        # (rows an older library may lack: _OPTIONAL_ROWS below)
+        "r3dgs_absgrad_workspace_floats": (_sz, [_i]),
+        "r3dgs_backward_absgrad": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,
+                                        _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _f, _i, _vp, _vp, _vp, _sz]),
         "r3dgs_export_binning": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_colour_variance_accumulate": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_profile_enable": (_i, [_i]),
@@ -163,6 +170,10 @@ _ABI = {
                                        _vp, _vp, _vp, _vp, _vp,                               # radii, the three blobs, dL_dpix
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,      # the ten gradients
                                        _f, _i, _vp]),
+        "r3dgs_backward_params_absgrad": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f,
+                                               _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _f, _i, _vp, _vp, _vp, _sz]),
         "r3dgs_activate_params": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     }),
     "quantised": (_NO_SUCH("quantised entry points"), {   # include/r3dgs_quantised.h
@@ -221,26 +232,51 @@ _ABI = {
 }
 
 
+# Rows that joined a group after libraries with that group were built: a library without them still has the group, and the calls
+# that want them say so (_need_rows).  {family: (sentence, names)}
+_OPTIONAL_ROWS = {
+    "absgrad": (_NO_SUCH("absolute-gradient entry points (r3dgs_backward_absgrad)"),
+                ("r3dgs_absgrad_workspace_floats", "r3dgs_backward_absgrad", "r3dgs_backward_params_absgrad")),
+}
+
+
 def _apply_abi(lib):
     """Sets restype / argtypes of every row on `lib` -> the set of groups it has.  An optional group is there when the library
-    exports all of its names; a name of the required group that is missing raises AttributeError."""
+    exports all of its names; a name of the required group that is missing raises AttributeError.  Names of _OPTIONAL_ROWS do
+    not count for either: the ones `lib` lacks are skipped."""
+    later = {name for _, names in _OPTIONAL_ROWS.values() for name in names}
     present = set()
     for group, (_, rows) in _ABI.items():
-        if group != "required" and not all(hasattr(lib, name) for name in rows):
+        if group != "required" and not all(hasattr(lib, name) for name in rows if name not in later):
             continue
         present.add(group)
         for name, (restype, argtypes) in rows.items():
+            if name in later and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
     return present
 
 
 _present = _apply_abi(_lib)
+# names of _OPTIONAL_ROWS the loaded library lacks
+_missing_rows = {name for _, names in _OPTIONAL_ROWS.values() for name in names if not hasattr(_lib, name)}
 
 
 def _need(group, error=RuntimeError):
     if group not in _present:
         raise error(_ABI[group][0].format(lib=_LIB_PATH))
+
+
+def _need_rows(family, error=RuntimeError):
+    sentence, names = _OPTIONAL_ROWS[family]
+    if any(name in _missing_rows for name in names):
+        raise error(sentence)
+
+
+def has_absgrad():
+    """Whether the loaded library has the absolute-gradient backward (r3dgs_backward_absgrad)."""
+    return not any(name in _missing_rows for name in _OPTIONAL_ROWS["absgrad"][1])
 
 
 LIBRARY_PATH = _LIB_PATH
@@ -258,7 +294,7 @@ if _binding_request != "ctypes":
     try:
         from . import _r3dgs_torch as _ext_loaded
         _rows = {name for group in _present for name in _ABI[group][1]}
-        _ext_loaded.bind({name: C.cast(getattr(_lib, name), _vp).value for name, _ in _ext_loaded.entry_points() if name in _rows})
+        _ext_loaded.bind({name: C.cast(getattr(_lib, name), _vp).value for name, _ in _ext_loaded.entry_points() if name in _rows and name not in _missing_rows})
         _ext = _ext_loaded
     except ImportError:
         if _binding_request == "torch":
@@ -760,19 +796,24 @@ def set_gradient_arena(fn):
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                  degrees, campos, geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity,
-                                 debug, _want_conic=False):
+                                 debug, _want_conic=False, _absgrad=False):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:224-305) -> (dL_dmeans2D[P,3], dL_dcolors[P,3],
-    dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])."""
+    dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4]).
+    _absgrad: + dL_dmeans2D_abs[P,3] as the LAST element (include/r3dgs_rasterizer.h r3dgs_backward_absgrad): the per-pixel
+    absolute values of what dL_dmeans2D sums, third column zero; the other outputs are the plain call's bit for bit."""
+    if _absgrad:
+        _need_rows("absgrad")
     dev = means3D.device
     P = int(means3D.size(0))
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
     opts = dict(dtype=torch.float32, device=dev)
     if P == 0:
-        return _zero_grads(dev, (0, 3), (0, 3), (0, 1), (0, 3), (0, 6), (0, M, 3), (0, 3), (0, 4))
+        return _zero_grads(dev, (0, 3), (0, 3), (0, 1), (0, 3), (0, 6), (0, M, 3), (0, 3), (0, 4)) + (
+            _zero_grads(dev, (0, 3)) if _absgrad else ())
     if _ext is not None and _grad_arena is None:
         cap = _pair_capacity(R, P, W, H, binningBuffer)
-        return tuple(_ext.backward(_t(background), means3D, _t(radii), _t(colors), _t(scales), _t(rotations),
+        return tuple((_ext.backward_absgrad if _absgrad else _ext.backward)(_t(background), means3D, _t(radii), _t(colors), _t(scales), _t(rotations),
                                    float(scale_modifier), _t(cov3D_precomp), _t(viewmatrix), _t(projmatrix), float(tan_fovx),
                                    float(tan_fovy), dL_dout_color, _t(sh), _t(degrees), _t(campos), geomBuffer, int(cap),
                                    binningBuffer, imageBuffer, float(lambda_sh_sparsity), bool(debug), bool(_want_conic)))
@@ -795,16 +836,30 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     g, shc = _dev(dL_dout_color, dev), _dev(sh, dev)
     deg, rad = _dev(degrees, dev, torch.int32), _dev(radii, dev, torch.int32)
     cap = _pair_capacity(R, P, W, H, binningBuffer)
+    abs_out, abs_tail = _absgrad_tail(_absgrad, P, cap, opts)
     with _on_device(dev):
-        st = _lib.r3dgs_backward(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sc),
-                                 float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp),
-                                 float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
-                                 _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
-                                 _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
-                                 _ptr(dL_drotations), float(lambda_sh_sparsity), int(bool(debug)), _stream())
+        st = (_lib.r3dgs_backward_absgrad if _absgrad else _lib.r3dgs_backward)(
+            P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sc),
+            float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp),
+            float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
+            _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
+            _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
+            _ptr(dL_drotations), float(lambda_sh_sparsity), int(bool(debug)), _stream(), *abs_tail)
     _check(st, "rasterize_gaussians_backward")
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    return out + (dL_dconic,) if _want_conic else out
+    out = out + (dL_dconic,) if _want_conic else out
+    return out + (abs_out,) if _absgrad else out
+
+
+def _absgrad_tail(absgrad, P, cap, opts):
+    """-> (dL_dmeans2D_abs or None, the three trailing arguments of the *_absgrad entry points or ()).  The workspace is the
+    call's own: its contents mean nothing before or after."""
+    if not absgrad:
+        return None, ()
+    out = torch.empty((P, 3), **opts)
+    n = int(_lib.r3dgs_absgrad_workspace_floats(int(cap)))
+    ws = torch.empty((n,), **opts)
+    return out, (out.data_ptr(), ws.data_ptr(), n)
 
 
 # ---- raster from the model's raw parameters (include/r3dgs_rasterizer.h r3dgs_*_params) ---------------------------------
@@ -893,21 +948,25 @@ def rasterize_gaussian_params(background, xyz, features_dc, features_rest, degre
 
 def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation,
                                        scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, campos,
-                                       geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug, _want_2d=False):
+                                       geomBuffer, R, binningBuffer, imageBuffer, lambda_sh_sparsity, debug, _want_2d=False,
+                                       _absgrad=False):
     """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dxyz[P,3], dL_dfeatures_dc[P,1,3], dL_dfeatures_rest[P,M-1,3],
     dL_dscaling[P,3], dL_drotation[P,4]): gradients of the tensors passed in (raw scaling / rotation included).
-    _want_2d: + (dL_dcolors[P,3], dL_dconic[P,2,2]), the per-Gaussian sums camera_backward reads (the ctypes marshalling)."""
+    _want_2d: + (dL_dcolors[P,3], dL_dconic[P,2,2]), the per-Gaussian sums camera_backward reads (the ctypes marshalling).
+    _absgrad: + dL_dmeans2D_abs[P,3] as the LAST element, as rasterize_gaussians_backward."""
     _need("params")
+    if _absgrad:
+        _need_rows("absgrad")
     P, M, dev = _check_params(xyz, features_dc, features_rest, opacity, scaling, rotation, degrees)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     opts = dict(dtype=torch.float32, device=dev)
     if P == 0:
         return _zero_grads(dev, (0, 3), (0, 1), (0, 3), (0, 1, 3), (0, M - 1, 3), (0, 3), (0, 4)) + (
-            _zero_grads(dev, (0, 3), (0, 2, 2)) if _want_2d else ())
+            _zero_grads(dev, (0, 3), (0, 2, 2)) if _want_2d else ()) + (_zero_grads(dev, (0, 3)) if _absgrad else ())
     rest = _NO_TENSOR if M == 1 else features_rest
     cap = _pair_capacity(R, P, W, H, binningBuffer)
     if _ext is not None and not _want_2d:
-        return tuple(_ext.backward_params(_t(background), xyz, _t(radii), features_dc, rest, degrees, opacity, scaling, rotation,
+        return tuple((_ext.backward_params_absgrad if _absgrad else _ext.backward_params)(_t(background), xyz, _t(radii), features_dc, rest, degrees, opacity, scaling, rotation,
                                           float(scale_modifier), _t(viewmatrix), _t(projmatrix), float(tan_fovx), float(tan_fovy),
                                           dL_dout_color, _t(campos), geomBuffer, int(cap), binningBuffer, imageBuffer,
                                           float(lambda_sh_sparsity), bool(debug)))
@@ -918,17 +977,20 @@ def rasterize_gaussian_params_backward(background, xyz, radii, features_dc, feat
     dL_dconic = e(P, 2, 2) if _want_2d else None
     bg, vm, pm, cp = (_dev(t, dev) for t in (background, viewmatrix, projmatrix, campos))
     g, deg, rad = _dev(dL_dout_color, dev), _dev(degrees, dev, torch.int32), _dev(radii, dev, torch.int32)
+    abs_out, abs_tail = _absgrad_tail(_absgrad, P, cap, opts)
     with _on_device(dev):
-        st = _lib.r3dgs_backward_params(P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest),
-                                        _ptr(scaling), float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp),
-                                        float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
-                                        _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
-                                        scratch.data_ptr(), _ptr(dL_dmeans3D), scratch.data_ptr() + 12 * P, _ptr(dL_ddc),
-                                        _ptr(dL_drest), _ptr(dL_dscaling), _ptr(dL_drotation), float(lambda_sh_sparsity),
-                                        int(bool(debug)), _stream())
+        st = (_lib.r3dgs_backward_params_absgrad if _absgrad else _lib.r3dgs_backward_params)(
+            P, _ptr(deg), M, int(cap), _ptr(bg), W, H, _ptr(xyz), _ptr(features_dc), _ptr(rest),
+            _ptr(scaling), float(scale_modifier), _ptr(rotation), _ptr(vm), _ptr(pm), _ptr(cp),
+            float(tan_fovx), float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer),
+            _ptr(imageBuffer), _ptr(g), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
+            scratch.data_ptr(), _ptr(dL_dmeans3D), scratch.data_ptr() + 12 * P, _ptr(dL_ddc),
+            _ptr(dL_drest), _ptr(dL_dscaling), _ptr(dL_drotation), float(lambda_sh_sparsity),
+            int(bool(debug)), _stream(), *abs_tail)
     _check(st, "rasterize_gaussian_params_backward")
     out = (dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_ddc, dL_drest, dL_dscaling, dL_drotation)
-    return out + (scratch.view(-1)[:3 * P].view(P, 3), dL_dconic) if _want_2d else out
+    out = out + (scratch.view(-1)[:3 * P].view(P, 3), dL_dconic) if _want_2d else out
+    return out + (abs_out,) if _absgrad else out
 
 
 def activate_params(scaling, rotation):

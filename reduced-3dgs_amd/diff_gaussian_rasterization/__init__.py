@@ -16,6 +16,10 @@ checkout over.  Behavioural notes:
   * gradients are bit-reproducible: the backward has no float atomics (the reference issues one per
     (pixel, Gaussian, component), so its low bits depend on scheduling).
 """
+import contextlib
+import functools
+import threading
+import weakref
 from typing import NamedTuple
 
 import torch
@@ -56,6 +60,62 @@ def _call_native(fn, args, debug, dump_name):
         raise
 
 
+# ---- absolute screen-space gradients (AbsGS; gsplat's absgrad): see absgrad() -----------------------------------------------
+# The request travels beside the autograd functions' inputs and the public signatures (which are the reference's): a scope
+# (absgrad()) or a one-shot note (rasterize_gaussians(..., absgrad=True)), taken by the forwards issued on the same thread.
+class _AbsgradRequest(threading.local):
+    on = scope = False   # per thread; the class attributes are what a thread that never asked reads
+
+
+_absgrad_request = _AbsgradRequest()
+
+
+@contextlib.contextmanager
+def absgrad(on=True):
+    """Renders issued inside `with absgrad():` -- GaussianRasterizer(...)(...), rasterize_gaussians, rasterize_gaussian_params,
+    on this thread -- also return the absolute screen-space gradients: after backward(), the `means2D` tensor passed to the
+    render carries `means2D.absgrad`, a detached float32 [P,3] tensor: per Gaussian the sum over its pixels of the ABSOLUTE
+    value of what each pixel adds to means2D.grad (include/r3dgs_rasterizer.h r3dgs_backward_absgrad), third column zero (the
+    gsplat convention).  It is OVERWRITTEN, not accumulated, by each backward of that render.  Every other result of the render
+    and of its backward is what it is outside the scope, bit for bit.  A render that needs no gradient asks for nothing."""
+    before = _absgrad_request.scope
+    _absgrad_request.scope = bool(on)
+    try:
+        yield
+    finally:
+        _absgrad_request.scope = before
+
+
+def _ask_absgrad(on):
+    _absgrad_request.on = bool(on)
+
+
+def _take_absgrad(ctx, means2D):
+    """In a forward: whether the render asked for the abs gradients -> ctx.absgrad_target (a weak reference to the caller's
+    means2D tensor, or None).  Nothing is asked of a render that needs no gradient."""
+    req = _absgrad_request
+    if not (req.on or req.scope):   # the usual case: one attribute set
+        ctx.absgrad_target = None
+        return
+    req.on = False   # the one-shot note is taken
+    ctx.absgrad_target = weakref.ref(means2D) if any(ctx.needs_input_grad) else None
+
+
+def _abs_native(ctx, native):
+    return functools.partial(native, _absgrad=True) if ctx.absgrad_target is not None else native
+
+
+def _split_absgrad(ctx, out):
+    """A native backward's result without its trailing dL_dmeans2D_abs, which becomes `.absgrad` of the render's means2D."""
+    out = tuple(out)
+    if ctx.absgrad_target is None:
+        return out
+    target = ctx.absgrad_target()
+    if target is not None:
+        target.absgrad = out[-1]
+    return out[:-1]
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Autograd boundary of the tile rasterizer.  Inputs (positional, as the reference):
     means3D, means2D, sh, degrees, colors_precomp, opacities (raw), scales (activated), rotations (unit),
@@ -69,6 +129,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, degrees,
                 rs.campos, rs.prefiltered, rs.debug)
         _C.hint_next_forward(any(ctx.needs_input_grad))   # rendering under no_grad: nothing is kept for a backward's sake
+        _take_absgrad(ctx, means2D)
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_native(
             _C.rasterize_gaussians, args, rs.debug, "snapshot_fw.dump")
         ctx.raster_settings = rs
@@ -92,14 +153,20 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, degrees, rs.campos,
                 geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_native(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump")
+         grad_rotations) = (_call_native(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump")
+                            if ctx.absgrad_target is None else
+                            _split_absgrad(ctx, _call_native(_abs_native(ctx, _C.rasterize_gaussians_backward), args, rs.debug,
+                                                             "snapshot_bw.dump")))
         # one slot per forward input; None for degrees, raster_settings, lambda_sh_sparsity
         return (grad_means3D, grad_means2D, grad_sh, None, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, degrees, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, lambda_sh_sparsity):
+                        raster_settings, lambda_sh_sparsity, absgrad=False):
+    """absgrad=True: this render as inside `with absgrad():` -- after backward(), `means2D.absgrad` holds its absolute
+    screen-space gradients (float32 [P,3], detached, third column zero; overwritten, not accumulated, by each backward of it)."""
+    _ask_absgrad(absgrad)
     return _RasterizeGaussians.apply(means3D, means2D, sh, degrees, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, lambda_sh_sparsity)
 
@@ -117,6 +184,7 @@ class _RasterizeGaussianParams(torch.autograd.Function):
         args = (rs.bg, xyz, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.campos, rs.prefiltered, rs.debug)
         _C.hint_next_forward(any(ctx.needs_input_grad))
+        _take_absgrad(ctx, means2D)
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_native(
             _C.rasterize_gaussian_params, args, rs.debug, "snapshot_fw.dump")
         ctx.raster_settings = rs
@@ -138,8 +206,11 @@ class _RasterizeGaussianParams(torch.autograd.Function):
         args = (rs.bg, xyz, radii, features_dc, features_rest, degrees, opacity, scaling, rotation, rs.scale_modifier,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.campos, geomBuffer,
                 ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
-        (grad_means2D, grad_opacity, grad_xyz, grad_dc, grad_rest, grad_scaling, grad_rotation) = _call_native(
-            _C.rasterize_gaussian_params_backward, args, rs.debug, "snapshot_bw.dump")
+        (grad_means2D, grad_opacity, grad_xyz, grad_dc, grad_rest, grad_scaling, grad_rotation) = (
+            _call_native(_C.rasterize_gaussian_params_backward, args, rs.debug, "snapshot_bw.dump")
+            if ctx.absgrad_target is None else
+            _split_absgrad(ctx, _call_native(_abs_native(ctx, _C.rasterize_gaussian_params_backward), args, rs.debug,
+                                             "snapshot_bw.dump")))
         if features_rest.numel() == 0:
             grad_rest = None
         # one slot per forward input; None for degrees, raster_settings, lambda_sh_sparsity
@@ -149,7 +220,7 @@ class _RasterizeGaussianParams(torch.autograd.Function):
 def rasterize_gaussian_params(xyz, means2D, features_dc, features_rest, degrees, opacity, scaling, rotation, raster_settings,
                               lambda_sh_sparsity=0.):
     """The rasterizer from GaussianModel's raw tensors (_xyz, _features_dc, _features_rest, _degrees, _opacity, _scaling,
-    _rotation) -> (color, radii); gradients flow to exactly those tensors."""
+    _rotation) -> (color, radii); gradients flow to exactly those tensors.  (Inside `with absgrad():` as GaussianRasterizer.)"""
     if features_rest is None:
         features_rest = torch.Tensor([])
     rs = raster_settings
@@ -183,10 +254,11 @@ def _cam_settings(raster_settings, model_device, viewmatrix, projmatrix, campos)
                                     campos=campos.detach().contiguous())
 
 
-def _cam_forward(ctx, native, args, rs, lambda_sh_sparsity, saved):
+def _cam_forward(ctx, native, args, rs, lambda_sh_sparsity, saved, means2D):
     """The forward body of both functions: the native call `native(*args)`, the context, `saved(radii, geomBuffer,
-    binningBuffer, imgBuffer)` -> the tensors to keep."""
+    binningBuffer, imgBuffer)` -> the tensors to keep.  means2D: the caller's tensor (where an abs gradient would go)."""
     _C.hint_next_forward(any(ctx.needs_input_grad))
+    _take_absgrad(ctx, means2D)
     num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_native(native, args, rs.debug, "snapshot_fw.dump")
     ctx.raster_settings, ctx.num_rendered, ctx.lambda_sh_sparsity = rs, num_rendered, lambda_sh_sparsity
     ctx.save_for_backward(*saved(radii, geomBuffer, binningBuffer, imgBuffer))
@@ -207,7 +279,7 @@ def _cam_backward(ctx, first_camera_slot, native, args, raw, **model):
     first_camera_slot .. + 2 of the function) -> (native's result, the three camera slots).  **model: camera_backward's
     model arguments."""
     rs = ctx.raster_settings
-    got = tuple(_call_native(native, args, rs.debug, "snapshot_bw.dump"))
+    got = _split_absgrad(ctx, _call_native(native, args, rs.debug, "snapshot_bw.dump"))
     needs = ctx.needs_input_grad[first_camera_slot:first_camera_slot + 3]
     want = tuple(n for n, need in zip(_C.CAMERA_GRADS, needs) if need)
     cam = {}
@@ -235,7 +307,7 @@ class _RasterizeGaussiansCam(torch.autograd.Function):
                 rs.campos, rs.prefiltered, rs.debug)
         return _cam_forward(ctx, _C.rasterize_gaussians, args, rs, lambda_sh_sparsity,
                             lambda radii, geom, binning, img: (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii,
-                                                               sh, geom, binning, img, degrees))
+                                                               sh, geom, binning, img, degrees), means2D)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
@@ -246,9 +318,13 @@ class _RasterizeGaussiansCam(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, _cam_upstream(rs, grad_out_color, means3D), sh, degrees,
                 rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
 
+        want_abs = ctx.absgrad_target is not None
+
         def native(*a):   # -> the eight gradients, then (dL_dcolors again, dL_dconic); an empty model has no conic rows
-            out = tuple(_C.rasterize_gaussians_backward(*a, _want_conic=True))
-            return out[:8] + (out[1], out[8] if len(out) == 9 else None)
+            out = tuple(_C.rasterize_gaussians_backward(*a, _want_conic=True, _absgrad=want_abs))
+            tail = out[-1:] if want_abs else ()   # dL_dmeans2D_abs stays last
+            out = out[:-1] if want_abs else out
+            return out[:8] + (out[1], out[8] if len(out) == 9 else None) + tail
         got, cam = _cam_backward(ctx, 11, native, args, False, means3D=means3D, degrees=degrees,
                                  sh=None if colors_precomp.numel() else sh, sh_rest=None, scales=scales, rotations=rotations,
                                  cov3D_precomp=cov3Ds_precomp, radii=radii, geomBuffer=geomBuffer)
@@ -270,7 +346,7 @@ class _RasterizeGaussianParamsCam(torch.autograd.Function):
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.campos, rs.prefiltered, rs.debug)
         return _cam_forward(ctx, _C.rasterize_gaussian_params, args, rs, lambda_sh_sparsity,
                             lambda radii, geom, binning, img: (xyz, features_dc, features_rest, degrees, opacity, scaling, rotation,
-                                                               radii, geom, binning, img))
+                                                               radii, geom, binning, img), means2D)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
@@ -281,7 +357,9 @@ class _RasterizeGaussianParamsCam(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, _cam_upstream(rs, grad_out_color, xyz), rs.campos, geomBuffer,
                 ctx.num_rendered, binningBuffer, imgBuffer, ctx.lambda_sh_sparsity, rs.debug)
         no_rest = features_rest.numel() == 0
-        got, cam = _cam_backward(ctx, 10, lambda *a: _C.rasterize_gaussian_params_backward(*a, _want_2d=True), args, True,
+        want_abs = ctx.absgrad_target is not None
+        got, cam = _cam_backward(ctx, 10, lambda *a: _C.rasterize_gaussian_params_backward(*a, _want_2d=True, _absgrad=want_abs),
+                                 args, True,
                                  means3D=xyz, degrees=degrees, sh=features_dc, sh_rest=None if no_rest else features_rest,
                                  scales=scaling, rotations=rotation, cov3D_precomp=None, radii=radii, geomBuffer=geomBuffer)
         grad_means2D, grad_opacity, grad_xyz, grad_dc, grad_rest, grad_scaling, grad_rotation = got[:7]
@@ -499,6 +577,8 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, degrees=None, colors_precomp=None, scales=None,
                 rotations=None, cov3D_precomp=None, lambda_sh_sparsity=0.):
+        """(The parameters are the reference's.  Called inside `with diff_gaussian_rasterization.absgrad():`, the backward of
+        this render also leaves `means2D.absgrad` on the means2D tensor passed in -- see absgrad().)"""
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         has_sr = scales is not None or rotations is not None

@@ -81,6 +81,17 @@ to r3dgs_normals.normal_consistency.  It combines with `aux`, `aux_grad`, `featu
 on every route; distortion=None / False (the default): the same dictionary, nothing new is launched.  Refused with a
 ValueError before anything is launched: a trainable QuantisedModel under grad mode, a camera that requires grad, a (near, far)
 that is neither (0, 0) nor 0 < near < far.
+
+Absolute screen-space gradients (AbsGS; gsplat's absgrad).  `absgrad=True`: after backward(), out["viewspace_points"].absgrad is a
+detached float32 [P,3] tensor -- per Gaussian, the sum over its pixels of the ABSOLUTE value of what each pixel adds to
+"viewspace_points".grad (columns 0 and 1; column 2 is zero, rows of culled Gaussians are zero).  It comes out of the backward
+blend itself (include/r3dgs_rasterizer.h r3dgs_backward_absgrad): every gradient, the image and the radii are what they are
+without the keyword, bit for bit.  It describes the COLOUR loss's backward only: `aux_grad`, `features_geom_grad`, `normals` and
+`distortion` add their terms to "viewspace_points".grad through autograd and nothing to .absgrad.  It is OVERWRITTEN, not
+accumulated, by each backward of this render.  Works on every route that has a backward (raw-parameter, activated, a camera
+that requires grad, a trainable QuantisedModel) and with `antialiasing` / `filter_3d`; under no_grad, or for a model that needs no
+gradient, it is a no-op.  r3dgs_train_stats.add_densification_stats_absgrad(pc, viewspace_points, radii) feeds it to the densifiers.
+absgrad=False (the default): nothing new is launched.
 """
 import functools
 import inspect
@@ -92,6 +103,7 @@ import torch
 from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps, aux_maps_with_grad,
                                          distortion_map, distortion_map_with_grad, feature_maps, feature_maps_with_grad,
                                          rasterize_gaussian_params)
+from diff_gaussian_rasterization import absgrad as absgrad_scope
 from r3dgs_quantised import QuantisedModel
 
 # render(aux_grad=True) asks the call it wraps for the tensors its forward was fed: a dictionary here, for the duration of that
@@ -423,6 +435,9 @@ def _model_normals(pc, pipe, rs, override_color, variable_sh_bands):
 
 @functools.wraps(_render)
 def render(*args, aux=None, **kwargs):
+    if kwargs.pop("absgrad", False):   # likewise: out["viewspace_points"].absgrad after backward (the module's docstring)
+        with absgrad_scope():   # every rasterizer forward this render issues asks for them
+            return render(*args, aux=aux, **kwargs)
     aux_grad = bool(kwargs.pop("aux_grad", False))   # keyword on top of `aux` (the module's docstring); default: today's maps
     features = kwargs.pop("features", None)          # likewise: the [P, C] tensor of the "features" map; default: no such key
     features_geom_grad = bool(kwargs.pop("features_geom_grad", False))

@@ -131,3 +131,13 @@ def add_densification_stats(pc, viewspace_point_tensor, radii):
             raise RuntimeError("add_densification_stats: viewspace_point_tensor has no .grad yet (call backward() first)")
         grad = grad.grad
     densification_stats(grad, radii, pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)
+
+
+def add_densification_stats_absgrad(pc, viewspace_point_tensor, radii):
+    """add_densification_stats with the AbsGS signal: the norm accumulated is that of viewspace_point_tensor.absgrad -- what
+    render(..., absgrad=True) leaves there after backward() -- through the same kernel (the tensor is [P,3] like .grad)."""
+    grad = getattr(viewspace_point_tensor, "absgrad", None)
+    if not isinstance(grad, torch.Tensor):
+        raise RuntimeError("add_densification_stats_absgrad: viewspace_point_tensor has no .absgrad (render with absgrad=True "
+                           "and call backward() first)")
+    densification_stats(grad, radii, pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)
