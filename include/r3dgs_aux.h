@@ -70,6 +70,24 @@ int r3dgs_aux_maps_backward(int P, int R, int width, int height, char* geom_buff
                             const float* dL_dmedian, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacity,
                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, char* workspace, void* stream);
 
+/* r3dgs_aux_maps_backward that also hands out the screen-space sums its per-Gaussian chain starts from, for the camera pass
+ * of the maps (r3dgs_camera.h r3dgs_camera_backward_maps, which reads them next to dL_dmeans2D).  Everything as above -- the
+ * same workspace, the six outputs the same bits -- plus two optional outputs:
+ *   dL_dconic [P,4]  A, B, unused (written 0), C: the gradient of the conic in the layout and units r3dgs_camera_backward
+ *                    reads, i.e. what the chain feeds to its covariance backward
+ *   dL_dz [P]        the gradient of the view depth z alone (what reaches means3D through the third row of viewmatrix)
+ * Rows of culled Gaussians, and of Gaussians that lost pairs to an overflowed reservation, are zero.  With both NULL the call
+ * IS r3dgs_aux_maps_backward.  With one of them asked for and dL_dmeans3D .. dL_dcov3D all NULL (a frozen model: a tracker
+ * that fits the camera alone) the call still walks, the chain behind the screen-space sums is skipped and of the model only
+ * radii is read: viewmatrix .. cov3D_precomp may be NULL. */
+int r3dgs_aux_maps_backward_screen(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
+                                   char* image_buffer, const float* viewmatrix, const float* projmatrix, float tan_fovx,
+                                   float tan_fovy, const float* means3D, const float* scales, float scale_modifier,
+                                   const float* rotations, const float* cov3D_precomp, const int* radii, const float* dL_ddepth,
+                                   const float* dL_dalpha, const float* dL_dmedian, float* dL_dmeans2D, float* dL_dmeans3D,
+                                   float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                   float* dL_dconic, float* dL_dz, char* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,36 @@ int r3dgs_camera_backward(int P, const int* D, int M, int width, int height, con
                           const float* dL_dmean2D, const float* dL_dconic, const float* dL_dcolor, float* dL_dviewmatrix,
                           float* dL_dprojmatrix, float* dL_dcampos, char* workspace, void* stream);
 
+/* The camera pass of the replay maps: dL/dviewmatrix and dL/dprojmatrix of a loss on the depth / alpha / median-depth maps
+ * (r3dgs_aux.h), the distortion map (r3dgs_distortion.h) or a feature map (r3dgs_features.h), from the per-Gaussian
+ * screen-space sums the map's _screen backward has just written (r3dgs_aux_maps_backward_screen,
+ * r3dgs_distortion_backward_screen, r3dgs_feature_maps_backward_screen).  Conventions, layouts and the partial-derivative
+ * reading of the outputs as r3dgs_camera_backward; per Gaussian with radii > 0 and mt = [m, 1]:
+ *   projmatrix  from dL_dmean2D, as above;
+ *   viewmatrix  from dL_dconic through J(t) and Rw, as above (the clamp masks are taken again in fp32 as the forward took
+ *               them: the geometry blob is not read), and -- the one path a colour image does not have -- from dL_dz: the maps
+ *               read the view depth z = (mt V)_2 itself, so dL_dviewmatrix[4 k + 2] += dL_dz * mt[k];
+ *   there is no campos output: no SH direction is involved.  tan_fovx / tan_fovy are not differentiated.
+ *   means3D [P,3]; scales [P,3] / rotations [P,4] ACTIVATED, or cov3D_precomp [P,6] (the two may then be NULL);
+ *   viewmatrix, projmatrix [16], tan_fovx, tan_fovy, width, height, scale_modifier: the forward's; radii [P] as it returned them.
+ *   dL_dmean2D [P,3] (x, y; the third component takes no part), dL_dconic [P,4] (A, B, -, C), dL_dz [P]: any of them NULL = zero.
+ *   dL_dviewmatrix [16], dL_dprojmatrix [16]: either may be NULL (not written).  OVERWRITTEN, every element, column 3 of the
+ *     first and column 2 of the second with zeros.
+ *   workspace: r3dgs_camera_backward_maps_workspace_bytes(P) bytes of device memory, contents irrelevant before and after.
+ * Two launches on `stream`: a kernel of its own over the Gaussians (one lane per Gaussian per trip, radii loaded first and
+ * everything else only where radii > 0, 24 double sums per lane, the wave / workgroup reduction of r3dgs_camera_backward in
+ * its fixed order, one row per workgroup into the workspace) and r3dgs_camera_backward's one-workgroup finish.  No SH loads,
+ * no atomics, no host wait, no allocation: the same inputs give the same bits, and the call can be captured in a graph (query
+ * the workspace size outside the capture).  The chain runs in double or in fp32 as r3dgs_set_f64_chain says.
+ * P == 0, or all three gradient inputs NULL: the outputs are zero-filled and nothing is read.  Each map runs its own pass and
+ * the caller adds the shares (autograd does): the pass is linear in its three gradient inputs. */
+size_t r3dgs_camera_backward_maps_workspace_bytes(int P);
+int r3dgs_camera_backward_maps(int P, int width, int height, const float* means3D, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                               const float* projmatrix, float tan_fovx, float tan_fovy, const int* radii,
+                               const float* dL_dmean2D, const float* dL_dconic, const float* dL_dz, float* dL_dviewmatrix,
+                               float* dL_dprojmatrix, char* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

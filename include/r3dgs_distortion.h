@@ -72,6 +72,22 @@ int r3dgs_distortion_map_backward(int P, int R, int width, int height, char* geo
                                   float* dL_dmeans3D, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                                   float* dL_dcov3D, char* workspace, void* stream);
 
+/* r3dgs_distortion_map_backward that also hands out the screen-space sums its per-Gaussian chain starts from, for the camera
+ * pass of the maps (r3dgs_camera.h r3dgs_camera_backward_maps).  Everything as above -- the same workspace, the six outputs
+ * the same bits -- plus two optional outputs, as r3dgs_aux_maps_backward_screen has them:
+ *   dL_dconic [P,4]  A, B, unused (written 0), C, in the layout and units r3dgs_camera_backward reads
+ *   dL_dz [P]        the gradient of the view depth z alone: for 0 < near < far AFTER dm / dz of the mapping
+ * Zero rows for culled Gaussians and for those that lost pairs.  Both NULL: the call IS r3dgs_distortion_map_backward.  One of
+ * them asked for and dL_dmeans3D .. dL_dcov3D all NULL (a frozen model): the call still walks, the chain behind the
+ * screen-space sums is skipped and viewmatrix .. cov3D_precomp may be NULL (radii and saved_moments may not). */
+int r3dgs_distortion_backward_screen(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
+                                     char* image_buffer, float near, float far, const float* viewmatrix, const float* projmatrix,
+                                     float tan_fovx, float tan_fovy, const float* means3D, const float* scales,
+                                     float scale_modifier, const float* rotations, const float* cov3D_precomp, const int* radii,
+                                     const float* dL_ddistortion, const float* saved_moments, float* dL_dmeans2D,
+                                     float* dL_dmeans3D, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
+                                     float* dL_dcov3D, float* dL_dconic, float* dL_dz, char* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,99 @@ __global__ __launch_bounds__(64) void aux_bwd_gauss_kernel(const AuxGaussArgs a)
     gauss_grad_store(a, i, o);
 }
 
+// The per-Gaussian kernel of the _screen entry points (r3dgs_aux_maps_backward_screen, r3dgs_distortion_backward_screen,
+// r3dgs_feature_maps_backward_screen): aux_bwd_gauss_kernel written out once more -- the same sums in the same order, the
+// same chain -- with the two screen-space outputs stored beside the six, over a slab of `rows_per_slot` 32-byte rows per list
+// slot (4 for the aux and distortion slabs, 4 * groups for the feature maps' geometric slab, whose seventh float is 0: its
+// dL_dz is zero).  A kernel of its own, so that the kernels above keep their arguments and their bits.
+// MODEL = false: a frozen model -- none of dL_dmeans3D .. dL_dcov3D is asked for, the chain behind the screen-space sums is
+// not run and of the model only radii is read (the other model pointers may be NULL).
+struct ScreenGaussArgs : AuxGaussArgs {
+    uint32_t rows_per_slot;
+    float *dL_dconic, *dL_dz;
+};
+
+template <bool F64, bool MODEL>
+__global__ __launch_bounds__(64) void screen_gauss_kernel(const ScreenGaussArgs a)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= a.P) return;
+    AuxGaussGrad o;
+    gauss_grad_clear(o);
+    AuxScreenGrad sg = {{0.f, 0.f, 0.f}, 0.f};
+    if (global_ptr(a.radii)[i] > 0) {
+        const uint32_t lo = run_begin(a.keys, a.R, i);
+        double sums[kAuxSums];
+        for (int k = 0; k < kAuxSums; k++) sums[k] = 0.0;
+        uint32_t j = lo;
+        for (; j < a.R && global_ptr(a.keys)[j] == i; j++) {   // the run, counted as it is summed
+            const uint32_t slot = global_ptr(a.slots)[j];
+            if (slot >= a.R) continue;
+            const auto* rows = reinterpret_cast<const R3_GLOBAL float4*>(global_ptr(a.slab)) + (size_t)slot * a.rows_per_slot * 2;
+            for (uint32_t q = 0; q < a.rows_per_slot; q++) {
+                const float4 r0 = rows[2 * q], r1 = rows[2 * q + 1];
+                sums[0] += (double)r0.x;
+                sums[1] += (double)r0.y;
+                sums[2] += (double)r0.z;
+                sums[3] += (double)r0.w;
+                sums[4] += (double)r1.x;
+                sums[5] += (double)r1.y;
+                sums[6] += (double)r1.z;
+            }
+        }
+        // lost pairs to an overflowed reservation: zero sums, as in aux_bwd_gauss_kernel
+        if (j - lo != global_ptr(a.tiles)[i])
+            for (int k = 0; k < kAuxSums; k++) sums[k] = 0.0;
+        Camera cam;
+        for (int k = 0; k < 16; k++) {
+            cam.view[k] = MODEL ? global_ptr(a.view)[k] : 0.f;
+            cam.proj[k] = MODEL ? global_ptr(a.proj)[k] : 0.f;
+        }
+        cam.campos[0] = cam.campos[1] = cam.campos[2] = 0.f;   // (no term of this chain looks at it)
+        cam.tan_fovx = a.tan_fovx;
+        cam.tan_fovy = a.tan_fovy;
+        cam.focal_y = a.H / (2.0f * a.tan_fovy);
+        cam.focal_x = a.W / (2.0f * a.tan_fovx);
+        cam.W = a.W;
+        cam.H = a.H;
+        cam.gx = (a.W + kTile - 1) / kTile;
+        cam.gy = (a.H + kTile - 1) / kTile;
+        cam.scale_modifier = a.scale_modifier;
+        const GRec r = global_ptr(a.rec)[i];
+        const float rec6[6] = {r.x, r.y, r.cA, r.cB, r.cC, r.op};
+        float m3[3] = {0.f, 0.f, 1.f}, sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c6[6];
+        bool precomp = false;
+        if (MODEL) {
+            precomp = a.cov3D_precomp != nullptr;
+            for (int k = 0; k < 3; k++) m3[k] = global_ptr(a.means3D)[3 * (size_t)i + k];
+            if (precomp) {
+                for (int k = 0; k < 6; k++) c6[k] = global_ptr(a.cov3D_precomp)[6 * (size_t)i + k];
+            } else {
+                for (int k = 0; k < 3; k++) sc[k] = global_ptr(a.scales)[3 * (size_t)i + k];
+                for (int k = 0; k < 4; k++) q[k] = global_ptr(a.rotations)[4 * (size_t)i + k];
+            }
+        }
+        // (MODEL = false: everything of the chain behind the screen-space gradients is unread and the compiler drops it)
+        aux_bwd_chain<F64>(cam, rec6, sums, m3, sc, q, precomp ? c6 : nullptr, o, &sg);
+    }
+    if (MODEL) {
+        gauss_grad_store(a, i, o);
+    } else if (a.dL_dmeans2D) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dmeans2D) + 3 * (size_t)i;
+        d[0] = o.mean2D[0];
+        d[1] = o.mean2D[1];
+        d[2] = 0.f;
+    }
+    if (a.dL_dconic) {
+        R3_GLOBAL float* d = global_ptr(a.dL_dconic) + 4 * (size_t)i;
+        d[0] = sg.conic[0];
+        d[1] = sg.conic[1];
+        d[2] = 0.f;
+        d[3] = sg.conic[2];
+    }
+    if (a.dL_dz) global_ptr(a.dL_dz)[i] = sg.z;
+}
+
 // the workspace: the slab, then the sort's arrays and temp storage
 struct AuxBwdWork {
     float* slab;
@@ -211,14 +304,41 @@ void aux_bwd_zero_outputs(int P, const AuxBwdGeom& g, hipStream_t s)
     if (g.dL_dscales) R3_HIP(hipMemsetAsync(g.dL_dscales, 0, sizeof(float) * 3 * n, s));
     if (g.dL_drotations) R3_HIP(hipMemsetAsync(g.dL_drotations, 0, sizeof(float) * 4 * n, s));
     if (g.dL_dcov3D) R3_HIP(hipMemsetAsync(g.dL_dcov3D, 0, sizeof(float) * 6 * n, s));
+    if (g.dL_dconic) R3_HIP(hipMemsetAsync(g.dL_dconic, 0, sizeof(float) * 4 * n, s));
+    if (g.dL_dz) R3_HIP(hipMemsetAsync(g.dL_dz, 0, sizeof(float) * n, s));
 }
 
 void aux_bwd_check_geom(const char* what, const AuxBwdGeom& g)
 {
+    if (g.screen_output() && !g.model_output()) {   // a frozen model (a _screen call for the camera alone): only radii is read
+        if (!g.radii) throw Error(std::string(what) + ": radii must not be NULL");
+        return;
+    }
     if (!g.viewmatrix || !g.projmatrix || !g.means3D || !g.radii)
         throw Error(std::string(what) + ": viewmatrix, projmatrix, means3D and radii must not be NULL");
     if (!g.cov3D_precomp && (!g.scales || !g.rotations))
         throw Error(std::string(what) + ": need scales and rotations, or cov3D_precomp");
+}
+
+void launch_screen_gauss(const char* what, const PassStates& st, const PairSortWork& sort, int P, int R, int width, int height,
+                         const AuxBwdGeom& in, const float* slab, uint32_t rows_per_slot, hipStream_t s)
+{
+    ScreenGaussArgs g = gauss_args_of<ScreenGaussArgs>(st, sort, P, R, width, height, in);
+    g.slab = slab;
+    g.rows_per_slot = rows_per_slot;
+    g.dL_dconic = in.dL_dconic;
+    g.dL_dz = in.dL_dz;
+    const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
+    const bool f64 = g_f64_chain.get() != 0;
+    if (in.model_output()) {
+        if (f64)
+            hipLaunchKernelGGL((screen_gauss_kernel<true, true>), dim3(gblocks), dim3(64), 0, s, g);
+        else
+            hipLaunchKernelGGL((screen_gauss_kernel<false, true>), dim3(gblocks), dim3(64), 0, s, g);
+    } else {   // (no double chain to select: the kernel stops at the screen-space sums)
+        hipLaunchKernelGGL((screen_gauss_kernel<false, false>), dim3(gblocks), dim3(64), 0, s, g);
+    }
+    check_launch((std::string(what) + ", per-Gaussian chain with screen-space outputs").c_str(), s, false);
 }
 
 void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int height, const AuxBwdGeom& in, char* workspace,
@@ -226,6 +346,10 @@ void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int hei
 {
     const AuxBwdWork w = AuxBwdWork::carve(workspace, (size_t)R, pair_sort_temp_bytes((size_t)R));
     launch_pair_sort("aux maps backward", st, P, R, w.sort, s);
+    if (in.screen_output()) {
+        launch_screen_gauss("aux maps backward", st, w.sort, P, R, width, height, in, w.slab, kAuxQuads, s);
+        return;
+    }
     AuxGaussArgs g = gauss_args_of<AuxGaussArgs>(st, w.sort, P, R, width, height, in);
     g.slab = w.slab;
     const uint32_t gblocks = ((uint32_t)P + 63u) / 64u;
@@ -260,16 +384,33 @@ int r3dgs_aux_maps_backward(int P, int R, int width, int height, char* geom_buff
                             const float* dL_dmedian, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacity,
                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, char* workspace, void* stream)
 {
+    return r3dgs_aux_maps_backward_screen(P, R, width, height, geom_buffer, binning_buffer, image_buffer, viewmatrix, projmatrix,
+                                          tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii,
+                                          dL_ddepth, dL_dalpha, dL_dmedian, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales,
+                                          dL_drotations, dL_dcov3D, nullptr, nullptr, workspace, stream);
+}
+
+int r3dgs_aux_maps_backward_screen(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
+                                   char* image_buffer, const float* viewmatrix, const float* projmatrix, float tan_fovx,
+                                   float tan_fovy, const float* means3D, const float* scales, float scale_modifier,
+                                   const float* rotations, const float* cov3D_precomp, const int* radii, const float* dL_ddepth,
+                                   const float* dL_dalpha, const float* dL_dmedian, float* dL_dmeans2D, float* dL_dmeans3D,
+                                   float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                   float* dL_dconic, float* dL_dz, char* workspace, void* stream)
+{
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
+        // (without the two screen-space outputs this is r3dgs_aux_maps_backward itself, message for message)
+        const char* const what = dL_dconic || dL_dz ? "aux_maps_backward_screen" : "aux_maps_backward";
         const AuxBwdGeom geom = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
-                                 cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
+                                 cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
+                                 dL_dconic, dL_dz};
         const auto w = replay_bwd_open(
-            "aux_maps_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer},
+            what, P, R, width, height, {geom_buffer, binning_buffer, image_buffer},
             dL_ddepth || dL_dalpha || dL_dmedian, geom, nullptr, 0, workspace, s,
             [&](const char* what) { check_replay_dims(what, P, R, width, height); },
-            [&] { aux_bwd_check_geom("aux_maps_backward", geom); });
+            [&] { aux_bwd_check_geom(what, geom); });
         if (!w) return 0;
         const PassStates& st = w->st;
         const AuxBwdArgs a = {walk_args_of(st, w->grid, P, R, width, height), dL_ddepth, dL_dalpha, dL_dmedian,

@@ -69,7 +69,12 @@ struct AuxBwdGeom {
     const float *rotations, *cov3D_precomp;
     const int* radii;
     float *dL_dmeans2D, *dL_dmeans3D, *dL_dopacity, *dL_dscales, *dL_drotations, *dL_dcov3D;
-    bool any_output() const { return dL_dmeans2D || dL_dmeans3D || dL_dopacity || dL_dscales || dL_drotations || dL_dcov3D; }
+    // the _screen entry points' two: dL_dconic [P,4] (A, B, unused, C) and dL_dz [P], for a camera pass behind the call
+    float *dL_dconic = nullptr, *dL_dz = nullptr;
+    bool screen_output() const { return dL_dconic || dL_dz; }
+    // what the chain behind the screen-space sums is run for (dL_dmeans2D needs none of it)
+    bool model_output() const { return dL_dmeans3D || dL_dopacity || dL_dscales || dL_drotations || dL_dcov3D; }
+    bool any_output() const { return dL_dmeans2D || model_output() || screen_output(); }
 };
 
 // ---- the per-Gaussian kernels' shared ends --------------------------------------------------------------------------------
@@ -182,5 +187,11 @@ A gauss_args_of(const PassStates& st, const PairSortWork& sort, int P, int R, in
 // keys, sort, per-Gaussian sum and chain over a slab the pixel pass has been launched on, on the same stream
 void aux_bwd_second_stage(const PassStates& st, int P, int R, int width, int height, const AuxBwdGeom& g, char* workspace,
                           hipStream_t s);
+// The per-Gaussian sum and chain of a call that asks for g.dL_dconic / g.dL_dz (the _screen entry points), over sorted keys
+// and a slab of `rows_per_slot` 32-byte rows per list slot laid out as the aux slab's: the six outputs as the unit's own
+// per-Gaussian kernel writes them, bit for bit, and the two screen-space ones.  With no model output asked for
+// (!g.model_output()) the chain behind the screen-space sums is skipped and of the model only g.radii is read.
+void launch_screen_gauss(const char* what, const PassStates& st, const PairSortWork& sort, int P, int R, int width, int height,
+                         const AuxBwdGeom& g, const float* slab, uint32_t rows_per_slot, hipStream_t s);
 
 }  // namespace r3

@@ -161,9 +161,16 @@ struct AuxGaussGrad {
 // xform4x3 reads), cov3d_backward, opacity_backward.  F64: the _f64 forms, as preprocess_bwd selects them.
 // `rec6`: x, y, conic A, B, C and the activated opacity of the Gaussian's record.  cov3D_precomp != nullptr: the covariance
 // was given (scale / rot stay 0, cov6 is the result); otherwise scales / rotations are the activated values.
+// `screen` (optional): receives the screen-space gradients the chain starts from -- dL_dconic (A, B, C) as cov2d_backward is fed
+// it and dL/dz of the view depth alone -- for a camera pass behind this one (camera_math.h camera_maps_gaussian).
+struct AuxScreenGrad {
+    float conic[3];   // A, B, C
+    float z;
+};
+
 template <bool F64>
 R3_HD void aux_bwd_chain(const Camera& cam, const float* rec6, const double* sums, const float* mean3, const float* scales,
-                         const float* rotations, const float* cov3D_precomp, AuxGaussGrad& o)
+                         const float* rotations, const float* cov3D_precomp, AuxGaussGrad& o, AuxScreenGrad* screen = nullptr)
 {
     Splat sp;
     sp.x = rec6[0];
@@ -185,6 +192,12 @@ R3_HD void aux_bwd_chain(const Camera& cam, const float* rec6, const double* sum
     const SplatGrad g = splat_grad_of(scale_splat(sp), u);
     o.mean2D[0] = g.mx * (0.5f * (float)cam.W);   // backward.cu:498-499
     o.mean2D[1] = g.my * (0.5f * (float)cam.H);
+    if (screen) {
+        screen->conic[0] = g.cA;
+        screen->conic[1] = g.cB;
+        screen->conic[2] = g.cC;
+        screen->z = g.r;
+    }
     float c6[6], sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f};
     if (cov3D_precomp) {
         for (int k = 0; k < 6; k++) c6[k] = cov3D_precomp[k];

@@ -13,6 +13,10 @@
 //   2. camera_finish_kernel -- one workgroup: lane k adds sum k of the rows in index order and the three outputs are written
 //      whole, the structurally empty columns with zeros.
 // The grid is a function of P alone (cam_rows), and with it the order of every addition: the same inputs give the same bits.
+//
+// r3dgs_camera_backward_maps -- the same pass for a loss on the replay maps (depth / alpha / median depth, distortion, feature
+// maps) -- is camera_maps_kernel below: no colour, so no SH row, no blob and no campos; 24 sums (the view depth's own gradient
+// joins column 2 of dL/dV); the same reduction, the same grid, and camera_finish_kernel over rows whose last three sums are 0.
 #include <string>
 #include <type_traits>
 
@@ -163,11 +167,155 @@ __global__ __launch_bounds__(64) void camera_finish_kernel(const double* __restr
     if (tid < 3 && dL_dcampos) dL_dcampos[tid] = (float)s_sum[24 + tid];
 }
 
+// ---- the camera pass of the replay maps (r3dgs_camera_backward_maps; camera_math.h camera_maps_gaussian) ----------------
+// camera_grad_kernel without a colour: no SH row, no blob, no campos; three per-Gaussian gradient inputs, any of them nullptr
+// (zero).  24 double sums per lane, the same wave / workgroup reduction in the same order, and rows of kCamSums doubles -- the
+// last three zero -- so that camera_finish_kernel finishes both passes.
+struct CamMapsArgs {
+    int P, W, H;
+    const float* means3D;
+    const float* scales;
+    const float* rotations;
+    const float* cov3D_precomp;
+    const float* view;
+    const float* proj;
+    float tan_fovx, tan_fovy, scale_modifier;
+    const int* radii;
+    const float* dL_dmean2D;   // [P,3] or nullptr
+    const float* dL_dconic;    // [P,4] or nullptr
+    const float* dL_dz;        // [P] or nullptr
+    double* rows;              // [gridDim.x][kCamSums]
+};
+
+template <bool F64>
+__global__ __launch_bounds__(kCamBlock) void camera_maps_kernel(const CamMapsArgs a)
+{
+    __shared__ double s_part[kCamWaves][kCamMapSums];
+    using T = typename std::conditional<F64, double, float>::type;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t P = (size_t)a.P;
+    ViewParams vp;
+    vp.tan_fovx = a.tan_fovx;
+    vp.tan_fovy = a.tan_fovy;
+    vp.W = a.W;
+    vp.H = a.H;
+    vp.scale_modifier = a.scale_modifier;
+    // scalar loads (campos: the view matrix's first three words stand in -- nothing of this pass looks at it)
+    const Camera cam = load_camera_from(global_ptr(a.view), global_ptr(a.proj), global_ptr(a.view), vp);
+    const bool precomp = a.cov3D_precomp != nullptr;
+    const bool has_g2 = a.dL_dmean2D != nullptr, has_con = a.dL_dconic != nullptr, has_z = a.dL_dz != nullptr;   // wave-uniform
+
+    double acc[kCamMapSums];
+#pragma unroll
+    for (int k = 0; k < kCamMapSums; k++) acc[k] = 0.0;
+
+    for (size_t i = (size_t)blockIdx.x * kCamBlock + tid; i < P; i += (size_t)gridDim.x * kCamBlock) {
+        if (global_ptr(a.radii)[i] <= 0) continue;   // culled: none of its other loads
+        // every load of the Gaussian before the first use of any of them
+        float m3[3], sc[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, c6[6], g2[2] = {0.f, 0.f}, gcon[3] = {0.f, 0.f, 0.f};
+        float gz = 0.f;
+        for (int k = 0; k < 3; k++) m3[k] = global_ptr(a.means3D)[3 * i + k];
+        if (precomp) {
+            for (int k = 0; k < 6; k++) c6[k] = global_ptr(a.cov3D_precomp)[6 * i + k];
+        } else {
+            for (int k = 0; k < 3; k++) sc[k] = global_ptr(a.scales)[3 * i + k];
+            for (int k = 0; k < 4; k++) q[k] = global_ptr(a.rotations)[4 * i + k];
+        }
+        if (has_g2) {
+            g2[0] = global_ptr(a.dL_dmean2D)[3 * i];
+            g2[1] = global_ptr(a.dL_dmean2D)[3 * i + 1];
+        }
+        if (has_con) {
+            gcon[0] = global_ptr(a.dL_dconic)[4 * i];
+            gcon[1] = global_ptr(a.dL_dconic)[4 * i + 1];
+            gcon[2] = global_ptr(a.dL_dconic)[4 * i + 3];
+        }
+        if (has_z) gz = global_ptr(a.dL_dz)[i];
+        camera_maps_gaussian<T>(cam, m3, sc, q, precomp ? c6 : nullptr, g2, gcon, gz, acc);
+    }
+
+    // wave sums: lane L adds lane L + 32, 16, 8, 4, 2, 1 in this order
+#pragma unroll
+    for (int k = 0; k < kCamMapSums; k++) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) s_part[wave][k] = v;
+    }
+    __syncthreads();
+    if (tid < kCamSums) {
+        double v = 0.0;   // (sums 24 .. 26 of a row: campos, which this pass does not have)
+        if (tid < kCamMapSums) {
+            v = s_part[0][tid];
+#pragma unroll
+            for (int w = 1; w < kCamWaves; w++) v += s_part[w][tid];
+        }
+        global_ptr(a.rows)[(size_t)blockIdx.x * kCamSums + tid] = v;
+    }
+}
+
 }  // namespace
 
 }  // namespace r3
 
 extern "C" {
+
+size_t r3dgs_camera_backward_maps_workspace_bytes(int P) { return r3dgs_camera_backward_workspace_bytes(P); }
+
+int r3dgs_camera_backward_maps(int P, int width, int height, const float* means3D, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                               const float* projmatrix, float tan_fovx, float tan_fovy, const int* radii,
+                               const float* dL_dmean2D, const float* dL_dconic, const float* dL_dz, float* dL_dviewmatrix,
+                               float* dL_dprojmatrix, char* workspace, void* stream)
+{
+    return r3::guarded_call([&]() {
+        using namespace r3;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (P < 0 || width < 1 || height < 1)
+            throw Error("camera_backward_maps: need P >= 0 and width, height >= 1, got P = " + std::to_string(P) + ", " +
+                        std::to_string(width) + "x" + std::to_string(height));
+        if (!dL_dviewmatrix && !dL_dprojmatrix) return 0;
+        if (P == 0 || (!dL_dmean2D && !dL_dconic && !dL_dz)) {   // zeros, nothing is read
+            if (dL_dviewmatrix) R3_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), s));
+            if (dL_dprojmatrix) R3_HIP(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), s));
+            return 0;
+        }
+        if (!workspace) throw Error("camera_backward_maps: the workspace must not be NULL");
+        if (!means3D || !radii || !viewmatrix || !projmatrix)
+            throw Error("camera_backward_maps: means3D, radii, viewmatrix and projmatrix must not be NULL");
+        if (!cov3D_precomp && (!scales || !rotations))
+            throw Error("camera_backward_maps: need scales and rotations, or cov3D_precomp");
+        Carver c(workspace);
+        const int nrows = cam_rows(P);
+        CamMapsArgs a;
+        a.P = P;
+        a.W = width;
+        a.H = height;
+        a.means3D = means3D;
+        a.scales = scales;
+        a.rotations = rotations;
+        a.cov3D_precomp = cov3D_precomp;
+        a.view = viewmatrix;
+        a.proj = projmatrix;
+        a.tan_fovx = tan_fovx;
+        a.tan_fovy = tan_fovy;
+        a.scale_modifier = scale_modifier;
+        a.radii = radii;
+        a.dL_dmean2D = dL_dmean2D;
+        a.dL_dconic = dL_dconic;
+        a.dL_dz = dL_dz;
+        a.rows = c.take<double>((size_t)nrows * kCamSums);
+        if (g_f64_chain.get() != 0)
+            hipLaunchKernelGGL(camera_maps_kernel<true>, dim3(nrows), dim3(kCamBlock), 0, s, a);
+        else
+            hipLaunchKernelGGL(camera_maps_kernel<false>, dim3(nrows), dim3(kCamBlock), 0, s, a);
+        check_launch("camera backward of the maps, per-Gaussian pass", s, false);
+        hipLaunchKernelGGL(camera_finish_kernel, dim3(1), dim3(64), 0, s, a.rows, nrows, dL_dviewmatrix, dL_dprojmatrix,
+                           (float*)nullptr);
+        check_launch("camera backward of the maps, finish", s, false);
+        return 0;
+    });
+}
 
 size_t r3dgs_camera_backward_workspace_bytes(int P)
 {

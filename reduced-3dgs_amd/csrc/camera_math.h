@@ -175,4 +175,27 @@ R3_HD void camera_grad_gaussian(const Camera& cam, const float* m3, const float*
     }
 }
 
+// The camera pass of the replay maps (r3dgs_camera_backward_maps: depth / alpha / median depth, distortion, feature maps):
+// one VISIBLE Gaussian's share of the first kCamMapSums sums, from the screen-space sums a _screen map backward wrote.  The
+// mean and the conic go the way they go above; no colour, so nothing for campos; and the one path the colour image does not
+// have -- the maps read the view depth z = t_2 = sum_j V[4 j + 2] mt_j itself, so dL_dz goes to column 2 of V with the
+// factor mt_j.  sc, q: ACTIVATED scales / rotations (ignored when c6_precomp != nullptr).
+constexpr int kCamMapSums = 24;
+
+template <class T>
+R3_HD void camera_maps_gaussian(const Camera& cam, const float* m3, const float* sc, const float* q, const float* c6_precomp,
+                                const float* g2, const float* gcon, float gz, double* acc)
+{
+    float c6[6];
+    if (c6_precomp) {
+        for (int k = 0; k < 6; k++) c6[k] = c6_precomp[k];
+    } else {
+        cov3d_from_scale_rot(sc, cam.scale_modifier, q, c6);
+    }
+    camera_grad_proj<T>(cam.proj, m3, g2[0], g2[1], acc);
+    camera_grad_view<T>(cam, m3, c6, gcon[0], gcon[1], gcon[2], acc);
+    const T mt[4] = {(T)m3[0], (T)m3[1], (T)m3[2], (T)1};
+    for (int j = 0; j < 4; j++) acc[3 * j + 2] += (double)(mt[j] * (T)gz);
+}
+
 }  // namespace r3

@@ -250,17 +250,34 @@ int r3dgs_distortion_map_backward(int P, int R, int width, int height, char* geo
                                   float* dL_dmeans3D, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                                   float* dL_dcov3D, char* workspace, void* stream)
 {
+    return r3dgs_distortion_backward_screen(P, R, width, height, geom_buffer, binning_buffer, image_buffer, near, far, viewmatrix,
+                                            projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
+                                            cov3D_precomp, radii, dL_ddistortion, saved_moments, dL_dmeans2D, dL_dmeans3D,
+                                            dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, workspace, stream);
+}
+
+int r3dgs_distortion_backward_screen(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
+                                     char* image_buffer, float near, float far, const float* viewmatrix, const float* projmatrix,
+                                     float tan_fovx, float tan_fovy, const float* means3D, const float* scales,
+                                     float scale_modifier, const float* rotations, const float* cov3D_precomp, const int* radii,
+                                     const float* dL_ddistortion, const float* saved_moments, float* dL_dmeans2D,
+                                     float* dL_dmeans3D, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
+                                     float* dL_dcov3D, float* dL_dconic, float* dL_dz, char* workspace, void* stream)
+{
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
+        // (without the two screen-space outputs this is r3dgs_distortion_map_backward itself, message for message)
+        const std::string name = dL_dconic || dL_dz ? "distortion_backward_screen" : "distortion_map_backward";
         const AuxBwdGeom geom = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
-                                 cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
+                                 cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
+                                 dL_dconic, dL_dz};
         const auto w = replay_bwd_open(
-            "distortion_map_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_ddistortion != nullptr,
+            name.c_str(), P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_ddistortion != nullptr,
             geom, nullptr, 0, workspace, s, [&](const char* what) { check_call(what, P, R, width, height, near, far); },
             [&] {
-                if (!saved_moments) throw Error("distortion_map_backward: saved_moments must not be NULL");
-                aux_bwd_check_geom("distortion_map_backward", geom);
+                if (!saved_moments) throw Error(name + ": saved_moments must not be NULL");
+                aux_bwd_check_geom(name.c_str(), geom);
             });
         if (!w) return 0;
         const PassStates& st = w->st;

@@ -543,24 +543,43 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
                                 float* dL_dfeatures, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacity,
                                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, char* workspace, void* stream)
 {
+    return r3dgs_feature_maps_backward_screen(P, R, width, height, geom_buffer, binning_buffer, image_buffer, viewmatrix,
+                                              projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
+                                              cov3D_precomp, radii, features, C, dL_dout, dL_dfeatures, dL_dmeans2D, dL_dmeans3D,
+                                              dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, workspace, stream);
+}
+
+int r3dgs_feature_maps_backward_screen(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
+                                       char* image_buffer, const float* viewmatrix, const float* projmatrix, float tan_fovx,
+                                       float tan_fovy, const float* means3D, const float* scales, float scale_modifier,
+                                       const float* rotations, const float* cov3D_precomp, const int* radii,
+                                       const float* features, int C, const float* dL_dout, float* dL_dfeatures,
+                                       float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacity, float* dL_dscales,
+                                       float* dL_drotations, float* dL_dcov3D, float* dL_dconic, float* dL_dz, char* workspace,
+                                       void* stream)
+{
     return r3::guarded_call([&]() {
         using namespace r3;
         hipStream_t s = static_cast<hipStream_t>(stream);
+        // (without the two screen-space outputs this is r3dgs_feature_maps_backward itself, message for message)
+        const std::string name = dL_dconic || dL_dz ? "feature_maps_backward_screen" : "feature_maps_backward";
         const AuxBwdGeom in = {viewmatrix, projmatrix, tan_fovx, tan_fovy, means3D, scales, scale_modifier, rotations,
-                               cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
+                               cov3D_precomp, radii, dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
+                               dL_dconic, dL_dz};
         const bool geom = in.any_output();
         const bool feat = dL_dfeatures != nullptr;
         const auto walk = replay_bwd_open(
-            "feature_maps_backward", P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_dout != nullptr, in,
+            name.c_str(), P, R, width, height, {geom_buffer, binning_buffer, image_buffer}, dL_dout != nullptr, in,
             dL_dfeatures, (size_t)C, workspace, s, [&](const char* what) { check_dims(what, P, R, C, width, height); },
             [&] {
-                if (!radii) throw Error("feature_maps_backward: radii must not be NULL");
+                if (!radii) throw Error(name + ": radii must not be NULL");
                 if (!geom) return;   // a frozen geometry: none of its inputs is read
-                if (!features) throw Error("feature_maps_backward: the geometry gradients need features");
+                if (!features) throw Error(name + ": the geometry gradients need features");
+                if (in.screen_output() && !in.model_output()) return;   // a frozen model: the screen-space sums read no more
                 if (!viewmatrix || !projmatrix || !means3D)
-                    throw Error("feature_maps_backward: the geometry gradients need viewmatrix, projmatrix and means3D");
+                    throw Error(name + ": the geometry gradients need viewmatrix, projmatrix and means3D");
                 if (!cov3D_precomp && (!scales || !rotations))
-                    throw Error("feature_maps_backward: need scales and rotations, or cov3D_precomp");
+                    throw Error(name + ": need scales and rotations, or cov3D_precomp");
             });
         if (!walk) return 0;
         const PassStates& st = walk->st;
@@ -599,7 +618,9 @@ int r3dgs_feature_maps_backward(int P, int R, int width, int height, char* geom_
             hipLaunchKernelGGL(feat_bwd_feature_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, f);
             check_launch("feature maps backward, feature sums", s, false);
         }
-        if (geom) {
+        if (geom && in.screen_output()) {
+            launch_screen_gauss("feature maps backward", st, w.sort, P, R, width, height, in, w.slab_g, 4u * a.ngroups, s);
+        } else if (geom) {
             FeatGaussArgs g = gauss_args_of<FeatGaussArgs>(st, w.sort, P, R, width, height, in);
             g.slab_g = w.slab_g;
             g.ngroups = a.ngroups;

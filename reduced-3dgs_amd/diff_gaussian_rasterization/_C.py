@@ -112,17 +112,28 @@ _ABI = {
         "r3dgs_aux_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_aux_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # 3 upstream, 6 outputs
+        "r3dgs_aux_maps_backward_screen": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,   # 3 upstream, 6 outputs
+                                                _vp, _vp, _vp, _vp]),                          # dL_dconic, dL_dz
         # include/r3dgs_distortion.h
         "r3dgs_distortion_map": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
         "r3dgs_distortion_map_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_distortion_map_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp,
                                                _vp,                                             # .. radii
                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # upstream, moments, 6 outputs
+        "r3dgs_distortion_backward_screen": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp,
+                                                  _vp,                                             # .. radii
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,          # upstream, moments, 6 outputs
+                                                  _vp, _vp, _vp, _vp]),                            # dL_dconic, dL_dz
         # include/r3dgs_features.h
         "r3dgs_feature_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
         "r3dgs_feature_maps_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
         "r3dgs_feature_maps_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp, _vp,   # .. radii
                                              _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # features .. 7 outputs
+        "r3dgs_feature_maps_backward_screen": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _f, _vp, _vp,
+                                                    _vp,                                           # .. radii
+                                                    _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,   # features .. 7 outputs
+                                                    _vp, _vp, _vp, _vp]),                          # dL_dconic, dL_dz
         # include/r3dgs_importance.h
         "r3dgs_contribution_scores_workspace_bytes": (_sz, [_i, _i, _i, _i]),
         "r3dgs_contribution_scores": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -149,6 +160,9 @@ _ABI = {
         "r3dgs_camera_backward_workspace_bytes": (_sz, [_i]),
         "r3dgs_camera_backward": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _f, _f,   # .. tan_fovy
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),   # radii, blob, 3 sums, 3 outputs
+        "r3dgs_camera_backward_maps_workspace_bytes": (_sz, [_i]),
+        "r3dgs_camera_backward_maps": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _f, _vp,   # .. radii
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),                     # 3 sums, 2 outputs
         # include/r3dgs_reduction.h
         "r3dgs_min_pixel_size": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_sphere_ellipsoid_intersection": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1322,15 +1336,25 @@ AUX_GRADS = ("means2D", "means3D", "opacity", "scales", "rotations", "cov3D")
 _AUX_GRAD_COLS = dict(means2D=3, means3D=3, opacity=1, scales=3, rotations=4, cov3D=6)
 
 
+# the two screen-space outputs of the _screen entry points (what camera_backward_maps reads next to "means2D")
+SCREEN_GRADS = ("conic", "z")
+_SCREEN_GRAD_COLS = dict(conic=4, z=1)
+_AUX_GRAD_COLS.update(_SCREEN_GRAD_COLS)
+
+
 def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
                       scales, scale_modifier, rotations, cov3D_precomp, radii, dL_ddepth=None, dL_dalpha=None, dL_dmedian=None,
-                      want=AUX_GRADS):
+                      want=AUX_GRADS, _screen=False):
     """r3dgs_aux_maps_backward (include/r3dgs_aux.h): the gradients of the maps of `aux_maps` over the same three buffers.
     dL_ddepth / dL_dalpha / dL_dmedian: float tensors of H*W elements (any shape), None = zero.  scales / rotations are the
     ACTIVATED values (or cov3D_precomp is given and they are empty).  -> {name: float [P, cols]} for the names in `want` (a
     subset of AUX_GRADS); "opacity" is the gradient of the raw opacity, "means2D" what densification reads.  The buffers are
-    only read; the workspace is allocated here, per call, from torch's caching allocator."""
-    want = _subset("aux_maps_backward", "gradient", want, AUX_GRADS)
+    only read; the workspace is allocated here, per call, from torch's caching allocator.
+    _screen=True (`aux_maps_backward_screen`): r3dgs_aux_maps_backward_screen -- `want` may also name the SCREEN_GRADS "conic"
+    [P,4] (A, B, 0, C) and "z" [P,1], the screen-space sums camera_backward_maps reads next to "means2D"; with none of
+    "means3D" .. "cov3D" wanted the model is frozen and the chain behind those sums is skipped."""
+    names, native = _screen_variant(_screen, AUX_GRADS, "r3dgs_aux_maps_backward")
+    want = _subset("aux_maps_backward", "gradient", want, names)
     P, H, W, cap, dev = _replay_state("aux_maps_backward", "the state buffers and the model", P, R, H, W, geomBuffer,
                                       binningBuffer, imageBuffer, means3D)
     ups = []
@@ -1341,8 +1365,38 @@ def aux_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewma
         ups.append(g)
     return _map_backward("aux_maps_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
                          (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
-                         (lambda: _lib.r3dgs_aux_maps_backward_workspace_bytes(P, cap, W, H), _lib.r3dgs_aux_maps_backward),
-                         (), [_ptr(g) for g in ups], AUX_GRADS, _AUX_GRAD_COLS, want)
+                         (lambda: _lib.r3dgs_aux_maps_backward_workspace_bytes(P, cap, W, H), native),
+                         (), [_ptr(g) for g in ups], names, _AUX_GRAD_COLS, want)
+
+
+# a map backward and its _screen form, by the sibling's name
+_SCREEN_ENTRY = {"r3dgs_aux_maps_backward": "r3dgs_aux_maps_backward_screen",
+                 "r3dgs_distortion_map_backward": "r3dgs_distortion_backward_screen",
+                 "r3dgs_feature_maps_backward": "r3dgs_feature_maps_backward_screen"}
+
+
+def _screen_variant(screen, names, entry):
+    """(every output of the call in its order, the native call) of the map backward `entry` or of its _screen form."""
+    if not screen:
+        return names, getattr(_lib, entry)
+    return names + SCREEN_GRADS, getattr(_lib, _SCREEN_ENTRY[entry])
+
+
+def aux_maps_backward_screen(*args, **kwargs):
+    """r3dgs_aux_maps_backward_screen (include/r3dgs_aux.h): `aux_maps_backward` whose `want` may also name "conic" and "z"."""
+    return aux_maps_backward(*args, _screen=True, **kwargs)
+
+
+def distortion_backward_screen(*args, **kwargs):
+    """r3dgs_distortion_backward_screen (include/r3dgs_distortion.h): `distortion_map_backward` whose `want` may also name
+    "conic" and "z" (the latter behind dm / dz of the mapping)."""
+    return distortion_map_backward(*args, _screen=True, **kwargs)
+
+
+def feature_maps_backward_screen(*args, **kwargs):
+    """r3dgs_feature_maps_backward_screen (include/r3dgs_features.h): `feature_maps_backward` whose `want` may also name
+    "conic" and "z" (zeros: a feature map does not read the depth)."""
+    return feature_maps_backward(*args, _screen=True, **kwargs)
 
 
 def _map_backward(what, dev, P, cap, H, W, buffers, geometry, native, lead, trail, names, cols, want):
@@ -1398,13 +1452,15 @@ def distortion_map(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, near=0.0,
 
 def distortion_map_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
                             scales, scale_modifier, rotations, cov3D_precomp, radii, dL_ddistortion, moments, near=0.0, far=0.0,
-                            want=AUX_GRADS):
+                            want=AUX_GRADS, _screen=False):
     """r3dgs_distortion_map_backward (include/r3dgs_distortion.h): the gradients of the map of `distortion_map` over the same
     three buffers, from dL_ddistortion (float, H*W elements, any shape; None = zero) and the `moments` that call returned for
     the same (near, far).  Everything else as aux_maps_backward: activated scales / rotations or cov3D_precomp -> {name: float
-    [P, cols]} for the names in `want` (a subset of AUX_GRADS).  The workspace is allocated here, per call."""
+    [P, cols]} for the names in `want` (a subset of AUX_GRADS).  The workspace is allocated here, per call.  _screen=True: as
+    in aux_maps_backward."""
     near, far = depth_mapping((near, far))
-    want = _subset("distortion_map_backward", "gradient", want, AUX_GRADS)
+    names, native = _screen_variant(_screen, AUX_GRADS, "r3dgs_distortion_map_backward")
+    want = _subset("distortion_map_backward", "gradient", want, names)
     P, H, W, cap, dev = _replay_state("distortion_map_backward", "the state buffers and the model", P, R, H, W, geomBuffer,
                                       binningBuffer, imageBuffer, means3D)
     g, mom = _dev(dL_ddistortion, dev), _dev(moments, dev)
@@ -1414,8 +1470,8 @@ def distortion_map_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, 
         raise RuntimeError(f"distortion_map_backward: moments must have {2 * H * W} elements (distortion_map(want_moments=True))")
     return _map_backward("distortion_map_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
                          (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
-                         (lambda: _lib.r3dgs_distortion_map_backward_workspace_bytes(P, cap, W, H), _lib.r3dgs_distortion_map_backward),
-                         (near, far), (_ptr(g), _ptr(mom)), AUX_GRADS, _AUX_GRAD_COLS, want)
+                         (lambda: _lib.r3dgs_distortion_map_backward_workspace_bytes(P, cap, W, H), native),
+                         (near, far), (_ptr(g), _ptr(mom)), names, _AUX_GRAD_COLS, want)
 
 
 FEATURE_MAX_CHANNELS = 512   # R3DGS_FEATURE_MAX_CHANNELS (include/r3dgs_features.h)
@@ -1454,13 +1510,14 @@ def feature_maps(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, features):
 
 
 def feature_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, tanfovx, tanfovy, means3D,
-                          scales, scale_modifier, rotations, cov3D_precomp, radii, features, dL_dout, want=FEATURE_GRADS):
+                          scales, scale_modifier, rotations, cov3D_precomp, radii, features, dL_dout, want=FEATURE_GRADS, _screen=False):
     """r3dgs_feature_maps_backward (include/r3dgs_features.h): dL_dout (C*H*W elements, None = zero) -> {name: float [P, cols]}
     for the names in `want` (a subset of FEATURE_GRADS): "features" [P, C] and the geometry gradients of aux_maps_backward, in
     its units.  With only "features" wanted the geometry is frozen: the geometric sums and the per-Gaussian chain are skipped and
     viewmatrix .. cov3D_precomp may be None.  The buffers are only read; the workspace is allocated here, per call, from
-    torch's caching allocator."""
-    want = _subset("feature_maps_backward", "gradient", want, FEATURE_GRADS)
+    torch's caching allocator.  _screen=True: as in aux_maps_backward."""
+    names, native = _screen_variant(_screen, FEATURE_GRADS, "r3dgs_feature_maps_backward")
+    want = _subset("feature_maps_backward", "gradient", want, names)
     P, H, W, cap, dev = _replay_state("feature_maps_backward", "the state buffers and the features", P, R, H, W, geomBuffer,
                                       binningBuffer, imageBuffer, features)
     feats, C_ = _feature_tensor(features, P, dev, "feature_maps_backward")
@@ -1469,8 +1526,8 @@ def feature_maps_backward(P, R, H, W, geomBuffer, binningBuffer, imageBuffer, vi
         raise RuntimeError(f"feature_maps_backward: dL_dout has {g.numel()} elements, the map {C_ * H * W}")
     return _map_backward("feature_maps_backward", dev, P, cap, H, W, (geomBuffer, binningBuffer, imageBuffer),
                          (viewmatrix, projmatrix, tanfovx, tanfovy, means3D, scales, scale_modifier, rotations, cov3D_precomp, radii),
-                         (lambda: _lib.r3dgs_feature_maps_backward_workspace_bytes(P, cap, C_, W, H), _lib.r3dgs_feature_maps_backward),
-                         (), (_ptr(feats), C_, _ptr(g)), FEATURE_GRADS, dict(_AUX_GRAD_COLS, features=C_), want)
+                         (lambda: _lib.r3dgs_feature_maps_backward_workspace_bytes(P, cap, C_, W, H), native),
+                         (), (_ptr(feats), C_, _ptr(g)), names, dict(_AUX_GRAD_COLS, features=C_), want)
 
 
 SCORES = ("sum", "max", "count", "views")
@@ -1621,6 +1678,48 @@ def camera_backward(means3D, degrees, sh, sh_rest, scales, rotations, scale_modi
             P, _ptr(deg), M, W, H, _ptr(m3), _ptr(shc), _ptr(rest), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), int(raw),
             _ptr(vm), _ptr(pm), _ptr(cp), float(tanfovx), float(tanfovy), _ptr(rad), _ptr(geom), _ptr(g2), _ptr(gcon), _ptr(gcol),
             *[_ptr(out.get(name)) for name in CAMERA_GRADS], work.data_ptr(), _stream()), "camera_backward")
+    return out
+
+
+CAMERA_MAP_GRADS = ("viewmatrix", "projmatrix")
+
+
+def camera_backward_maps(means3D, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy,
+                         image_height, image_width, radii, dL_dmeans2D=None, dL_dconic=None, dL_dz=None, want=CAMERA_MAP_GRADS):
+    """r3dgs_camera_backward_maps (include/r3dgs_camera.h): the partial derivatives of a loss on the replay maps with respect to
+    viewmatrix [4,4] and projmatrix [4,4] -- independent inputs, in their own (transposed, row-vector) layout -- from the
+    per-Gaussian sums a _screen map backward has just written: dL_dmeans2D [P,3], dL_dconic [P,4] (A, B, -, C), dL_dz [P]
+    (None = zero).  scales / rotations ACTIVATED, or cov3D_precomp.  -> {name: tensor} for the names in `want` (a subset of
+    CAMERA_MAP_GRADS).  Two launches, no host wait; the workspace comes from torch's caching allocator per call.  Tensors are
+    read in place: a host tensor, a wrong dtype or a non-contiguous tensor is refused."""
+    want = _subset("camera_backward_maps", "gradient", want, CAMERA_MAP_GRADS)
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("camera_backward_maps: means3D must have dimensions (num_points, 3)")
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("camera_backward_maps: means3D: the MI355X rasterizer needs device tensors (no CPU path)")
+    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+
+    def take(t, name, numel=None, dtype=torch.float32):
+        try:
+            return _cam_tensor(t, dev, name, numel, dtype)
+        except RuntimeError as e:   # the refusals of camera_backward, under this call's name
+            raise RuntimeError(str(e).replace("camera_backward:", "camera_backward_maps:", 1)) from None
+    m3 = take(means3D, "means3D")
+    vm, pm = take(viewmatrix, "viewmatrix", 16), take(projmatrix, "projmatrix", 16)
+    sc, rot = take(scales, "scales", 3 * P), take(rotations, "rotations", 4 * P)
+    cov = take(cov3D_precomp, "cov3D_precomp", 6 * P)
+    rad = take(radii, "radii", P, torch.int32)
+    g2, gcon, gz = take(dL_dmeans2D, "dL_dmeans2D", 3 * P), take(dL_dconic, "dL_dconic", 4 * P), take(dL_dz, "dL_dz", P)
+    if P and (vm is None or pm is None):
+        raise RuntimeError("camera_backward_maps: viewmatrix and projmatrix are needed")
+    out = {name: torch.empty((4, 4), dtype=torch.float32, device=dev) for name in want}
+    with _on_device(dev):
+        work = _workspace("camera_backward_maps", _lib.r3dgs_camera_backward_maps_workspace_bytes(P), dev, False)
+        _check(_lib.r3dgs_camera_backward_maps(
+            P, W, H, _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(cov), _ptr(vm), _ptr(pm), float(tanfovx),
+            float(tanfovy), _ptr(rad), _ptr(g2), _ptr(gcon), _ptr(gz), *[_ptr(out.get(name)) for name in CAMERA_MAP_GRADS],
+            work.data_ptr(), _stream()), "camera_backward_maps")
     return out
 
 

@@ -564,6 +564,120 @@ def feature_maps_with_grad(features, means3D, means2D, opacities, scales, rotati
                               raster_settings)
 
 
+# ---- the three replay maps with the camera differentiable as well (_AuxMapsCam, _DistortionMapCam, _FeatureMapsCam).  Each is
+# its counterpart above plus two inputs (viewmatrix, projmatrix, LAST, as _RasterizeGaussiansCam has them) and, in the backward,
+# the map's _screen call followed by a camera pass of its own (_C.camera_backward_maps); autograd adds the shares of the maps
+# and of the colour route.  There is no campos input: no SH direction is involved. ---------------------------------------------
+
+def _cam_map_settings(raster_settings, model_device, viewmatrix, projmatrix):
+    """raster_settings with the two camera tensors as the native calls read them -- detached, contiguous -- checked in the
+    forward: the camera pass reads them in place and would refuse them only in the backward."""
+    for name, t in (("viewmatrix", viewmatrix), ("projmatrix", projmatrix)):
+        if not isinstance(t, torch.Tensor) or t.numel() != 16:
+            raise RuntimeError(f"camera gradients of the maps: {name} must be a tensor of 16 elements")
+        if t.device != model_device:
+            raise RuntimeError(f"camera gradients of the maps: {name}: expected a tensor on {model_device}, got {t.device}")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"camera gradients of the maps: {name}: expected float32, got {str(t.dtype)[6:]}")
+    return raster_settings._replace(viewmatrix=viewmatrix.detach().contiguous(), projmatrix=projmatrix.detach().contiguous())
+
+
+def _replay_backward_cam(ctx, native, names, *upstream):
+    """_replay_backward for a function whose last two inputs are viewmatrix and projmatrix: where one of them needs a gradient
+    the native call is its _screen form, asked for the screen-space sums as well, and `_C.camera_backward_maps` turns those into
+    the two partial derivatives.  A model none of whose tensors needs a gradient (a tracker) is not differentiated at all."""
+    rs = ctx.raster_settings
+    means3D, scales, rotations, cov3D_precomp, radii, geomBuffer, binningBuffer, imgBuffer = ctx.saved_tensors[:8]
+    needs = ctx.needs_input_grad
+    want = tuple(n for n, need in zip(names, needs) if need)
+    cam_want = tuple(n for n, need in zip(_C.CAMERA_MAP_GRADS, needs[-2:]) if need)
+    screen = ("means2D",) + _C.SCREEN_GRADS
+    got = native(int(radii.numel()), ctx.num_rendered, rs.image_height, rs.image_width, geomBuffer, binningBuffer, imgBuffer,
+                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, means3D, scales, rs.scale_modifier, rotations,
+                 cov3D_precomp, radii, *upstream, want=want + tuple(n for n in screen if cam_want and n not in want),
+                 _screen=bool(cam_want))
+    cam = {}
+    if cam_want:
+        cam = _C.camera_backward_maps(means3D, scales, rotations, rs.scale_modifier, cov3D_precomp, rs.viewmatrix, rs.projmatrix,
+                                      rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, radii, got["means2D"],
+                                      got["conic"], got["z"], want=cam_want)
+    return (tuple(got[n] if n in want else None for n in names) + (None,) * (len(needs) - len(names) - 2)
+            + tuple(cam.get(n) for n in _C.CAMERA_MAP_GRADS))
+
+
+class _AuxMapsCam(torch.autograd.Function):
+    """_AuxMaps with the camera differentiable: its inputs, then viewmatrix [4,4] and projmatrix [4,4] -- the tensors of
+    raster_settings, handed in as arguments so that autograd sees them.  The backward is `_C.aux_maps_backward_screen` and
+    `_C.camera_backward_maps`; the two are independent inputs, chained outside (r3dgs_camera.RefinedCamera)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, maps, viewmatrix,
+                projmatrix):
+        rs = _cam_map_settings(raster_settings, means3D.device, viewmatrix, projmatrix)
+        return _AuxMaps.forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, rs, maps)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        up = dict(zip(ctx.maps, grads))
+        return _replay_backward_cam(ctx, _C.aux_maps_backward, _MODEL_INPUTS, up.get("depth"), up.get("alpha"),
+                                    up.get("median_depth"))
+
+
+class _DistortionMapCam(torch.autograd.Function):
+    """_DistortionMap with the camera differentiable: its inputs, then viewmatrix and projmatrix (see _AuxMapsCam).  The
+    backward is `_C.distortion_backward_screen` and `_C.camera_backward_maps`."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, mapping, viewmatrix,
+                projmatrix):
+        rs = _cam_map_settings(raster_settings, means3D.device, viewmatrix, projmatrix)
+        return _DistortionMap.forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, rs, mapping)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return _replay_backward_cam(ctx, _C.distortion_map_backward, _MODEL_INPUTS, grad, ctx.saved_tensors[8], *ctx.mapping)
+
+
+class _FeatureMapsCam(torch.autograd.Function):
+    """_FeatureMaps with the camera differentiable: its inputs, then viewmatrix and projmatrix (see _AuxMapsCam).  The
+    backward is `_C.feature_maps_backward_screen` and `_C.camera_backward_maps`."""
+
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings, viewmatrix,
+                projmatrix):
+        rs = _cam_map_settings(raster_settings, means3D.device, viewmatrix, projmatrix)
+        return _FeatureMaps.forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, rs)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _replay_backward_cam(ctx, _C.feature_maps_backward, ("features",) + _MODEL_INPUTS, ctx.saved_tensors[8], grad_out)
+
+
+def aux_maps_with_camera_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
+                              maps=("depth", "alpha", "median_depth")):
+    """`aux_maps_with_grad` whose maps are attached to raster_settings.viewmatrix / .projmatrix as well."""
+    maps = tuple(maps)
+    rs = raster_settings
+    got = _AuxMapsCam.apply(means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state, rs, maps,
+                            rs.viewmatrix, rs.projmatrix)
+    return dict(zip(maps, got))
+
+
+def distortion_map_with_camera_grad(means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings,
+                                    near=0.0, far=0.0):
+    """`distortion_map_with_grad` whose map is attached to raster_settings.viewmatrix / .projmatrix as well."""
+    rs = raster_settings
+    return _DistortionMapCam.apply(means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state, rs,
+                                   (near, far), rs.viewmatrix, rs.projmatrix)
+
+
+def feature_maps_with_camera_grad(features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, state, raster_settings):
+    """`feature_maps_with_grad` whose map is attached to raster_settings.viewmatrix / .projmatrix as well."""
+    rs = raster_settings
+    return _FeatureMapsCam.apply(features, means3D, means2D, opacities, *_or_empty(scales, rotations, cov3D_precomp), state, rs,
+                                 rs.viewmatrix, rs.projmatrix)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

@@ -36,8 +36,15 @@ Camera gradients.  A camera whose world_view_transform, full_proj_transform or c
 (r3dgs_camera.RefinedCamera builds such a camera from a 6-parameter pose correction) makes "render" differentiable with respect
 to those tensors too, on the raw-parameter route and on the activated one: the backward runs one more pass over the Gaussians
 (include/r3dgs_camera.h) and autograd chains the three partial derivatives through whatever ties the tensors together.  Refused
-with a ValueError: a QuantisedModel, and aux_grad=True (the maps' share of a pose gradient is out of scope).  tan_fov / the focal
-length is not differentiated.
+with a ValueError: a QuantisedModel, and -- unless camera_grad_maps=True -- aux_grad=True, distortion and features_geom_grad=True.
+tan_fov / the focal length is not differentiated.
+
+`camera_grad_maps=True` (with a camera that requires grad; a no-op otherwise) carries the maps' share of a pose gradient: the
+maps of aux_grad=True, distortion= and features_geom_grad=True are attached to world_view_transform / full_proj_transform as well
+as to whatever in the model is trainable (diff_gaussian_rasterization._AuxMapsCam / _DistortionMapCam / _FeatureMapsCam: the
+map's _screen backward, then include/r3dgs_camera.h r3dgs_camera_backward_maps), and autograd adds their shares to the colour
+route's.  The model may be frozen in this mode -- a tracker: only the camera gets gradients, and the "nothing trainable" refusal
+does not apply.  Still refused: normals=True, antialiasing=True and a QuantisedModel with a camera that requires grad.
 
 `features=F` (float32 [P, C] on the model's device, 1 <= C <= _C.FEATURE_MAX_CHANNELS; a non-contiguous F is made contiguous)
 adds the key "features": the [C,H,W] map sum F[id] alpha T over the blended Gaussians (include/r3dgs_features.h) -- not
@@ -46,7 +53,7 @@ with colors_precomp = F[:, c:c+3].  If F requires grad the map is attached to F 
 geometry stays frozen and the backward skips its sums); `features_geom_grad=True` attaches it to the model's geometry as well,
 and those gradients add to the colour backward's through autograd ("viewspace_points".grad receives both).  `pc` may be a
 QuantisedModel.  Refused with a ValueError: features_geom_grad=True for a QuantisedModel, together with a camera that requires
-grad, or under no_grad; an F of the wrong shape, dtype, device or channel count.  `features` combines freely with `aux` /
+grad (unless camera_grad_maps=True), or under no_grad; an F of the wrong shape, dtype, device or channel count.  `features` combines freely with `aux` /
 `aux_grad`; features=None (the default): the same dictionary, no extra launch, no recorder.
 
 Anti-aliasing.  `antialiasing=True` multiplies every Gaussian's opacity by rho = sqrt(det C / det(C + 0.3 I)) of its projected
@@ -79,7 +86,7 @@ Under grad mode, for a model with something trainable, the map is attached to th
 no_grad, nothing trainable, a QuantisedModel -- it is detached.  The 2DGS recipe: lambda_dist * out["distortion"].mean() next
 to r3dgs_normals.normal_consistency.  It combines with `aux`, `aux_grad`, `features`, `normals`, `antialiasing` and `filter_3d`
 on every route; distortion=None / False (the default): the same dictionary, nothing new is launched.  Refused with a
-ValueError before anything is launched: a trainable QuantisedModel under grad mode, a camera that requires grad, a (near, far)
+ValueError before anything is launched: a trainable QuantisedModel under grad mode, a camera that requires grad (unless camera_grad_maps=True), a (near, far)
 that is neither (0, 0) nor 0 < near < far.
 
 Absolute screen-space gradients (AbsGS; gsplat's absgrad).  `absgrad=True`: after backward(), out["viewspace_points"].absgrad is a
@@ -100,9 +107,10 @@ import threading
 
 import torch
 
-from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps, aux_maps_with_grad,
-                                         distortion_map, distortion_map_with_grad, feature_maps, feature_maps_with_grad,
-                                         rasterize_gaussian_params)
+from diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, _C, aux_maps,
+                                         aux_maps_with_camera_grad, aux_maps_with_grad, distortion_map,
+                                         distortion_map_with_camera_grad, distortion_map_with_grad, feature_maps,
+                                         feature_maps_with_camera_grad, feature_maps_with_grad, rasterize_gaussian_params)
 from diff_gaussian_rasterization import absgrad as absgrad_scope
 from r3dgs_quantised import QuantisedModel
 
@@ -279,7 +287,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
 _render = render   # the reference's signature, parameter for parameter (tests/test_params_cpu.py holds it to the reference's source)
 
 
-def _checked_features(features, pc, features_geom_grad, camera):
+def _checked_features(features, pc, features_geom_grad, camera, cam_maps=False):
     """The refusals of render(features=...), before anything is launched."""
     P = int(pc.P) if isinstance(pc, QuantisedModel) else int(pc._xyz.shape[0])
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != P:
@@ -293,17 +301,17 @@ def _checked_features(features, pc, features_geom_grad, camera):
     if features.device.type != "cuda" or features.device != where:
         raise ValueError(f"render: features must live on the model's device ({where}), got {features.device}")
     if features_geom_grad:
-        _checked_geom_grad(pc, camera)
+        _checked_geom_grad(pc, camera, cam_maps)
 
 
-def _checked_geom_grad(pc, camera):
+def _checked_geom_grad(pc, camera, cam_maps=False):
     """The refusals of render(features_geom_grad=True)."""
     if isinstance(pc, QuantisedModel):
         raise ValueError("render: features_geom_grad=True is not available for a QuantisedModel (geometry gradients of its "
                          "codebooks through the feature map are out of scope); its features alone can be trained")
-    if camera_requires_grad(camera):
+    if camera_requires_grad(camera) and not cam_maps:
         raise ValueError("render: features_geom_grad=True together with a camera that requires grad is not supported: the "
-                         "feature map's share of a pose gradient is out of scope")
+                         "feature map's share of a pose gradient is out of scope (camera_grad_maps=True carries it)")
     if not torch.is_grad_enabled():
         raise ValueError("render: features_geom_grad=True under no_grad: there is no graph to attach the map to")
 
@@ -314,7 +322,7 @@ def _anchored(zero, tensors):
     return zero + 0.0 * sum(t.sum() for t in tensors if t is not None and t.requires_grad)
 
 
-def _feature_map(features, camera, out, state, rs, inputs=None):
+def _feature_map(features, camera, out, state, rs, inputs=None, cam_maps=False):
     """The "features" entry of the result: [C,H,W] from the six-tuple `state` of the forward that produced `out` (None: an empty
     model -- a zero map), attached to `features` when it requires grad and, with `inputs` (means3D, opacities, scales,
     rotations, cov3D_precomp), to the model's geometry as well."""
@@ -330,10 +338,11 @@ def _feature_map(features, camera, out, state, rs, inputs=None):
         empty = torch.Tensor([])
         return feature_maps_with_grad(features, empty, empty, empty, None, None, None, state, rs)
     means3D, opacities, scales, rotations, cov3D = inputs
-    return feature_maps_with_grad(features, means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs)
+    attached = feature_maps_with_camera_grad if cam_maps else feature_maps_with_grad
+    return attached(features, means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs)
 
 
-def _distortion_map(mapping, camera, out, state, rs, inputs):
+def _distortion_map(mapping, camera, out, state, rs, inputs, cam_maps=False):
     """The "distortion" entry of the result: [1,H,W] from the six-tuple `state` of the forward that produced `out` (None: an
     empty model -- a zero map); with `inputs` (means3D, opacities, scales, rotations, cov3D_precomp) attached to them."""
     H, W = int(camera.image_height), int(camera.image_width)
@@ -345,7 +354,8 @@ def _distortion_map(mapping, camera, out, state, rs, inputs):
         num_rendered, _, radii, geom, binning, img = state
         return distortion_map(int(radii.numel()), num_rendered, H, W, geom, binning, img, near, far)
     means3D, opacities, scales, rotations, cov3D = inputs
-    return distortion_map_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs, near, far)
+    attached = distortion_map_with_camera_grad if cam_maps else distortion_map_with_grad
+    return attached(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, state, rs, near, far)
 
 
 _SIGNATURE = inspect.signature(_render)
@@ -446,6 +456,7 @@ def render(*args, aux=None, **kwargs):
     normals = bool(kwargs.pop("normals", False))             # likewise: the "normal" map (the module's docstring)
     distortion = kwargs.pop("distortion", None)              # likewise: the "distortion" map; None / False: no such key
     mapping = None if distortion is None or distortion is False else _C.depth_mapping(distortion)
+    camera_grad_maps = bool(kwargs.pop("camera_grad_maps", False))   # likewise: the maps' share of a pose gradient
     camera = args[0] if args else kwargs.get("viewpoint_camera")
     if callable(getattr(camera, "snapshot", None)):   # a camera that builds its tensors on access (r3dgs_camera.RefinedCamera):
         camera = camera.snapshot()                    # built once for this render
@@ -459,18 +470,21 @@ def render(*args, aux=None, **kwargs):
         b.arguments["pc"] = _antialiased_model(camera, b.arguments["pc"], b.arguments["pipe"], b.arguments["bg_color"],
                                                b.arguments["scaling_modifier"], antialiasing, filter_3d)
         args, kwargs = b.args, b.kwargs
+    # the maps attached to the camera's tensors as well (a no-op for a camera that does not require grad)
+    cam_maps = camera_grad_maps and camera_requires_grad(camera)
     if camera_requires_grad(camera):   # (before anything is launched)
         pc = args[1] if len(args) > 1 else kwargs.get("pc")
         if isinstance(pc, QuantisedModel):
             raise ValueError("render: camera gradients are not available for a QuantisedModel (its forward reads ids and "
                              "codebooks; no backward of it writes the per-Gaussian sums they are formed from); decode() it and "
                              "render the dense tensors")
-        if aux_grad:
+        if aux_grad and not cam_maps:
             raise ValueError("render: aux_grad=True together with a camera that requires grad is not supported: the maps' "
-                             "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera)")
-        if mapping is not None:
+                             "share of a pose gradient is out of scope (render the maps without aux_grad, or detach the camera; "
+                             "camera_grad_maps=True carries it)")
+        if mapping is not None and not cam_maps:
             raise ValueError("render: distortion together with a camera that requires grad is not supported: the map's "
-                             "share of a pose gradient is out of scope (detach the camera)")
+                             "share of a pose gradient is out of scope (detach the camera; camera_grad_maps=True carries it)")
     if features is None and features_geom_grad and not normals:
         raise ValueError("render: features_geom_grad=True without features: pass the [P, C] tensor the map is blended from")
     if aux is None:   # nothing changes: no recorder, no extra launch, the same dictionary
@@ -493,9 +507,9 @@ def render(*args, aux=None, **kwargs):
     if normals:                # (before anything is launched)
         _checked_normals(camera, pc, pipe, features)
         if features is None and features_geom_grad:
-            _checked_geom_grad(pc, camera)
+            _checked_geom_grad(pc, camera, cam_maps)
     if features is not None:   # (before anything is launched)
-        _checked_features(features, pc, features_geom_grad, camera)
+        _checked_features(features, pc, features_geom_grad, camera, cam_maps)
     # the distortion map is attached whenever there is a graph to attach it to; a QuantisedModel gets the detached map
     dist_attach = mapping is not None and torch.is_grad_enabled() and not isinstance(pc, QuantisedModel)
     if mapping is not None and isinstance(pc, QuantisedModel) and pc.trainable and torch.is_grad_enabled():
@@ -534,13 +548,15 @@ def render(*args, aux=None, **kwargs):
         _tls.inputs = None
     means3D, opacities, scales, rotations, cov3D = got["inputs"]
     trainable = any(t is not None and t.requires_grad for t in got["inputs"])
-    if not trainable and (aux_grad or features_geom_grad):
+    if not trainable and (aux_grad or features_geom_grad) and not cam_maps:   # (a tracker: the camera alone is fitted)
         raise ValueError(f"render: {'aux_grad' if aux_grad else 'features_geom_grad'}=True for a model with nothing trainable")
     rs = _settings(camera, pc, pipe, a["bg_color"], a["scaling_modifier"])
     if mapping is not None:   # (nothing trainable: the detached map)
-        out["distortion"] = _distortion_map(mapping, camera, out, st.result, rs, got["inputs"] if trainable else None)
+        out["distortion"] = _distortion_map(mapping, camera, out, st.result, rs, got["inputs"] if trainable or cam_maps else None,
+                                            cam_maps)
     if features is not None:
-        out["features"] = _feature_map(features, camera, out, st.result, rs, got["inputs"] if features_geom_grad else None)
+        out["features"] = _feature_map(features, camera, out, st.result, rs, got["inputs"] if features_geom_grad else None,
+                                       cam_maps and features_geom_grad)
     out = blended(out)
     if not aux_grad:
         return _with_aux(aux, camera, out, st.result)
@@ -548,5 +564,6 @@ def render(*args, aux=None, **kwargs):
         out = _with_aux(aux, camera, out, None)
         out.update({name: _anchored(out[name], got["inputs"]) for name in aux})
         return out
-    out.update(aux_maps_with_grad(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, st.result, rs, maps=aux))
+    attached = aux_maps_with_camera_grad if cam_maps else aux_maps_with_grad
+    out.update(attached(means3D, out["viewspace_points"], opacities, scales, rotations, cov3D, st.result, rs, maps=aux))
     return out
