@@ -13,9 +13,12 @@
 //     of a zero-padded convolution with a symmetric window is the same filter over in-image positions, so
 //     dx = F[gS dS/dmu_x] + 2x F[gS dS/dE_xx] + y F[gS dS/dE_xy] + g_l1 sign(x - y) / n.
 // No atomics anywhere: every sum has a fixed order (ssim_tile.h), so values and gradients are identical run to run.
+// The second half of the file is the same loss behind a per-image exposure and a pixel mask (r3dgs_exposure_loss_*,
+// exposure_math.h): its own kernels on the same tile filter and the same reduction; the kernels above are not touched by it.
 #include "../../include/r3dgs_loss.h"
 
 #include "common.h"
+#include "exposure_math.h"
 #include "loss_math.h"
 #include "ssim_tile.h"
 
@@ -198,6 +201,280 @@ void check_shape(int B, int C, int H, int W)
                         std::to_string(C) + "x" + std::to_string(H) + "x" + std::to_string(W));
 }
 
+// ---- the same loss behind a per-image exposure and a pixel mask (r3dgs_exposure_loss_*): x'' = m (x E[:, :3] + E[:, 3]),
+// y' = m y or y (exposure_math.h).  The forward stages (x'', y') instead of (x, y) and is the plain forward from there on;
+// the backward recomputes x'' and y' where the plain one reads x and y, and carries the gradient of x'' on to x and to E.
+
+struct ExposureIn {
+    const float* E;      // [B or 1][3][4], or NULL: identity
+    const float* mask;   // [B or 1][H][W], or NULL: ones
+    int e_per_image, mask_per_image, mask_target;
+};
+
+struct ExpFwdArgs {
+    FwdArgs f;   // x, y: the inputs before the map; ssim_map unused
+    int C;
+    ExposureIn in;
+};
+
+__global__ __launch_bounds__(kBlock) void exposure_fwd_kernel(ExpFwdArgs a)
+{
+    __shared__ float sxy[2][kInH][kInW];
+    __shared__ float sh[5][kInH][kTW];
+    __shared__ float red[2][kBlock / 64];
+    const int W = a.f.p.W;
+    const Tile tl = tile_of(a.f.p);
+    const size_t hw = (size_t)a.f.p.H * W;
+    const size_t base = (size_t)tl.plane * hw;
+    const int b = tl.plane / a.C, ch = tl.plane - b * a.C;
+    const float* Y = a.f.y + base;
+    const float* M = a.in.mask ? a.in.mask + (a.in.mask_per_image ? (size_t)b * hw : 0) : nullptr;
+    // this channel's own plane (the diagonal term) and, under an exposure, the other two in rising order with their coefficients
+    const float* Xd = a.f.x + base;
+    const float *Xa = Xd, *Xb = Xd;
+    float ed = 1.f, ea = 0.f, eb = 0.f, off = 0.f;
+    if (a.in.E) {
+        const float* E = a.in.E + (a.in.e_per_image ? (size_t)b * kExposureFloats : 0);
+        const int ka = exposure_other_a(ch), kb = exposure_other_b(ch);
+        Xa = a.f.x + ((size_t)b * 3 + ka) * hw;
+        Xb = a.f.x + ((size_t)b * 3 + kb) * hw;
+        ed = E[4 * ch + ch];
+        ea = E[4 * ka + ch];
+        eb = E[4 * kb + ch];
+        off = E[4 * ch + 3];
+    }
+    stage_tiles(a.f.p, tl, sxy, [&](int gy, int gx, float (&v)[2]) {
+        const size_t o = (size_t)gy * W + gx;
+        const float m = M ? M[o] : 1.f;
+        const float yv = Y[o];
+        v[0] = a.in.E ? exposure_sum(ed, ea, eb, off, Xd[o], Xa[o], Xb[o], m) : m * Xd[o];
+        v[1] = a.in.mask_target ? m * yv : yv;
+    });
+    float acc[kRows][5];
+    filter_tile(a.f.win, sh, acc, MomentTaps{sxy});
+    float sums[2] = {0.f, 0.f};   // S, |x'' - y'|
+    for_each_output(a.f.p, tl, [&](int o, int gy, int gx, int r, int c) {
+        const float xv = sxy[0][r][c], yv = sxy[1][r][c];
+        const SsimPixel px = ssim_pixel(acc[o][0], acc[o][1], acc[o][2], acc[o][3], acc[o][4]);
+        sums[0] += px.s;
+        sums[1] += fabsf(xv - yv);
+        const size_t q = base + (size_t)gy * W + gx;
+        if (a.f.partials) {
+            a.f.partials[q] = px.d_mu;
+            a.f.partials[a.f.n + q] = px.d_exx;
+            a.f.partials[2 * a.f.n + q] = px.d_exy;
+        }
+    });
+    block_sums(sums, red);
+    if (threadIdx.x == 0) {
+        a.f.slots[blockIdx.x] = sums[0];
+        a.f.slots[a.f.nblocks + blockIdx.x] = sums[1];
+    }
+}
+
+struct ExpBwdArgs {
+    Plane p;
+    int C;
+    const float* x;
+    const float* y;
+    const float* partials;
+    const float* g;     // upstream gradient of the loss, [1]
+    float coef_l1, coef_s, inv_n;
+    ExposureIn in;
+    float* dx;
+    double* slots;      // [12][nslots] per-workgroup sums of dE, or NULL: dE not wanted
+    int nslots;
+    long long n;
+    Window win;
+};
+
+// No exposure (any C): one workgroup per (plane, tile) as the plain backward, with x'' = m x, y' = m y or y, dx = m g.
+__global__ __launch_bounds__(kBlock) void masked_bwd_kernel(ExpBwdArgs a)
+{
+    __shared__ float sq[3][kInH][kInW];
+    __shared__ float sh[3][kInH][kTW];
+    const int W = a.p.W;
+    const Tile tl = tile_of(a.p);
+    const size_t hw = (size_t)a.p.H * W;
+    const size_t base = (size_t)tl.plane * hw;
+    const float* M = a.in.mask ? a.in.mask + (a.in.mask_per_image ? (size_t)(tl.plane / a.C) * hw : 0) : nullptr;
+    const float gs_uniform = a.coef_s * a.g[0] * a.inv_n;
+    const float gl = a.coef_l1 * a.g[0] * a.inv_n;
+    stage_tiles(a.p, tl, sq, [&](int gy, int gx, float (&v)[3]) {
+        const size_t q = base + (size_t)gy * W + gx;
+        const float g = gs_uniform;
+        v[0] = g * a.partials[q];
+        v[1] = g * a.partials[a.n + q];
+        v[2] = g * a.partials[2 * a.n + q];
+    });
+    float acc[kRows][3];
+    filter_tile(a.win, sh, acc, [&](int r, int c, float (&v)[3]) {
+#pragma unroll
+        for (int m = 0; m < 3; m++) v[m] = sq[m][r][c];
+    });
+    for_each_output(a.p, tl, [&](int o, int gy, int gx, int, int) {
+        const size_t q = base + (size_t)gy * W + gx;
+        const float m = M ? M[q - base] : 1.f;
+        const float xv = m * a.x[q], yv = a.in.mask_target ? m * a.y[q] : a.y[q];
+        const float ds = acc[o][0] + 2.f * xv * acc[o][1] + yv * acc[o][2];
+        a.dx[q] = m * (gl * l1_sign(xv, yv) + ds);
+    });
+}
+
+// Under an exposure (C = 3): one workgroup per (image, tile).  Per channel the scaled partials are staged and filtered and
+// g_c = dL/dx''_c formed from the recomputed x''_c and y'_c; the kRows x 3 values of g stay in registers, then dx_k of the three
+// planes is written and the twelve terms of dE summed per thread in double, per workgroup into its slots (fixed order).
+__global__ __launch_bounds__(kBlock) void exposure_bwd_kernel(ExpBwdArgs a)
+{
+    __shared__ float sq[3][kInH][kInW];
+    __shared__ float sh[3][kInH][kTW];
+    __shared__ double red[kExposureFloats][kBlock / 64];
+    const int W = a.p.W;
+    const Tile tl = tile_of(a.p);   // .plane: the image
+    const size_t hw = (size_t)a.p.H * W;
+    const size_t ibase = (size_t)tl.plane * 3 * hw;
+    const float* M = a.in.mask ? a.in.mask + (a.in.mask_per_image ? (size_t)tl.plane * hw : 0) : nullptr;
+    const float* Eg = a.in.E + (a.in.e_per_image ? (size_t)tl.plane * kExposureFloats : 0);
+    float E[kExposureFloats];
+#pragma unroll
+    for (int i = 0; i < kExposureFloats; i++) E[i] = Eg[i];
+    const float gs_uniform = a.coef_s * a.g[0] * a.inv_n;
+    const float gl = a.coef_l1 * a.g[0] * a.inv_n;
+    float xin[kRows][3], mv[kRows], g[kRows][3];
+#pragma unroll
+    for (int o = 0; o < kRows; o++) {
+        mv[o] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) xin[o][k] = g[o][k] = 0.f;
+    }
+    for_each_output(a.p, tl, [&](int o, int gy, int gx, int, int) {
+        const size_t q = (size_t)gy * W + gx;
+        mv[o] = M ? M[q] : 1.f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) xin[o][k] = a.x[ibase + k * hw + q];
+    });
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const size_t base = ibase + c * hw;
+        stage_tiles(a.p, tl, sq, [&](int gy, int gx, float (&v)[3]) {
+            const size_t q = base + (size_t)gy * W + gx;
+            v[0] = gs_uniform * a.partials[q];
+            v[1] = gs_uniform * a.partials[a.n + q];
+            v[2] = gs_uniform * a.partials[2 * a.n + q];
+        });
+        float acc[kRows][3];
+        filter_tile(a.win, sh, acc, [&](int r, int col, float (&v)[3]) {
+#pragma unroll
+            for (int m = 0; m < 3; m++) v[m] = sq[m][r][col];
+        });
+        for_each_output(a.p, tl, [&](int o, int gy, int gx, int, int) {
+            const size_t q = base + (size_t)gy * W + gx;
+            const float xv = exposed(E, xin[o][0], xin[o][1], xin[o][2], mv[o], c);
+            const float yv = a.in.mask_target ? mv[o] * a.y[q] : a.y[q];
+            const float ds = acc[o][0] + 2.f * xv * acc[o][1] + yv * acc[o][2];
+            g[o][c] = gl * l1_sign(xv, yv) + ds;
+        });
+    }
+    double dE[kExposureFloats];
+#pragma unroll
+    for (int i = 0; i < kExposureFloats; i++) dE[i] = 0.0;
+    for_each_output(a.p, tl, [&](int o, int gy, int gx, int, int) {
+        const size_t q = ibase + (size_t)gy * W + gx;
+#pragma unroll
+        for (int k = 0; k < 3; k++) a.dx[q + k * hw] = exposed_adjoint(E, g[o][0], g[o][1], g[o][2], mv[o], k);
+        if (a.slots) exposure_grad_accumulate(dE, xin[o][0], xin[o][1], xin[o][2], g[o][0], g[o][1], g[o][2], mv[o]);
+    });
+    if (!a.slots) return;
+    block_sums(dE, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kExposureFloats; i++) a.slots[(size_t)i * a.nslots + blockIdx.x] = dE[i];
+    }
+}
+
+struct ExpFinishArgs {
+    int B, tiles, shared;
+    const double* slots;   // [12][B * tiles]
+    float* dE;             // [B][3][4], or [3][4] when shared
+};
+
+// One workgroup: each of the twelve entries, image by image, thread-strided double sums of its slots and a fixed tree; a shared
+// exposure gets the sum over the images in their order.
+__global__ __launch_bounds__(kBlock) void exposure_finish_kernel(ExpFinishArgs a)
+{
+    __shared__ double buf[kBlock];
+    const int t = threadIdx.x;
+    const size_t nslots = (size_t)a.B * a.tiles;
+    for (int i = 0; i < kExposureFloats; i++) {
+        double total = 0.0;
+        for (int b = 0; b < a.B; b++) {
+            double s = 0.0;
+            const double* row = a.slots + i * nslots + (size_t)b * a.tiles;
+            for (int j = t; j < a.tiles; j += kBlock) s += row[j];
+            s = tree_sum(s, buf);
+            total += s;
+            if (t == 0 && !a.shared) a.dE[b * kExposureFloats + i] = (float)s;
+        }
+        if (t == 0 && a.shared) a.dE[i] = (float)total;
+    }
+}
+
+// out = clamp?(x E[:, :3] + E[:, 3]) per pixel: evaluation and saving (train_test_exp); no gradient
+__global__ __launch_bounds__(kBlock) void exposure_apply_kernel(long long npix, long long hw, const float* __restrict__ img,
+                                                                const float* __restrict__ exposure, int e_per_image, int clamp01,
+                                                                float* __restrict__ out)
+{
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= npix) return;
+    const long long b = p / hw, q = b * 3 * hw + (p - b * hw);
+    const float* E = exposure + (e_per_image ? b * kExposureFloats : 0);
+    const float x0 = img[q], x1 = img[q + hw], x2 = img[q + 2 * hw];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float v = exposed(E, x0, x1, x2, 1.f, c);
+        if (clamp01) v = fminf(fmaxf(v, 0.f), 1.f);
+        out[q + c * hw] = v;
+    }
+}
+
+// byte offsets in the exposure loss's workspace: the forward's float slots [2][B*C*tiles], then the backward's double slots
+// [12][B*tiles]
+struct ExpWorkspace {
+    long long nblocks, image_tiles;   // B*C*tiles, B*tiles; nblocks < 0: invalid shape
+    size_t dE_offset, bytes;
+};
+
+ExpWorkspace exposure_workspace(int B, int C, int H, int W)
+{
+    ExpWorkspace w{};
+    w.nblocks = ssim_blocks(B, C, H, W);
+    if (w.nblocks < 0) return w;
+    w.image_tiles = w.nblocks / C;
+    w.dE_offset = (size_t)(2 * w.nblocks) * sizeof(float);
+    w.bytes = w.dE_offset + (size_t)(kExposureFloats * w.image_tiles) * sizeof(double);
+    return w;
+}
+
+// what both exposure loss calls refuse -> the workspace layout
+ExpWorkspace check_exposure_call(const char* what, int B, int C, int H, int W, const float* exposure, const char* workspace,
+                                 size_t workspace_bytes)
+{
+    const std::string name(what);
+    const ExpWorkspace w = exposure_workspace(B, C, H, W);
+    if (w.nblocks < 0)
+        throw r3::Error(name + ": need B, C, H, W >= 1 and fewer than 2^31 tiles, got " + std::to_string(B) + "x" +
+                        std::to_string(C) + "x" + std::to_string(H) + "x" + std::to_string(W));
+    if (exposure && C != 3)
+        throw r3::Error(name + ": an exposure maps 3 colour channels, the images have C = " + std::to_string(C));
+    if (!workspace) throw r3::Error(name + ": a required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(workspace) % sizeof(double) != 0)
+        throw r3::Error(name + ": the workspace must be 8-byte aligned (it holds double sums)");
+    if (workspace_bytes < w.bytes)
+        throw r3::Error(name + ": the workspace holds " + std::to_string(workspace_bytes) + " bytes, this shape needs " +
+                        std::to_string(w.bytes) + " (r3dgs_exposure_loss_workspace_bytes)");
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,6 +598,119 @@ int r3dgs_l1_backward(long long n, const float* x, const float* y, const float* 
         hipStream_t s = static_cast<hipStream_t>(stream);
         l1_bwd_kernel<<<(int)((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(n, x, y, grad, (float)(1.0 / (double)n), grad_x);
         r3::check_launch("l1 backward", s, false);
+        return 0;
+    });
+}
+
+size_t r3dgs_exposure_loss_workspace_bytes(int B, int C, int H, int W)
+{
+    return exposure_workspace(B, C, H, W).bytes;
+}
+
+int r3dgs_exposure_loss_forward(int B, int C, int H, int W, const float* img1, const float* img2, const float* exposure,
+                                int exposure_per_image, const float* mask, int mask_per_image, int mask_target,
+                                float lambda_dssim, float* l1_mean, float* ssim_mean, float* ssim_image, float* loss,
+                                float* dssim, float* partials, char* workspace, size_t workspace_bytes, void* stream)
+{
+    return r3::guarded_call([&]() {
+        check_exposure_call("exposure_loss_forward", B, C, H, W, exposure, workspace, workspace_bytes);
+        if (!img1 || !img2) throw r3::Error("exposure_loss_forward: a required pointer is NULL");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        ExpFwdArgs a;
+        a.f.p = plane_of(H, W);
+        a.f.nblocks = (int)ssim_blocks(B, C, H, W);
+        a.f.x = img1;
+        a.f.y = img2;
+        a.f.ssim_map = nullptr;
+        a.f.partials = partials;
+        a.f.slots = reinterpret_cast<float*>(workspace);
+        a.f.n = (long long)B * C * H * W;
+        a.f.win = window();
+        a.C = C;
+        a.in = ExposureIn{exposure, mask, exposure_per_image != 0, mask_per_image != 0, mask_target != 0};
+        exposure_fwd_kernel<<<a.f.nblocks, kBlock, 0, s>>>(a);
+        r3::check_launch("exposure loss forward", s, false);
+        ReduceArgs r;
+        r.nimages = B;
+        r.blocks_per_image = C * a.f.p.tiles_per_plane;
+        r.nblocks = a.f.nblocks;
+        r.n_image = (double)C * H * W;
+        r.n_total = (double)a.f.n;
+        r.lambda = lambda_dssim;
+        r.slots = a.f.slots;
+        r.l1_mean = l1_mean;
+        r.ssim_mean = ssim_mean;
+        r.ssim_image = ssim_image;
+        r.loss = loss;
+        r.dssim = dssim;
+        loss_reduce_kernel<<<1, kBlock, 0, s>>>(r);
+        r3::check_launch("loss reduce", s, false);
+        return 0;
+    });
+}
+
+int r3dgs_exposure_loss_backward(int B, int C, int H, int W, const float* img1, const float* img2, const float* exposure,
+                                 int exposure_per_image, const float* mask, int mask_per_image, int mask_target,
+                                 const float* partials, const float* grad_loss, float coef_l1, float coef_ssim,
+                                 float* grad_img1, float* grad_exposure, char* workspace, size_t workspace_bytes, void* stream)
+{
+    return r3::guarded_call([&]() {
+        const ExpWorkspace w = check_exposure_call("exposure_loss_backward", B, C, H, W, exposure, workspace, workspace_bytes);
+        if (!img1 || !img2 || !partials || !grad_loss || !grad_img1)
+            throw r3::Error("exposure_loss_backward: a required pointer is NULL");
+        if (grad_exposure && !exposure)
+            throw r3::Error("exposure_loss_backward: grad_exposure is asked for without an exposure");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        ExpBwdArgs a;
+        a.p = plane_of(H, W);
+        a.C = C;
+        a.x = img1;
+        a.y = img2;
+        a.partials = partials;
+        a.g = grad_loss;
+        a.coef_l1 = coef_l1;
+        a.coef_s = coef_ssim;
+        a.n = (long long)B * C * H * W;
+        a.inv_n = (float)(1.0 / (double)a.n);
+        a.in = ExposureIn{exposure, mask, exposure_per_image != 0, mask_per_image != 0, mask_target != 0};
+        a.dx = grad_img1;
+        a.slots = grad_exposure ? reinterpret_cast<double*>(workspace + w.dE_offset) : nullptr;
+        a.nslots = (int)w.image_tiles;
+        a.win = window();
+        if (!exposure) {
+            masked_bwd_kernel<<<(int)w.nblocks, kBlock, 0, s>>>(a);
+            r3::check_launch("masked loss backward", s, false);
+            return 0;
+        }
+        exposure_bwd_kernel<<<(int)w.image_tiles, kBlock, 0, s>>>(a);
+        r3::check_launch("exposure loss backward", s, false);
+        if (grad_exposure) {
+            ExpFinishArgs f;
+            f.B = B;
+            f.tiles = a.p.tiles_per_plane;
+            f.shared = !exposure_per_image;
+            f.slots = a.slots;
+            f.dE = grad_exposure;
+            exposure_finish_kernel<<<1, kBlock, 0, s>>>(f);
+            r3::check_launch("exposure gradient finish", s, false);
+        }
+        return 0;
+    });
+}
+
+int r3dgs_exposure_apply(int B, int H, int W, const float* img, const float* exposure, int exposure_per_image, int clamp01,
+                         float* out, void* stream)
+{
+    return r3::guarded_call([&]() {
+        const long long hw = (long long)H * W, npix = hw * B;
+        if (B < 1 || H < 1 || W < 1 || (npix + kBlock - 1) / kBlock > 0x7fffffffLL)
+            throw r3::Error("exposure_apply: need B, H, W >= 1 and fewer than 2^39 pixels, got " + std::to_string(B) + "x3x" +
+                            std::to_string(H) + "x" + std::to_string(W));
+        if (!img || !exposure || !out) throw r3::Error("exposure_apply: a required pointer is NULL");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        exposure_apply_kernel<<<(int)((npix + kBlock - 1) / kBlock), kBlock, 0, s>>>(npix, hw, img, exposure,
+                                                                                    exposure_per_image != 0, clamp01 != 0, out);
+        r3::check_launch("exposure apply", s, false);
         return 0;
     });
 }

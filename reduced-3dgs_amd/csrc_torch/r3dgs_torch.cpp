@@ -9,7 +9,7 @@
 // cache, one reservation advisor -- whichever build R3DGS_LIB selected; an unbound module refuses every call.
 //
 // Scope: the two calls a training step makes -- the asynchronous forward (r3dgs_forward_reserved + the strict-mode check
-// of the pass header) and the backward -- plus the fused training loss of r3dgs_loss.h (r3dgs_loss.py) and the fused Adam
+// of the pass header) and the backward -- plus the fused training loss of r3dgs_loss.h (r3dgs_loss.py, r3dgs_exposure.py) and the fused Adam
 // step of r3dgs_optim.h (r3dgs_optim.py).  Everything else (exact-size path, ragged inference forward, counter mode, the
 // reduction operators, debug accessors) stays in the ctypes module diff_gaussian_rasterization/_C.py, which calls this
 // one when it is built (R3DGS_BINDING=ctypes forces the pure-ctypes route).  Why it exists: at small scenes the step is
@@ -89,7 +89,11 @@ using at::Tensor;
     X(r3dgs_quantised_codebook_grad, false)                   \
     X(r3dgs_absgrad_workspace_floats, false)                  \
     X(r3dgs_backward_absgrad, false)                          \
-    X(r3dgs_backward_params_absgrad, false)
+    X(r3dgs_backward_params_absgrad, false)                   \
+    X(r3dgs_exposure_loss_workspace_bytes, false)             \
+    X(r3dgs_exposure_loss_forward, false)                     \
+    X(r3dgs_exposure_loss_backward, false)                    \
+    X(r3dgs_exposure_apply, false)
 
 struct Api {   // (types taken from the C headers)
 #define R3_MEMBER(name, required) decltype(&::name) name = nullptr;
@@ -759,6 +763,73 @@ Tensor l1_backward(const Tensor& x, const Tensor& y, const Tensor& grad)
     return dx;
 }
 
+// ---- the loss behind an exposure and a mask (r3dgs_loss.h r3dgs_exposure_*): the same calls as _C.py's exposure_*;
+// r3dgs_exposure.py has checked the inputs.  An absent exposure or mask is an empty tensor.
+
+void need_exposure() { need(api.r3dgs_exposure_loss_forward, "exposure loss entry points (r3dgs_exposure_loss_forward)"); }
+
+Tensor exposure_workspace(const char* what, int64_t B, int64_t C, int64_t H, int64_t W, const c10::Device& dev)
+{
+    const size_t ws_bytes = api.r3dgs_exposure_loss_workspace_bytes((int)B, (int)C, (int)H, (int)W);
+    if (ws_bytes == 0) throw std::runtime_error(std::string(what) + ": invalid shape");
+    return at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> exposure_loss_forward(
+    const Tensor& img1, const Tensor& img2, const Tensor& exposure, bool exposure_per_image, const Tensor& mask,
+    bool mask_per_image, bool mask_target, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials)
+{
+    need_exposure();
+    const c10::Device dev = img1.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    Tensor l1 = at::empty({}, f32), ssim = at::empty({}, f32), loss = at::empty({}, f32), dssim = at::empty({}, f32);
+    Tensor per_image = at::empty({B}, f32);
+    Tensor partials = want_partials ? at::empty({3, B, C, H, W}, f32) : at::empty({0}, f32);
+    Tensor ws = exposure_workspace("exposure_loss_forward", B, C, H, W, dev);
+    if (api.r3dgs_exposure_loss_forward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
+                                        opt_ptr<float>(exposure), (int)exposure_per_image, opt_ptr<float>(mask), (int)mask_per_image,
+                                        (int)mask_target, (float)lambda_dssim, l1.data_ptr<float>(), ssim.data_ptr<float>(),
+                                        per_image.data_ptr<float>(), loss.data_ptr<float>(), dssim.data_ptr<float>(),
+                                        want_partials ? partials.data_ptr<float>() : nullptr, blob_ptr(ws), (size_t)ws.numel(),
+                                        cur_stream(dev)) < 0)
+        fail("exposure_loss_forward");
+    return {l1, ssim, loss, dssim, per_image, partials};
+}
+
+std::tuple<Tensor, Tensor> exposure_loss_backward(const Tensor& img1, const Tensor& img2, const Tensor& exposure,
+                                                  bool exposure_per_image, const Tensor& mask, bool mask_per_image, bool mask_target,
+                                                  const Tensor& partials, const Tensor& grad_loss, double coef_l1, double coef_ssim,
+                                                  bool want_exposure_grad, int64_t B, int64_t C, int64_t H, int64_t W)
+{
+    need_exposure();
+    const c10::Device dev = img1.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    Tensor dx = at::empty({B, C, H, W}, f32);
+    Tensor dE = !want_exposure_grad ? at::empty({0}, f32) : (exposure_per_image ? at::empty({B, 3, 4}, f32) : at::empty({3, 4}, f32));
+    Tensor ws = exposure_workspace("exposure_loss_backward", B, C, H, W, dev);
+    if (api.r3dgs_exposure_loss_backward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
+                                         opt_ptr<float>(exposure), (int)exposure_per_image, opt_ptr<float>(mask), (int)mask_per_image,
+                                         (int)mask_target, opt_ptr<float>(partials), opt_ptr<float>(grad_loss), (float)coef_l1,
+                                         (float)coef_ssim, dx.data_ptr<float>(), want_exposure_grad ? dE.data_ptr<float>() : nullptr,
+                                         blob_ptr(ws), (size_t)ws.numel(), cur_stream(dev)) < 0)
+        fail("exposure_loss_backward");
+    return {dx, dE};
+}
+
+Tensor exposure_apply(const Tensor& img, const Tensor& exposure, bool exposure_per_image, bool clamp01, int64_t B, int64_t H, int64_t W)
+{
+    need(api.r3dgs_exposure_apply, "exposure loss entry points (r3dgs_exposure_loss_forward)");
+    const c10::Device dev = img.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = at::empty({B, 3, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    if (api.r3dgs_exposure_apply((int)B, (int)H, (int)W, img.data_ptr<float>(), exposure.data_ptr<float>(), (int)exposure_per_image,
+                                 (int)clamp01, out.data_ptr<float>(), cur_stream(dev)) < 0)
+        fail("exposure_apply");
+    return out;
+}
+
 // ---- fused Adam step (r3dgs_optim.h): the same calls as diff_gaussian_rasterization/_C.py's adam_step*; r3dgs_optim.py has
 // checked the tensors (one device, fp32, contiguous, matching sizes).  Scalars arrive as doubles and are rounded to fp32 once.
 
@@ -944,6 +1015,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("l1_ssim_backward", &l1_ssim_backward);
     m.def("l1_forward", &l1_forward);
     m.def("l1_backward", &l1_backward);
+    m.def("exposure_loss_forward", &exposure_loss_forward);
+    m.def("exposure_loss_backward", &exposure_loss_backward);
+    m.def("exposure_apply", &exposure_apply);
     m.def("adam_step", &adam_step);
     m.def("adam_step_capturable", &adam_step_capturable);
     m.def("adam_step_visible", &adam_step_visible);

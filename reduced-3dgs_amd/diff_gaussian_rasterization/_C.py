@@ -176,6 +176,14 @@ _ABI = {
         "r3dgs_knn_query": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_pack_view_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
         "r3dgs_reduce_shards": (_i, [_i, _ll, _ll, _ll, _vp, _vp, _vp]),
+        # include/r3dgs_loss.h, the loss behind an exposure and a mask; called by r3dgs_exposure.py (rows an older library may
+        # lack: _OPTIONAL_ROWS below).  B, C, H, W, img1, img2, exposure, per_image, mask, per_image, mask_target ..
+        "r3dgs_exposure_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+        "r3dgs_exposure_loss_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _f,   # .. lambda
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),      # 5 outputs, partials, workspace
+        "r3dgs_exposure_loss_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i,
+                                              _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp]),   # partials, grad, coefs, 2 outputs
+        "r3dgs_exposure_apply": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     }),
     "params": (_NO_SUCH("raw-parameter entry points"), {   # raster from the model's raw parameters
         "r3dgs_forward_params": (_i, _BLOBS_EXACT + [_i, _vp, _i] + _FWD_PARAMS_TAIL),
@@ -251,6 +259,9 @@ _ABI = {
 _OPTIONAL_ROWS = {
     "absgrad": (_NO_SUCH("absolute-gradient entry points (r3dgs_backward_absgrad)"),
                 ("r3dgs_absgrad_workspace_floats", "r3dgs_backward_absgrad", "r3dgs_backward_params_absgrad")),
+    "exposure": (_NO_SUCH("exposure loss entry points (r3dgs_exposure_loss_forward)"),
+                 ("r3dgs_exposure_loss_workspace_bytes", "r3dgs_exposure_loss_forward", "r3dgs_exposure_loss_backward",
+                  "r3dgs_exposure_apply")),
 }
 
 
@@ -2080,6 +2091,87 @@ def l1_backward(x, y, grad):
     with _on_device(dev):
         _check(_lib.r3dgs_l1_backward(x.numel(), _ptr(x), _ptr(y), _ptr(grad), _ptr(dx), _stream()), "l1_backward")
     return dx
+
+
+# ---- the same loss behind a per-image exposure and a pixel mask (include/r3dgs_loss.h r3dgs_exposure_*, csrc/loss.hip); the
+# autograd surface is r3dgs_exposure.py, which checks the inputs.  exposure / mask: device tensors, empty for an absent one;
+# exposure [B,3,4] or [3,4], mask [B,H,W] or [H,W] in memory (per image: the leading B).
+
+def has_exposure_loss():
+    """Whether the loaded library has the exposure loss (r3dgs_exposure_loss_forward)."""
+    return not any(name in _missing_rows for name in _OPTIONAL_ROWS["exposure"][1])
+
+
+def exposure_loss_workspace_bytes(B, Cc, H, W):
+    """r3dgs_exposure_loss_workspace_bytes: 0 for an invalid shape."""
+    _need_rows("exposure")
+    return int(_lib.r3dgs_exposure_loss_workspace_bytes(int(B), int(Cc), int(H), int(W)))
+
+
+def exposure_loss_forward(img1, img2, exposure, exposure_per_image, mask, mask_per_image, mask_target, B, Cc, H, W,
+                          lambda_dssim, want_partials, _workspace=None):
+    """-> (l1, ssim, loss, dssim, ssim_image[B], partials[3,B,C,H,W] or empty); 0-d tensors for the scalars.  One tile kernel
+    + the fixed-order reduction.  _workspace (tests): a uint8 device tensor to use instead of this call's own."""
+    _need_rows("exposure")
+    if _ext is not None and _workspace is None:
+        return _ext.exposure_loss_forward(img1, img2, _t(exposure), bool(exposure_per_image), _t(mask), bool(mask_per_image),
+                                          bool(mask_target), B, Cc, H, W, float(lambda_dssim), bool(want_partials))
+    dev = img1.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    l1, ssim, loss, dssim = (torch.empty((), **f32) for _ in range(4))
+    per_image = torch.empty((B,), **f32)
+    partials = torch.empty((3, B, Cc, H, W), **f32) if want_partials else _NO_TENSOR
+    with _on_device(dev):
+        ws = _workspace
+        if ws is None:
+            ws_bytes = _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W)
+            if ws_bytes == 0:
+                raise RuntimeError(f"exposure_loss_forward: invalid shape {B}x{Cc}x{H}x{W}")
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_exposure_loss_forward(B, Cc, H, W, _ptr(img1), _ptr(img2), _ptr(exposure), int(exposure_per_image),
+                                                _ptr(mask), int(mask_per_image), int(mask_target), float(lambda_dssim),
+                                                _ptr(l1), _ptr(ssim), _ptr(per_image), _ptr(loss), _ptr(dssim), _ptr(partials),
+                                                _ptr(ws), ws.numel(), _stream()), "exposure_loss_forward")
+    return l1, ssim, loss, dssim, per_image, partials
+
+
+def exposure_loss_backward(img1, img2, exposure, exposure_per_image, mask, mask_per_image, mask_target, partials, grad_loss,
+                           coef_l1, coef_ssim, want_exposure_grad, B, Cc, H, W, _workspace=None):
+    """-> (d/d img1 [B,C,H,W], d/d exposure shaped like `exposure` or empty) (r3dgs_exposure_loss_backward)."""
+    _need_rows("exposure")
+    if _ext is not None and _workspace is None:
+        return _ext.exposure_loss_backward(img1, img2, _t(exposure), bool(exposure_per_image), _t(mask), bool(mask_per_image),
+                                           bool(mask_target), partials, grad_loss, float(coef_l1), float(coef_ssim),
+                                           bool(want_exposure_grad), B, Cc, H, W)
+    dev = img1.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    dx = torch.empty((B, Cc, H, W), **f32)
+    dE = torch.empty((B, 3, 4) if exposure_per_image else (3, 4), **f32) if want_exposure_grad else _NO_TENSOR
+    with _on_device(dev):
+        ws = _workspace
+        if ws is None:
+            ws_bytes = _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W)
+            if ws_bytes == 0:
+                raise RuntimeError(f"exposure_loss_backward: invalid shape {B}x{Cc}x{H}x{W}")
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _check(_lib.r3dgs_exposure_loss_backward(B, Cc, H, W, _ptr(img1), _ptr(img2), _ptr(exposure), int(exposure_per_image),
+                                                 _ptr(mask), int(mask_per_image), int(mask_target), _ptr(partials),
+                                                 _ptr(grad_loss), float(coef_l1), float(coef_ssim), _ptr(dx), _ptr(dE),
+                                                 _ptr(ws), ws.numel(), _stream()), "exposure_loss_backward")
+    return dx, dE
+
+
+def exposure_apply(img, exposure, exposure_per_image, clamp01, B, H, W):
+    """-> clamp?(x E[:, :3] + E[:, 3]) [B,3,H,W] (r3dgs_exposure_apply)."""
+    _need_rows("exposure")
+    if _ext is not None:
+        return _ext.exposure_apply(img, exposure, bool(exposure_per_image), bool(clamp01), B, H, W)
+    dev = img.device
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(_lib.r3dgs_exposure_apply(B, H, W, _ptr(img), _ptr(exposure), int(exposure_per_image), int(clamp01), _ptr(out),
+                                         _stream()), "exposure_apply")
+    return out
 
 
 # ---- fused Adam step (include/r3dgs_optim.h, csrc/optim.hip); the optimizer is r3dgs_optim.Adam, which checks the tensors
