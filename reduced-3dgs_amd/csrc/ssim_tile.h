@@ -218,6 +218,21 @@ __device__ __forceinline__ T tree_sum(T v, T* buf)
     return total;
 }
 
+// The finishing sums of N runs of `count` per-workgroup slots: one thread-strided loop adds all N in double, then each goes
+// through the fixed tree in its own row of `buf`; every thread gets the totals.
+template <int N, class T>
+__device__ __forceinline__ void slot_sums(const T* const (&run)[N], int count, double (&sum)[N], double (&buf)[N][kBlock])
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) sum[k] = 0.0;
+    for (int i = threadIdx.x; i < count; i += kBlock) {
+#pragma unroll
+        for (int k = 0; k < N; k++) sum[k] += run[k][i];
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) sum[k] = tree_sum(sum[k], buf[k]);
+}
+
 }  // namespace r3
 
 #endif  // R3DGS_SSIM_TILE_H

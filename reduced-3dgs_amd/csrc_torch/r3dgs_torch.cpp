@@ -697,6 +697,13 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
 
 void need_loss() { need(api.r3dgs_l1_ssim_workspace_bytes, "fused loss"); }
 
+// the scratch tensor of a loss call whose size query said ws_bytes; 0 refuses `what`, "<call>: invalid <size>"
+Tensor loss_workspace(const char* what, size_t ws_bytes, const c10::Device& dev)
+{
+    if (ws_bytes == 0) throw std::runtime_error(what);
+    return at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+}
+
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> l1_ssim_forward(
     const Tensor& img1, const Tensor& img2, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials,
     bool want_map)
@@ -709,9 +716,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> l1_ssim_forwa
     Tensor per_image = at::empty({B}, f32);
     Tensor ssim_map = want_map ? at::empty({B, C, H, W}, f32) : at::empty({0}, f32);
     Tensor partials = want_partials ? at::empty({3, B, C, H, W}, f32) : at::empty({0}, f32);
-    const size_t ws_bytes = api.r3dgs_l1_ssim_workspace_bytes((int)B, (int)C, (int)H, (int)W);
-    if (ws_bytes == 0) throw std::runtime_error("l1_ssim_forward: invalid shape");
-    Tensor ws = at::empty({(int64_t)ws_bytes}, f32.dtype(at::kByte));
+    Tensor ws = loss_workspace("l1_ssim_forward: invalid shape", api.r3dgs_l1_ssim_workspace_bytes((int)B, (int)C, (int)H, (int)W), dev);
     if (api.r3dgs_l1_ssim_forward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
                                   (float)lambda_dssim, l1.data_ptr<float>(), ssim.data_ptr<float>(), per_image.data_ptr<float>(),
                                   loss.data_ptr<float>(), dssim.data_ptr<float>(), want_map ? ssim_map.data_ptr<float>() : nullptr,
@@ -742,9 +747,7 @@ Tensor l1_forward(const Tensor& x, const Tensor& y)
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
     Tensor out = at::empty({}, f32);
-    const size_t ws_bytes = api.r3dgs_l1_workspace_bytes(x.numel());
-    if (ws_bytes == 0) throw std::runtime_error("l1_forward: invalid element count");
-    Tensor ws = at::empty({(int64_t)ws_bytes}, f32.dtype(at::kByte));
+    Tensor ws = loss_workspace("l1_forward: invalid element count", api.r3dgs_l1_workspace_bytes(x.numel()), dev);
     if (api.r3dgs_l1_forward(x.numel(), x.data_ptr<float>(), y.data_ptr<float>(), out.data_ptr<float>(),
                              reinterpret_cast<char*>(ws.data_ptr()), cur_stream(dev)) < 0)
         fail("l1_forward");
@@ -768,13 +771,6 @@ Tensor l1_backward(const Tensor& x, const Tensor& y, const Tensor& grad)
 
 void need_exposure() { need(api.r3dgs_exposure_loss_forward, "exposure loss entry points (r3dgs_exposure_loss_forward)"); }
 
-Tensor exposure_workspace(const char* what, int64_t B, int64_t C, int64_t H, int64_t W, const c10::Device& dev)
-{
-    const size_t ws_bytes = api.r3dgs_exposure_loss_workspace_bytes((int)B, (int)C, (int)H, (int)W);
-    if (ws_bytes == 0) throw std::runtime_error(std::string(what) + ": invalid shape");
-    return at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-}
-
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> exposure_loss_forward(
     const Tensor& img1, const Tensor& img2, const Tensor& exposure, bool exposure_per_image, const Tensor& mask,
     bool mask_per_image, bool mask_target, int64_t B, int64_t C, int64_t H, int64_t W, double lambda_dssim, bool want_partials)
@@ -786,7 +782,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> exposure_loss_forward
     Tensor l1 = at::empty({}, f32), ssim = at::empty({}, f32), loss = at::empty({}, f32), dssim = at::empty({}, f32);
     Tensor per_image = at::empty({B}, f32);
     Tensor partials = want_partials ? at::empty({3, B, C, H, W}, f32) : at::empty({0}, f32);
-    Tensor ws = exposure_workspace("exposure_loss_forward", B, C, H, W, dev);
+    Tensor ws = loss_workspace("exposure_loss_forward: invalid shape",
+                               api.r3dgs_exposure_loss_workspace_bytes((int)B, (int)C, (int)H, (int)W), dev);
     if (api.r3dgs_exposure_loss_forward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
                                         opt_ptr<float>(exposure), (int)exposure_per_image, opt_ptr<float>(mask), (int)mask_per_image,
                                         (int)mask_target, (float)lambda_dssim, l1.data_ptr<float>(), ssim.data_ptr<float>(),
@@ -808,7 +805,8 @@ std::tuple<Tensor, Tensor> exposure_loss_backward(const Tensor& img1, const Tens
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
     Tensor dx = at::empty({B, C, H, W}, f32);
     Tensor dE = !want_exposure_grad ? at::empty({0}, f32) : (exposure_per_image ? at::empty({B, 3, 4}, f32) : at::empty({3, 4}, f32));
-    Tensor ws = exposure_workspace("exposure_loss_backward", B, C, H, W, dev);
+    Tensor ws = loss_workspace("exposure_loss_backward: invalid shape",
+                               api.r3dgs_exposure_loss_workspace_bytes((int)B, (int)C, (int)H, (int)W), dev);
     if (api.r3dgs_exposure_loss_backward((int)B, (int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(),
                                          opt_ptr<float>(exposure), (int)exposure_per_image, opt_ptr<float>(mask), (int)mask_per_image,
                                          (int)mask_target, opt_ptr<float>(partials), opt_ptr<float>(grad_loss), (float)coef_l1,

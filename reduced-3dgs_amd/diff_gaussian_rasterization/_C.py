@@ -2025,6 +2025,13 @@ def ssim_window():
     return np.array(w[:], np.float32)
 
 
+def _loss_scratch(what, nbytes, dev):
+    """The scratch tensor of a loss call whose size query said `nbytes`; 0 refuses `what`, "<call>: invalid <size>"."""
+    if nbytes == 0:
+        raise RuntimeError(what)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
+
 def l1_ssim_forward(img1, img2, B, Cc, H, W, lambda_dssim, want_partials, want_map):
     """-> (l1, ssim, loss, dssim, ssim_image[B], ssim_map or empty, partials[3,B,C,H,W] or empty); 0-d tensors for the
     scalars.  One tile kernel + one fixed-order reduction."""
@@ -2038,10 +2045,8 @@ def l1_ssim_forward(img1, img2, B, Cc, H, W, lambda_dssim, want_partials, want_m
     ssim_map = torch.empty((B, Cc, H, W), **f32) if want_map else _NO_TENSOR
     partials = torch.empty((3, B, Cc, H, W), **f32) if want_partials else _NO_TENSOR
     with _on_device(dev):
-        ws_bytes = _lib.r3dgs_l1_ssim_workspace_bytes(B, Cc, H, W)
-        if ws_bytes == 0:
-            raise RuntimeError(f"l1_ssim_forward: invalid shape {B}x{Cc}x{H}x{W}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws = _loss_scratch(f"l1_ssim_forward: invalid shape {B}x{Cc}x{H}x{W}",
+                           _lib.r3dgs_l1_ssim_workspace_bytes(B, Cc, H, W), dev)
         _check(_lib.r3dgs_l1_ssim_forward(B, Cc, H, W, _ptr(img1), _ptr(img2), float(lambda_dssim), _ptr(l1), _ptr(ssim),
                                           _ptr(per_image), _ptr(loss), _ptr(dssim), _ptr(ssim_map), _ptr(partials),
                                           _ptr(ws), _stream()), "l1_ssim_forward")
@@ -2073,10 +2078,7 @@ def l1_forward(x, y):
     n = x.numel()
     out = torch.empty((), dtype=torch.float32, device=dev)
     with _on_device(dev):
-        ws_bytes = _lib.r3dgs_l1_workspace_bytes(n)
-        if ws_bytes == 0:
-            raise RuntimeError(f"l1_forward: invalid element count {n}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws = _loss_scratch(f"l1_forward: invalid element count {n}", _lib.r3dgs_l1_workspace_bytes(n), dev)
         _check(_lib.r3dgs_l1_forward(n, _ptr(x), _ptr(y), _ptr(out), _ptr(ws), _stream()), "l1_forward")
     return out
 
@@ -2124,10 +2126,8 @@ def exposure_loss_forward(img1, img2, exposure, exposure_per_image, mask, mask_p
     with _on_device(dev):
         ws = _workspace
         if ws is None:
-            ws_bytes = _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W)
-            if ws_bytes == 0:
-                raise RuntimeError(f"exposure_loss_forward: invalid shape {B}x{Cc}x{H}x{W}")
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            ws = _loss_scratch(f"exposure_loss_forward: invalid shape {B}x{Cc}x{H}x{W}",
+                               _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W), dev)
         _check(_lib.r3dgs_exposure_loss_forward(B, Cc, H, W, _ptr(img1), _ptr(img2), _ptr(exposure), int(exposure_per_image),
                                                 _ptr(mask), int(mask_per_image), int(mask_target), float(lambda_dssim),
                                                 _ptr(l1), _ptr(ssim), _ptr(per_image), _ptr(loss), _ptr(dssim), _ptr(partials),
@@ -2150,10 +2150,8 @@ def exposure_loss_backward(img1, img2, exposure, exposure_per_image, mask, mask_
     with _on_device(dev):
         ws = _workspace
         if ws is None:
-            ws_bytes = _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W)
-            if ws_bytes == 0:
-                raise RuntimeError(f"exposure_loss_backward: invalid shape {B}x{Cc}x{H}x{W}")
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            ws = _loss_scratch(f"exposure_loss_backward: invalid shape {B}x{Cc}x{H}x{W}",
+                               _lib.r3dgs_exposure_loss_workspace_bytes(B, Cc, H, W), dev)
         _check(_lib.r3dgs_exposure_loss_backward(B, Cc, H, W, _ptr(img1), _ptr(img2), _ptr(exposure), int(exposure_per_image),
                                                  _ptr(mask), int(mask_per_image), int(mask_target), _ptr(partials),
                                                  _ptr(grad_loss), float(coef_l1), float(coef_ssim), _ptr(dx), _ptr(dE),

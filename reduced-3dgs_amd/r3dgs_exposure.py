@@ -18,7 +18,7 @@ device tensors (no CPU path).  Values and gradients are deterministic and the ca
 import torch
 
 from diff_gaussian_rasterization import _C
-from r3dgs_loss import _bchw, _check_pair
+from r3dgs_loss import _bchw, _check_devices, _check_pair
 
 __all__ = ["exposed_l1_dssim", "apply_exposure", "ExposureTable"]
 
@@ -58,17 +58,6 @@ def _check_image(what, image):
         raise TypeError(f"{what}: prediction must be a tensor")
     if image.dim() not in (3, 4) or image.numel() == 0:
         raise ValueError(f"{what}: expected [C,H,W] or [B,C,H,W], got {tuple(image.shape)}")
-
-
-def _check_devices(what, image, **named):
-    """Last of the checks, as in r3dgs_loss._check_pair: everything on the prediction's device, which is not the host."""
-    for name, t in named.items():
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: {name} is a host tensor; the fused loss needs device tensors (no CPU path)")
-        if t.device != image.device:
-            raise ValueError(f"{what}: tensors on {image.device} and {t.device}")
 
 
 class _ExposedL1DSSIM(torch.autograd.Function):

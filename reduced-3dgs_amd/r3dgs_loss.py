@@ -18,6 +18,17 @@ _EMPTY = torch.Tensor([])
 _MEAN, _PER_IMAGE, _MAP = 0, 1, 2   # upstream gradient of the SSIM map: of its mean, of the per-image means, of the map
 
 
+def _check_devices(what, first, **named):
+    """Every tensor of `named` that is not None on `first`'s device, which is not the host."""
+    for name, t in named.items():
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{what}: {name} is a host tensor; the fused loss needs device tensors (no CPU path)")
+        if t.device != first.device:
+            raise ValueError(f"{what}: tensors on {first.device} and {t.device}")
+
+
 def _check_pair(what, a, b, images=True):
     for name, t in (("prediction", a), ("target", b)):
         if not isinstance(t, torch.Tensor):
@@ -33,11 +44,7 @@ def _check_pair(what, a, b, images=True):
     if b.requires_grad:
         raise RuntimeError(f"{what}: the target requires grad; the fused loss differentiates with respect to the prediction "
                            "only (pass target.detach())")
-    for name, t in (("prediction", a), ("target", b)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: {name} is a host tensor; the fused loss needs device tensors (no CPU path)")
-    if a.device != b.device:
-        raise ValueError(f"{what}: tensors on {a.device} and {b.device}")
+    _check_devices(what, a, prediction=a, target=b)
 
 
 def _bchw(t):
