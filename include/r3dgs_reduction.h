@@ -32,12 +32,21 @@ int r3dgs_min_pixel_size(int P, int n_cameras, const float* w2ndc, const float* 
 /* For every (Gaussian, candidate neighbour) pair: does the sphere of radius sphere_radius[i] around Gaussian i
  * intersect the neighbour's ellipsoid (redundancy_score.cu:121-159; the rotation used is Gaussian i's own, as in
  * the reference).  neighbours: int32[P,knn]; redundancy[P] (count of intersecting neighbours) and
- * mask[P,knn] (one byte per pair, 0/1) are written. */
+ * mask[P,knn] (one byte per pair, 0/1) are written; knn == 0 writes redundancy = 0 and touches nothing else.
+ *
+ * NO NEIGHBOUR: a neighbour index outside [0, P) -- the -1 that r3dgs_knn leaves in unfilled slots when P - 1 < K, which
+ * the reference's caller (scene/__init__.py:143-174) hands straight on -- is no neighbour.  The pair gets mask 0, is not
+ * counted, and nothing is read through the index.  r3dgs_min_redundancy never scatters through such a pair, whatever its
+ * mask byte says.  Results for indices inside [0, P) are unaffected.  The reference does not guard this: its
+ * sphereEllipsoidIntersectionCUDA (redundancy_score.cu:144-146) reads means3D[neighbour_id] and scales[neighbour_id], and
+ * its findMinimumRedundancyValueCUDA (:23-24) does atomicMin(&minimum_redundancy_values[neighbour_idx], ...), with the
+ * index as found -- out of bounds for -1.  This is a deliberate departure from it. */
 int r3dgs_sphere_ellipsoid_intersection(int P, int knn, const float* means3D, const float* scales,
                                         const float* rotations, const int* neighbours, const float* sphere_radius,
                                         int* redundancy, uint8_t* mask, void* stream);
 
-/* min_redundancy[n] = min(P, min over pairs (i, n) with mask set of redundancy[i]) (redundancy_score.cu:6-27). */
+/* min_redundancy[n] = min(P, min over pairs (i, n) with mask set of redundancy[i]) (redundancy_score.cu:6-27); pairs
+ * whose index is outside [0, P) are skipped (NO NEIGHBOUR, above).  All P entries of min_redundancy are written. */
 int r3dgs_min_redundancy(int P, int knn, const int* redundancy, const int* neighbours, const uint8_t* mask,
                          int* min_redundancy, void* stream);
 

@@ -82,9 +82,12 @@ def rotation_columns(rot):
 
 def sphere_ellipsoid_intersection(means3D, scales, rotations, nbr, radius, knn, ambig_rel=1e-5):
     """-> (count int32[P,1], mask bool[P,knn], ambig bool[P,knn]).  The rotation is the QUERY's own
-    (`R[idx]`, redundancy_score.cu:147), the scales are the neighbour's."""
+    (`R[idx]`, redundancy_score.cu:147), the scales are the neighbour's.  An index outside [0, P) is no neighbour
+    (include/r3dgs_reduction.h; the reference reads out of bounds there): mask False, not counted, never ambiguous."""
     P = means3D.shape[0]
     nbr = nbr.reshape(P, knn)
+    valid = (nbr >= 0) & (nbr < P)
+    nbr = np.where(valid, nbr, 0)
     c0, c1, c2 = rotation_columns(rotations)
     xyz = means3D.astype(F)
     diff = xyz[:, None, :] - xyz[nbr]                                  # [P,k,3]
@@ -98,18 +101,19 @@ def sphere_ellipsoid_intersection(means3D, scales, rotations, nbr, radius, knn, 
     with np.errstate(all="ignore"):
         inv = (F(1.0) / (aug * aug).astype(F)).astype(F)
         val = ((num[..., 0] * inv[..., 0] + num[..., 1] * inv[..., 1]) + num[..., 2] * inv[..., 2]).astype(F)
-    mask = val < F(1.0)
-    ambig = np.abs(val - 1.0) < ambig_rel
+    mask = (val < F(1.0)) & valid
+    ambig = (np.abs(val - 1.0) < ambig_rel) & valid
     return mask.sum(1).astype(np.int32).reshape(P, 1), mask, ambig
 
 
 def min_redundancy(redundancy, nbr, mask, knn):
-    """-> int32[P,1], initial value P, scatter-min of the source's value onto each intersecting neighbour."""
+    """-> int32[P,1], initial value P, scatter-min of the source's value onto each intersecting neighbour.  A pair whose
+    index is outside [0, P) is skipped whatever its mask says (include/r3dgs_reduction.h)."""
     P = redundancy.shape[0]
     out = np.full((P,), P, np.int32)
     nbr = nbr.reshape(P, knn)
     src = np.broadcast_to(redundancy.reshape(P, 1).astype(np.int32), (P, knn))
-    m = mask.reshape(P, knn)
+    m = mask.reshape(P, knn).astype(bool) & (nbr >= 0) & (nbr < P)
     np.minimum.at(out, nbr[m], src[m])
     return out.reshape(P, 1)
 

@@ -81,10 +81,13 @@ __global__ __launch_bounds__(kBlock) void intersection_kernel(int P, int knn, co
     const long long pair = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool live = pair < total;
     bool hit = false;
-    int g = 0;
+    int g = 0, n = -1;
     if (live) {
         g = (int)(pair / knn);
-        const int n = neighbours[pair];
+        n = neighbours[pair];
+    }
+    // an index outside [0, P) is no neighbour (r3dgs_reduction.h): mask 0, not counted, nothing read through it
+    if ((unsigned)n < (unsigned)P) {
         const float r = rotations[4 * g], x = rotations[4 * g + 1], y = rotations[4 * g + 2], z = rotations[4 * g + 3];
         const float d0 = means3D[3 * g] - means3D[3 * n];
         const float d1 = means3D[3 * g + 1] - means3D[3 * n + 1];
@@ -97,8 +100,8 @@ __global__ __launch_bounds__(kBlock) void intersection_kernel(int P, int knn, co
         const float l2 = ((2.f * (x * z + r * y)) * d0 + (2.f * (y * z - r * x)) * d1) + (1.f - 2.f * (x * x + y * y)) * d2;
         const float v = ((l0 * l0) * (1.f / (a0 * a0)) + (l1 * l1) * (1.f / (a1 * a1))) + (l2 * l2) * (1.f / (a2 * a2));
         hit = v < 1.f;
-        mask[pair] = hit ? 1 : 0;
     }
+    if (live) mask[pair] = hit ? 1 : 0;
     // count per Gaussian: lanes of one Gaussian form a contiguous segment of the wave
     const unsigned long long hits = __ballot(hit);
     if (live) {
@@ -125,21 +128,23 @@ __global__ __launch_bounds__(kBlock) void zero_cut_runs_kernel(int P, int knn, i
     if ((a >> 6) != (b >> 6)) redundancy[g] = 0;
 }
 
-// redundancy_score.cu:6-27, one lane per pair.
+// redundancy_score.cu:6-27, one lane per pair.  The reference scatters through whatever index the row holds; here an
+// index outside [0, P) (distIndex2's -1 in an unfilled slot) is skipped.
 __global__ __launch_bounds__(kBlock) void fill_int_kernel(int n, int v, int* __restrict__ out)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < n) out[i] = v;
 }
-__global__ __launch_bounds__(kBlock) void min_redundancy_kernel(long long total, int knn,
-                                                                const int* __restrict__ redundancy,
+__global__ __launch_bounds__(kBlock) void min_redundancy_kernel(int P, int knn, const int* __restrict__ redundancy,
                                                                 const int* __restrict__ neighbours,
                                                                 const uint8_t* __restrict__ mask,
                                                                 int* __restrict__ min_redundancy)
 {
     const long long pair = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (pair >= total || !mask[pair]) return;
-    atomicMin(&min_redundancy[neighbours[pair]], redundancy[pair / knn]);
+    if (pair >= (long long)P * knn || !mask[pair]) return;
+    const int n = neighbours[pair];
+    if ((unsigned)n >= (unsigned)P) return;  // no neighbour (r3dgs_reduction.h), whatever the mask byte says
+    atomicMin(&min_redundancy[n], redundancy[pair / knn]);
 }
 
 // densification statistics of one view, for the view-parallel exchange (multiview.py)
@@ -276,8 +281,8 @@ int r3dgs_min_redundancy(int P, int knn, const int* redundancy, const int* neigh
         hipStream_t s = static_cast<hipStream_t>(stream);
         fill_int_kernel<<<grid_for(P), kBlock, 0, s>>>(P, P, min_redundancy);
         if (knn)
-            min_redundancy_kernel<<<grid_for((long long)P * knn), kBlock, 0, s>>>((long long)P * knn, knn, redundancy,
-                                                                                    neighbours, mask, min_redundancy);
+            min_redundancy_kernel<<<grid_for((long long)P * knn), kBlock, 0, s>>>(P, knn, redundancy, neighbours, mask,
+                                                                                    min_redundancy);
         r3::check_launch("min redundancy", s, false);
         return 0;
     });
